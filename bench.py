@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Train-step throughput of the detection hot path on MI355X (BASELINE.json configs[1]):
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns the N ranks itself, self_launch())
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 without a launcher: spawns the N ranks itself, self_launch())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 step = forward + balanced BCE + zero_grad + backward (+ RCCL gradient all-reduce, overlapped) + Adam on a batch of
@@ -607,6 +607,25 @@ def plumbing(args, world, rank):
 
 
 # ------------------------------------------------------------------------------------------------ detection
+def dump_outputs(d, loss, model, opt):
+    """--dump-outputs: what a caller of the timed train step holds after its last call -- the returned loss, the model's parameters and
+    BatchNorm buffers, and the Adam moments -- one .npy per tensor (float32; loss and integer counters float64).  The model has ~0.62 M
+    parameters, so this is ~7.5 MB whatever the batch or tile size."""
+    os.makedirs(d, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach().cpu()
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        np.save(os.path.join(d, name + ".npy"), (t.double() if wide else t.float()).numpy())
+
+    save("loss", loss.reshape(1).double())
+    for k, v in model.state_dict().items():
+        save(f"state.{k}", v)
+    for k, p in model.named_parameters():
+        for m in ("exp_avg", "exp_avg_sq"):
+            save(f"adam_{m}.{k}", opt.state[p][m])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -628,6 +647,8 @@ def main():
     ap.add_argument("--rec-width", type=int, default=400)
     ap.add_argument("--rec-config5", action="store_true", help="(default since round 4) time the width-bucketed variable-width CRNN workload")
     ap.add_argument("--no-rec-config5", action="store_true", help="skip the width-bucketed variable-width CRNN workload (BASELINE configs[4] per-rank share)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed detection step produced as DIR/<name>.npy "
+                    "(loss, model state dict, Adam moments; float32 / float64, ~7.5 MB): compares two builds output for output")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:  # plain `python bench.py --gpus N`: spawn the N ranks ourselves
@@ -665,7 +686,7 @@ def main():
 
     ddp_info = {}
 
-    def run_det(dtype_name, warmup, steps, roofline, use_ddp=None, ref_style=False):
+    def run_det(dtype_name, warmup, steps, roofline, use_ddp=None, ref_style=False, dump_dir=None):
         use_ddp = distributed if use_ddp is None else use_ddp
         act = torch.bfloat16 if dtype_name == "bf16" else torch.float32
         torch.manual_seed(1234)
@@ -741,6 +762,8 @@ def main():
 
             timing = {f: [(_Dur(float(dur[a:b].sum())), None, args) for a, b, args in lst] for f, lst in recs.items()}
         final_loss = float(loss) if ref_style else float(loss.item())
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, loss, model, opt)
         if use_ddp:
             ex = net.bucketer.exposed_ms()
             nflt = sum(p.numel() for p in model.parameters())
@@ -767,7 +790,7 @@ def main():
         torch.cuda.empty_cache()
         return dt, final_loss, warm, timing
 
-    dt, final_loss, warm, timing = run_det(args.dtype, args.warmup, args.steps, not args.no_roofline)
+    dt, final_loss, warm, timing = run_det(args.dtype, args.warmup, args.steps, not args.no_roofline, dump_dir=args.dump_outputs)
     ms = dt / args.steps * 1e3
     value = B * world * args.steps / dt
     sz = 2 if args.dtype == "bf16" else 4
