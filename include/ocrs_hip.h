@@ -373,6 +373,31 @@ int ocrs_collate_pad(const void* packed, const long long* offs, const int* width
 int ocrs_resize_aa(const float* in, float* ws, float* out, int planes, int h, int w, int oh, int ow, hipStream_t st);
 long ocrs_resize_aa_ws_floats(int planes, int h, int ow);
 
+/* ------------------------------------------------------------------ validation metrics ------- */
+/* Word-level metrics of the detection test() loop (ocrs_models/train_detection.py:177-184) on the device, restating the host contract
+ * ocrs_models_amd/postprocess.py (reference postprocess.py:11-36 extract_cc_quads, :102-187 box_match_metrics); csrc/postprocess.hip.
+ * Masks are (B, 1, H, W) / (B, H, W): kind 0 = fp32, foreground = value > threshold; kind 1 = uint8 / bool, foreground = non-zero.
+ * Components are 8-connected and numbered in raster order of their first pixel (scipy.ndimage.label's order).  Nothing here
+ * synchronises the stream: counts stay on the device and every launch is sized from (B, H, W).  ws: caller-owned device memory of the
+ * size the matching *_ws_bytes query returns (0 = shape not supported: H or W < 1, or per-image indices beyond 32 bits).
+ * ocrs_cc_quads_capacity: the most components an H x W image can hold, ceil(H/2) * ceil(W/2). */
+long ocrs_cc_quads_capacity(int H, int W);
+long ocrs_cc_quads_ws_bytes(int B, int H, int W);
+/* ncomp [B] int; quads [B][capacity][4][2] fp32 (x, y): the min-area rectangle of each component's pixel-centre hull (extract_cc_quads);
+ * rows past ncomp[b] are left untouched.  labels (nullable) [B][H][W] int: 0 = background, component id + 1 (scipy.ndimage.label's array). */
+int ocrs_cc_quads(const void* mask, int kind, float threshold, int B, int H, int W, int* ncomp, float* quads, int* labels, void* ws,
+                  hipStream_t st);
+/* box_match_metrics per image: pred_quads [B][cap_p][4][2], target_quads [B][cap_t][4][2] fp32 with device counts n_pred / n_target [B];
+ * out [B][4] fp64 = precision | recall | merged_frac | split_frac.  Targets are bucketed by floor(bbox x-min) into nbkt unit-wide
+ * columns starting at x = 0 (values outside go to the end buckets; nbkt = 1 compares every pair). */
+long ocrs_box_match_ws_bytes(int B, long cap_t, int nbkt);
+int ocrs_box_match_metrics(const float* pred_quads, const int* n_pred, long cap_p, const float* target_quads, const int* n_target, long cap_t, int B,
+                           int nbkt, double* out, void* ws, hipStream_t st);
+/* mask_metrics end to end: ocrs_cc_quads of both batches + ocrs_box_match_metrics; out [B][4] fp64 as above. */
+long ocrs_mask_metrics_ws_bytes(int B, int H, int W);
+int ocrs_mask_metrics(const void* pred, int pred_kind, const void* target, int target_kind, float threshold, int B, int H, int W, double* out, void* ws,
+                      hipStream_t st);
+
 /* ------------------------------------------------------------------ optimiser ---------------- */
 /* table [nt][5] int64 {param, grad, exp_avg, exp_avg_sq, numel}; chunks [nchunks][2] int32 {tensor, chunk of ocrs_opt_chunk()}. */
 int ocrs_opt_chunk(void);

@@ -11,6 +11,17 @@ Host-side numpy, like the reference's own CPU post-processing -- this is not par
   another component (RETR_EXTERNAL drops them, they are kept here).
 * ``box_match_metrics``: the quads are convex, so intersection areas come from Sutherland-Hodgman clipping and union = a + b - intersection
   (shapely's general polygon overlay is not needed); the matching rules and the four reported numbers are the reference's.
+
+The same contract on the GPU (csrc/postprocess.hip, C ABI ``ocrs_cc_quads`` / ``ocrs_box_match_metrics`` / ``ocrs_mask_metrics``):
+
+* ``batch_mask_metrics(pred, target)``: ``mask_metrics`` of every image of a device batch as a (B, 4) fp64 device tensor, without a host
+  sync -- what ``train_detection.test(..., metrics_fn="device")`` uses.
+* ``extract_cc_quads_device(mask)``: the quads of one device mask, on the device (one sync, to read the count).
+* ``box_match_metrics_device(pred_quads, target_quads)``: ``box_match_metrics`` of two device quad sets.
+
+Components, their numbering and the hull vertex sequence are identical to the host's (integer work); the calipers, clipping and areas
+repeat the host's fp64 operations in the host's order, so quads agree to rounding and the four counts agree exactly in practice (DESIGN.md
+"Device validation metrics" says where bit-identity is and is not guaranteed).
 """
 from __future__ import annotations
 
@@ -168,3 +179,112 @@ def box_match_metrics(pred: torch.Tensor, target: torch.Tensor) -> dict[str, flo
 def mask_metrics(bin_pred_mask: torch.Tensor, bin_target_mask: torch.Tensor) -> dict[str, float]:
     """what train_detection.py:177-184 computes per image: quads of both masks, then the box-match metrics"""
     return box_match_metrics(extract_cc_quads(bin_pred_mask), extract_cc_quads(bin_target_mask))
+
+
+# ------------------------------------------------------------------ device path (csrc/postprocess.hip) ------------------------------------
+def _mask_arg(mask: torch.Tensor, threshold: float):
+    """(B, H, W) view of a device mask and its kind for the C ABI: 0 = fp32 (> threshold), 1 = uint8 / bool (non-zero)"""
+    if not mask.is_cuda:
+        raise RuntimeError("device post-processing needs a GPU tensor (the host path is extract_cc_quads / mask_metrics)")
+    if mask.dtype in (torch.uint8, torch.bool):
+        m, kind = mask.contiguous().view(torch.uint8), 1
+    else:
+        m, kind = mask.contiguous().to(torch.float32), 0
+    return m, kind
+
+
+def extract_cc_quads_device(mask: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+    """``extract_cc_quads`` on the GPU: quads [N][4][2] fp32 on the mask's device, same components in the same (raster) order.
+
+    ``mask`` is H x W or 1 x H x W on the device; fp32 masks are binarised with ``> threshold`` (``binarize_mask``), uint8 / bool masks
+    with ``!= 0``.  Reading N back is this function's one host synchronisation."""
+    from ._lib import lib, ptr
+
+    if mask.dim() > 2:
+        if mask.dim() != 3 or mask.shape[0] != 1:
+            raise ValueError("Expected mask to be an HxW or 1xHxW tensor")
+        mask = mask[0]
+    H, W = mask.shape
+    m, kind = _mask_arg(mask, threshold)
+    L = lib()
+    ws_bytes = L.cc_quads_ws_bytes(1, H, W)
+    if ws_bytes <= 0:
+        raise ValueError(f"mask shape {H}x{W} not supported")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=m.device)
+    n = torch.empty(1, dtype=torch.int32, device=m.device)
+    quads = torch.empty(L.cc_quads_capacity(H, W), 4, 2, dtype=torch.float32, device=m.device)
+    L.cc_quads(ptr(m), kind, float(threshold), 1, H, W, ptr(n), ptr(quads), None, ptr(ws))
+    return quads[: int(n.item())]
+
+
+def label_components_device(masks: torch.Tensor, threshold: float = 0.5) -> tuple[torch.Tensor, torch.Tensor]:
+    """The labelling of the device path: ``scipy.ndimage.label`` with 8-connectivity for every image of a (B, 1, H, W) / (B, H, W) device
+    batch -> (labels (B, H, W) int32, 0 = background, components numbered from 1 in raster order of their first pixel; counts (B,) int32),
+    both on the device, no sync."""
+    from ._lib import lib, ptr
+
+    if masks.dim() == 4:
+        if masks.shape[1] != 1:
+            raise ValueError("Expected a (B, 1, H, W) or (B, H, W) batch")
+        masks = masks[:, 0]
+    if masks.dim() != 3:
+        raise ValueError("Expected a (B, 1, H, W) or (B, H, W) batch")
+    B, H, W = masks.shape
+    m, kind = _mask_arg(masks, threshold)
+    L = lib()
+    ws_bytes = L.cc_quads_ws_bytes(B, H, W)
+    if ws_bytes <= 0:
+        raise ValueError(f"batch shape {B}x{H}x{W} not supported")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=m.device)
+    n = torch.empty(B, dtype=torch.int32, device=m.device)
+    quads = torch.empty(B, L.cc_quads_capacity(H, W), 4, 2, dtype=torch.float32, device=m.device)
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
+    L.cc_quads(ptr(m), kind, float(threshold), B, H, W, ptr(n), ptr(quads), ptr(labels), ptr(ws))
+    return labels, n
+
+
+def box_match_metrics_device(pred: torch.Tensor, target: torch.Tensor) -> dict[str, float]:
+    """``box_match_metrics`` of two device quad sets [N][4][2] (fp32; every pair is a candidate, so this is for small sets -- the mask
+    path ``batch_mask_metrics`` buckets the targets).  Returns the host function's dict (one sync to read it)."""
+    from ._lib import lib, ptr
+
+    dev = pred.device if pred.is_cuda else target.device
+    if not dev.type == "cuda":
+        raise RuntimeError("box_match_metrics_device needs GPU tensors")
+    P = pred.to(dev, torch.float32).reshape(-1, 4, 2).contiguous()
+    T = target.to(dev, torch.float32).reshape(-1, 4, 2).contiguous()
+    counts = torch.tensor([P.shape[0], T.shape[0]], dtype=torch.int32).to(dev, non_blocking=True)
+    P = P if P.shape[0] else torch.zeros(1, 4, 2, device=dev)
+    T = T if T.shape[0] else torch.zeros(1, 4, 2, device=dev)
+    L = lib()
+    ws = torch.empty(L.box_match_ws_bytes(1, T.shape[0], 1), dtype=torch.uint8, device=dev)
+    out = torch.empty(1, 4, dtype=torch.float64, device=dev)
+    L.box_match_metrics(ptr(P), ptr(counts), P.shape[0], ptr(T), counts.data_ptr() + 4, T.shape[0], 1, 1, ptr(out), ptr(ws))
+    return dict(zip(METRIC_KEYS, out[0].tolist()))
+
+
+METRIC_KEYS = ("precision", "recall", "merged_frac", "split_frac")
+
+
+def batch_mask_metrics(pred: torch.Tensor, target: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+    """``mask_metrics`` of every image of a batch on the GPU: (B, 4) fp64 on the device, columns ``METRIC_KEYS``.
+
+    ``pred`` / ``target``: (B, 1, H, W) or (B, H, W) device tensors, fp32 (binarised with ``> threshold``, ``binarize_mask``) or uint8 /
+    bool (non-zero).  No host synchronisation: component counts stay on the device, the workspace is sized from (B, H, W)."""
+    from ._lib import lib, ptr
+
+    if pred.shape != target.shape or pred.dim() not in (3, 4) or (pred.dim() == 4 and pred.shape[1] != 1):
+        raise ValueError(f"expected two (B, 1, H, W) or (B, H, W) masks of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    B, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]
+    out = torch.empty(B, 4, dtype=torch.float64, device=pred.device)
+    if B == 0:
+        return out
+    p, pk = _mask_arg(pred, threshold)
+    t, tk = _mask_arg(target, threshold)
+    L = lib()
+    ws_bytes = L.mask_metrics_ws_bytes(B, H, W)
+    if ws_bytes <= 0:
+        raise ValueError(f"mask shape {H}x{W} not supported")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pred.device)
+    L.mask_metrics(ptr(p), pk, ptr(t), tk, float(threshold), B, H, W, ptr(out), ptr(ws))
+    return out

@@ -69,24 +69,37 @@ def test(device, dataloader, model, loss_fn=balanced_cross_entropy_loss, metrics
     the CPU per image exactly where the reference does (train_detection.py:177-184) by ``postprocess.mask_metrics`` -- a numpy
     restatement of the reference's cv2 + shapely post-processing (postprocess.py:11-36, 102-187; neither library is installed here, so
     its parity is unpinned: see ocrs_models_amd/postprocess.py).  ``metrics_fn(bin_pred_mask_cpu, bin_target_mask_cpu) -> dict`` replaces
-    it (e.g. the reference's own functions); ``metrics_fn=None`` skips the metrics (empty dict).
+    it (e.g. the reference's own functions); ``metrics_fn=None`` skips the metrics (empty dict).  ``metrics_fn="device"`` computes the same
+    four metrics on the GPU (``postprocess.batch_mask_metrics`` on the device-resident prediction and target, running sums on the device):
+    no per-batch host copy, and the loop's one host sync returns the same dict as the default path.
     """
-    if metrics_fn == "default":
+    device_metrics = isinstance(metrics_fn, str) and metrics_fn == "device"
+    if isinstance(metrics_fn, str) and metrics_fn == "default":
         from .postprocess import mask_metrics as metrics_fn
+    elif device_metrics:
+        from .postprocess import METRIC_KEYS, batch_mask_metrics
     model.eval()
     n_batches = 0
+    n_images = 0
     metrics = []
     with torch.inference_mode():
         total = torch.zeros((), device=device)
+        msum = torch.zeros(4, dtype=torch.float64, device=device) if device_metrics else None
         for batch in dataloader:
             img = batch["image"].to(device, non_blocking=True)
             masks = batch["text_mask"].to(device, non_blocking=True)
             pred_masks = model(img)
             total += loss_fn(pred_masks, masks)
             n_batches += 1
-            if metrics_fn is not None:
+            if device_metrics:
+                msum += batch_mask_metrics(pred_masks, masks).sum(0)
+                n_images += pred_masks.shape[0]
+            elif metrics_fn is not None:
                 bin_pred_masks = binarize_mask(pred_masks).cpu()
                 bin_masks = binarize_mask(masks).cpu()
                 for item_index, bin_pred_mask in enumerate(bin_pred_masks):
                     metrics.append(metrics_fn(bin_pred_mask, bin_masks[item_index]))
+    if device_metrics:
+        vals = torch.cat([total.double().reshape(1), msum]).tolist()  # the one host sync of the loop
+        return vals[0] / max(n_batches, 1), ({k: v / n_images for k, v in zip(METRIC_KEYS, vals[1:])} if n_images else {})
     return float(total.item()) / max(n_batches, 1), get_metric_means(metrics)
