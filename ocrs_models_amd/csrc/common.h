@@ -410,8 +410,6 @@ static inline int env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 static inline int persistent_grid(long ntiles, int blocks_per_cu) {
-    static const int bpc_env = env_int("OCRS_BPC", 0);
-    if (bpc_env > 0) blocks_per_cu = bpc_env;
     long cap = (long)kNumCU * blocks_per_cu;
     long g = ntiles < cap ? ntiles : cap;
     if (g >= 8) g &= ~7L;

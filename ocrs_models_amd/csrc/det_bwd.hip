@@ -473,13 +473,11 @@ __global__ __launch_bounds__(256, ((CIN > 32 || COUT > 32) && CIN * COUT <= 8192
 // kernel computes (sum ghat and sum ghat*(z - mean), ghat = dx~ * [bn(z) > 0]): the input x is that producer's raw z, so its
 // k_bn_bwd_reduce pass over (g, z) -- 2.1 ms of the step -- disappears.  Partials go to workspace rows 9..10 (stat_mask bit 0 / 1 =
 // source a / b wants them); k_dw_partials_reduce scales by rstd and adds them to the producers' gsum [2][C] (fp64).
-#ifndef OCRS_DW_BLOCKS
-#define OCRS_DW_BLOCKS 3  // 168 VGPRs: the per-channel load transform lives in LDS (3 vector reads per tile) instead of 12 registers, and the
-                          // final-reduction scratch aliases the tiles, so that three blocks fit a CU (registers AND LDS).  Applies to the
-                          // bf16 STATS variant (every launch of a training step); the fp32 / no-stats variants would spill and keep 2
-#endif
+// Launch bounds: 3 blocks per CU for the bf16 STATS variant (every launch of a training step) at 168 VGPRs: the per-channel load transform
+// lives in LDS (3 vector reads per tile) instead of 12 registers, and the final-reduction scratch aliases the tiles, so that three blocks fit a
+// CU (registers AND LDS).  The fp32 / no-stats variants would spill and keep 2.
 template <class T, int CG, bool STATS>
-__global__ __launch_bounds__(256, (Elem<T>::is_bf16 && STATS) ? OCRS_DW_BLOCKS : 2) void k_dw_bwd(Src2<T> x, const float* __restrict__ tra, const float* __restrict__ trb,
+__global__ __launch_bounds__(256, (Elem<T>::is_bf16 && STATS) ? 3 : 2) void k_dw_bwd(Src2<T> x, const float* __restrict__ tra, const float* __restrict__ trb,
                                                 const float* __restrict__ wdw /*master [C][9]*/, const T* __restrict__ du,
                                                 T* __restrict__ gxa, T* __restrict__ gxb, float* __restrict__ dwdw /*[C][9]*/,
                                                 float* __restrict__ ws /*[gridDim.x][C][9 (+2)] block partials or null*/,
@@ -1431,10 +1429,7 @@ static inline int cg_grid(long items) { return ew_grid(items); }
 // wgrad-carrying persistent grids: each block flushes a weight-gradient tile with atomics, so make every block
 // chew through >= 8 pixel tiles when there are enough of them.
 static inline int wgrad_grid(long ntiles, int cap_blocks) {
-    static const int cap_env = env_int("OCRS_WGRAD_CAP", 0);
-    if (cap_env > 0) cap_blocks = cap_env;
-    static const int tpb = env_int("OCRS_WGRAD_TPB", 4);  // minimum tiles per block (each block flushes one full weight-gradient partial)
-    long g = ntiles / tpb;
+    long g = ntiles / 4;  // at least 4 tiles per block (each block flushes one full weight-gradient partial)
     if (g < 1) g = 1;
     if (g > cap_blocks) g = cap_blocks;
     if (g >= 8) g &= ~7L;
@@ -1454,7 +1449,7 @@ int ocrs_bn_bwd_reduce(const void* g1, const void* g2, int pooled, const void* z
     // every block ends with 2C fp64 atomics onto the same addresses: at the deep levels (tens of thousands of pixels) give each thread
     // at least 8 items instead of launching 2048 nearly idle blocks (those launches were 60 us of pure flush)
     long gl = (P * (C / 8) + 256 * 8 - 1) / (256 * 8);
-    static const int bpc = env_int("OCRS_BNR_BPC", 2);  // blocks per CU: every block ends in 2 C same-address fp64 atomics (~11 ns each, serial per address: 73 -> 54 us at level 1)
+    const int bpc = 2;  // blocks per CU: every block ends in 2 C same-address fp64 atomics (~11 ns each, serial per address: 73 -> 54 us at level 1)
     const int grid = (int)(gl < 8 ? 8 : (gl > kNumCU * bpc ? kNumCU * bpc : gl));
     const size_t smem = (2 * C + 256 * 16) * sizeof(float);
     if (dtype == 1) {
@@ -1516,13 +1511,9 @@ static int launch_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const f
 }
 extern "C" {
 
-#ifdef OCRS_PW_ONLY_16  // (compile-time experiments: tools/kres.py with KRES_FLAGS=-DOCRS_PW_ONLY_16)
-#define PW_BWD_COMBOS(X) X(16, 16)
-#else
 #define PW_BWD_COMBOS(X) \
     X(8, 8) X(8, 16) X(16, 16) X(16, 32) X(32, 32) X(32, 64) X(64, 64) X(64, 128) X(128, 128) X(128, 256) X(256, 256) X(256, 128) X(128, 64) \
         X(64, 32) X(32, 16) X(16, 8)
-#endif
 
 // Pointwise-conv backward of a DepthwiseConv block: du = Wpw^T dz (written, [P][Cin]); dwpw += u^T dz (accumulated, master layout
 // [Cout][Cin]); dz is formed on the fly from (g1 [+g2], z, bn, coef), u is recomputed from the block input.
@@ -1537,16 +1528,11 @@ long det_pw2_ws_floats(int Cin, int Cout, int N, int H, int W);
 int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
                    int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
                    int H, int W, int ldu, int ldw, hipStream_t st);
-// det_pw8.hip: eight-wave kernel for the deep levels (bf16, Cin, Cout in {64, 128, 256}); same tiling and workspace rule as k_pw_bwd
-long det_pw8_supported(int Cin, int Cout, int dtype);
 long det_pwb_supported(int Cin, int Cout, int dtype);  // det_pwb.hip
 int det_pwb_gx(int Cin, int Cout, int N, int H, int W, int pooled);
 int det_pwb_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
                    int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
                    int H, int W, const BnFin* fin, hipStream_t st);
-int det_pw8_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
-                   int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
-                   int H, int W, int gx, hipStream_t st);
 // a 64-channel concat input (32 | 32) is handled as two k_pw_bwd2<32, Cout> launches, one per source (see ocrs_pw_bwd)
 static bool pw2_split_ok(int Ca, int Cb, int Cout, int dtype) { return Ca == 32 && Cb == 32 && det_pw2_supported(32, Cout, dtype); }
 
@@ -1578,11 +1564,9 @@ int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
     OCRS_CHECK_ARG((Cb == 0) == (xb == nullptr));
     const int Cin = Ca + Cb;
     OCRS_CHECK_ARG((long)N * H * W < (1L << 31));
-    static const int use_pw2 = env_int("OCRS_PW2", 1);
-    if (use_pw2 && det_pw2_supported(Cin, Cout, dtype))
+    if (det_pw2_supported(Cin, Cout, dtype))
         return det_pw2_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, Cin, Cin, st);
-    static const int use_split = env_int("OCRS_PW2_SPLIT", 1);
-    if (use_pw2 && use_split && pw2_split_ok(Ca, Cb, Cout, dtype)) {
+    if (pw2_split_ok(Ca, Cb, Cout, dtype)) {
         // cat(32 | 32) -> Cout: z = Wpw[:, :32] u_a + Wpw[:, 32:] u_b, so du and dWpw separate by source; dz is the same for both.  Two launches of the
         // tuned two-pixel kernel (each re-reads g and z: 512 instead of 384 B per pixel) beat the generic 64-channel path (392 -> ~270 us at
         // level 2).  Per half: depthwise weights [32][9], packed W^T fragments (M tiles 2h, 2h+1), du / dWpw columns 32h.., row strides 64.
@@ -1596,13 +1580,6 @@ int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
     }
     if (det_pwb_supported(Cin, Cout, dtype))  // deep levels, up to 64 input channels: a whole tile in three barriers (det_pwb.hip)
         return det_pwb_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, nullptr, st);
-    if (det_pw8_supported(Cin, Cout, dtype)) {
-#define X(CI, CO)                 \
-    if (Cin == CI && Cout == CO)  \
-        return det_pw8_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, pw_bwd_gx<CI, CO>(N, H, W), st);
-        PW_BWD_COMBOS(X)
-#undef X
-    }
 #define X(CI, CO)                                                                                                                         \
     if (Cin == CI && Cout == CO)                                                                                                          \
         return dtype == 1 ? launch_pw_bwd<bf16, CI, CO>(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, N, H, W, st) \
@@ -1631,14 +1608,12 @@ int ocrs_pw_bwd_fin(const void* xa, const void* xb, int Ca, int Cb, const float*
 
 // Depthwise-conv backward: gxa/gxb (either may be null) receive dL/dx~ split at channel Ca; dwdw accumulated in master layout [C][1][3][3].
 static void dw_bwd_grid(int C, int N, int H, int W, int& gx, int& gy, int& cg) {
-    static const int cg_max = env_int("OCRS_DW_CG", 4);  // channel groups (of 8) per block: 4 -> 8x4-pixel tiles, 2 -> 8x8, 1 -> 8x16
-    cg = C / 8 < cg_max ? C / 8 : cg_max;
+    cg = C / 8 < 4 ? C / 8 : 4;  // channel groups (of 8) per block: 4 -> 8x4-pixel tiles, 2 -> 8x8, 1 -> 8x16
     gy = C / (cg * 8);
     const Tiling2 tg = make_tiling2(N, H, W, 32 / cg, 8);
     // 3 blocks per CU are resident (k_dw_bwd's launch bounds): a grid of exactly that many blocks (all y-slabs together) has no partial last
     // round -- with 8 per CU the 2048 blocks ran as 2.67 rounds of 768
-    static const int bpc = env_int("OCRS_DW_BPC", 3);
-    gx = persistent_grid(tg.ntiles, bpc / gy > 0 ? bpc / gy : 1);
+    gx = persistent_grid(tg.ntiles, 3 / gy > 0 ? 3 / gy : 1);
 }
 // ws: ocrs_dw_bwd_ws_floats() floats (per-block partials of dwdw, summed by a second kernel) or null (float atomics).
 long ocrs_dw_bwd_ws_floats(int C, int N, int H, int W) {
@@ -1676,17 +1651,10 @@ int ocrs_dw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
             OCRS_LAUNCH_T((k_dw_bwd<T_, CG_, false>), dim3(gx, gy), dim3(256), smem, st, x, tra, trb, wdw, (const T_*)du, (T_*)gxa, (T_*)gxb, \
                                dwdw, ws, saved_a, saved_b, 0, tg, bl);                                                                    \
     }
-    BwdLast bl{nullptr, nullptr, gsum_a, gsum_b, saved_a, saved_b, Ca, 1};
-    // k_dw_bwd (the deep levels: 768 short workgroups per launch): the drain + ticket at the end of every workgroup costs what the ~5 us reduce launch
-    // it takes off the chain saves -- A/B on one box, whole step: 12.19 / 12.18 ms with it, 12.14 / 12.10 ms without (and 12.23 / 12.20 ms with nothing
-    // deferred) -- so it is off by default here; k_mm_bwd / k_rs_bwd (levels 0-2) keep it
-    static const int last_on = env_int("OCRS_BWD_LAST", 1) && env_int("OCRS_BWD_LAST_DW", 0);
-    if (stat_mask && last_on) {
-        if (double* p = bwd_defer_scratch(BWD_LAST_SLOTS * 2 * C + 2)) {
-            bl.raw = p;
-            bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * C);
-        }
-    }
+    // k_dw_bwd (the deep levels: 768 short workgroups per launch) does not take the last-block sums fold of k_mm_bwd / k_rs_bwd (levels 0-2):
+    // the drain + ticket at the end of every workgroup cost what the ~5 us reduce launch it takes off the chain saved -- A/B on one box, whole
+    // step: 12.19 / 12.18 ms with it, 12.14 / 12.10 ms without (and 12.23 / 12.20 ms with nothing deferred)
+    const BwdLast bl{nullptr, nullptr, gsum_a, gsum_b, saved_a, saved_b, Ca, 1};
     if (dtype == 1) {
         if (cg == 1) DWB(bf16, 1) else if (cg == 2) DWB(bf16, 2) else DWB(bf16, 4)
     } else {
@@ -1696,10 +1664,7 @@ int ocrs_dw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
     if (ws) {
         const int nrow = stat_mask ? 11 : 9;
         // deferred second stage: with the sums done in the block kernel (or none asked for) only the tap rows are left, and nothing in the backward reads them
-        static const int dwq = env_int("OCRS_BWD_DW_QUEUE", 1);
-        if (dwq && (bl.raw || !stat_mask) && bwd_defer_reduce(ws, gx, C * nrow, nullptr, 0, 1, 1, dwdw, 9 * C)) {
-        } else if (bl.raw) {
-            OCRS_LAUNCH_T(k_dw_partials_reduce, dim3((C * 9 + 31) / 32), dim3(256), 0, st, ws, gx, C, Ca, nrow, dwdw, (double*)nullptr, (double*)nullptr, saved_a, saved_b);
+        if (!stat_mask && bwd_defer_reduce(ws, gx, C * nrow, nullptr, 0, 1, 1, dwdw, 9 * C)) {
         } else {
             OCRS_LAUNCH_T(k_dw_partials_reduce, dim3((C * nrow + 31) / 32), dim3(256), 0, st, ws, gx, C, Ca, nrow, dwdw, gsum_a,
                                gsum_b, saved_a, saved_b);
@@ -1764,8 +1729,7 @@ long ocrs_convt_bwd_ws_floats(int Cup, int Cout, int N, int h, int w, int dtype)
 // 86-us ocrs_bn_bwd_reduce pass)
 long det_ctd_supported(int Cup, int Cout, int dtype);  // det_ctd.hip
 long ocrs_convt_bwd_stats_supported(int Cup, int Cout, int dtype) {
-    static const int ctd_stats = env_int("OCRS_CTD_STATS", 1);  // the deep-level input-gradient kernel also produces the sums (round 5)
-    if (ctd_stats && det_ctd_supported(Cup, Cout, dtype)) return 1;
+    if (det_ctd_supported(Cup, Cout, dtype)) return 1;  // the deep-level input-gradient kernel also produces the sums (round 5)
     return convt_wgrad_tr_ok(Cup, Cout, dtype) && !(Cup == 32 && Cout == 16) ? 1 : 0;
 }
 
@@ -1898,9 +1862,7 @@ int ocrs_head_bwd_loss(const void* z, const float* tr, const float* w, const flo
                        const void* state, const float* gout, float* gl, double* acc64, const float* saved, double* gsum, long P, int dtype,
                        hipStream_t st) {
     OCRS_CHECK_ARG(z && tr && w && pred && target && lpx && cls && state && gout && gl && acc64 && saved && gsum && P > 0 && P % 4 == 0);
-    static const int bpc = env_int("OCRS_HEADL_BPC", 8);
-    int grid = ew_grid(P / 4);
-    if (grid > kNumCU * bpc) grid = kNumCU * bpc;
+    int grid = ew_grid(P / 4);  // (ew_grid caps at 8 blocks per CU)
     if (dtype == 1)
         hipLaunchKernelGGL(k_head_bwd_loss<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)z, tr, w, pred, target, lpx, cls, (const LossState*)state,
                            gout, acc64, saved, gsum, P, gl);

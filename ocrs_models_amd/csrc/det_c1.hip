@@ -170,8 +170,8 @@ __global__ void k_c1_bwd_fin(const double* __restrict__ c1acc /*[8][32]*/, const
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // backward (single direct gradient g, no pooling: the in_conv block's second conv is the only consumer): dz = cf0 ghat + cf1 z + cf2,
 // ghat = g [bn(z) > 0];  du = sum_c Wpw[c] dz[c] stays in a register;  acc64 [17] += dWpw[c] = sum u dz[c] | dWdw[k] = sum du img[p + off_k]
-// ZU (round 5): z is not read -- it is rebuilt from the depthwise output this kernel recomputes anyway, z[c] = round(Wpw[c] * u): the stored values
-// bit for bit, 16 bytes per pixel less
+// z is not read (round 5) -- it is rebuilt from the depthwise output this kernel recomputes anyway, z[c] = round(Wpw[c] * u): the stored values
+// bit for bit, 16 bytes per pixel less (ZU = true is the only instantiation; the parameter keeps the kernel's name)
 template <class T, bool ZU>
 __global__ __launch_bounds__(256) void k_c1_bwd2(const float* __restrict__ img, const float* __restrict__ wdw, const float* __restrict__ wpw,
                                                  const T* __restrict__ g, const T* __restrict__ z, const float* __restrict__ bn,
@@ -197,16 +197,14 @@ __global__ __launch_bounds__(256) void k_c1_bwd2(const float* __restrict__ img, 
     int item = (int)blockIdx.x * 4 + wave;
     struct Buf {
         C1Img im;
-        Raw8<T> g[2], z[2];
+        Raw8<T> g[2];
         C1Item it;
     };
     auto issue = [&](Buf& b, int i) {
         b.it = c1_item(i, items, HP2, WS);
         const long p0 = b.it.act ? (((long)b.it.n * H + b.it.h0) * W + b.it.w0 + lane) * 8 : 0;
         const long p1 = b.it.act ? p0 + (long)W * 8 : 0;
-        if constexpr (!ZU) b.z[0] = load8_raw(z + p0);
         b.g[0] = load8_raw(g + p0);
-        if constexpr (!ZU) b.z[1] = load8_raw(z + p1);
         b.g[1] = load8_raw(g + p1);
         c1_issue_img(b.im, img, b.it, H, W, lane);
     };
@@ -221,12 +219,8 @@ __global__ __launch_bounds__(256) void k_c1_bwd2(const float* __restrict__ img, 
 #pragma unroll
             for (int k = 0; k < 9; ++k) u = fmaf(wd[k], nb[q + k / 3][k % 3], u);
             u = Elem<T>::round(u);
-            if constexpr (ZU) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) zv[i] = Elem<T>::round(wp[i] * u);
-            } else {
-                unpack8(b.z[q], zv);
-            }
+            for (int i = 0; i < 8; ++i) zv[i] = Elem<T>::round(wp[i] * u);
             float d = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -257,8 +251,7 @@ __global__ __launch_bounds__(256) void k_c1_bwd2(const float* __restrict__ img, 
 extern "C" {
 
 long det_c1v2_supported(int N, int H, int W) {
-    static const int on = env_int("OCRS_C1V2", 1);
-    return on && N > 0 && H >= 2 && H % 2 == 0 && W >= 64 && W % 64 == 0 && (long)N * (H / 2) * (W / 64) < (1L << 30);
+    return N > 0 && H >= 2 && H % 2 == 0 && W >= 64 && W % 64 == 0 && (long)N * (H / 2) * (W / 64) < (1L << 30);
 }
 
 static int c1v2_grid(int N, int H, int W, int bpc) {
@@ -269,8 +262,7 @@ static int c1v2_grid(int N, int H, int W, int bpc) {
 
 int det_c1v2_fwd_launch(const float* img, const float* wdw, const float* wpw, void* z, double* gstat, int N, int H, int W, int dtype, hipStream_t st,
                         void* uplane, double* fsum) {
-    static const int bpc = env_int("OCRS_C1V2_FWD_BPC", 8);
-    const int grid = c1v2_grid(N, H, W, bpc);
+    const int grid = c1v2_grid(N, H, W, 8);
     if (dtype == 1 && fsum)
         hipLaunchKernelGGL((k_c1_fwd2<bf16, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (bf16*)z, gstat, N, H, W, (bf16*)uplane, fsum);
     else if (dtype == 1)
@@ -288,17 +280,11 @@ int det_c1_bwd_fin_launch(const double* c1acc, const double* fsum, const float* 
 
 int det_c1v2_bwd_launch(const float* img, const float* wdw, const float* wpw, const void* g, const void* z, const float* bn, const float* coef,
                         double* acc64, int N, int H, int W, int dtype, hipStream_t st) {
-    static const int bpc = env_int("OCRS_C1V2_BWD_BPC", 5);
-    const int grid = c1v2_grid(N, H, W, bpc);
-    static const int zu_env = env_int("OCRS_C1_ZU", 1);  // rebuild z from the recomputed depthwise output instead of reading it
-    const bool zu = zu_env || !z;
-    if (dtype == 1) {
-        if (zu) hipLaunchKernelGGL((k_c1_bwd2<bf16, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const bf16*)g, (const bf16*)z, bn, coef, acc64, N, H, W);
-        else hipLaunchKernelGGL((k_c1_bwd2<bf16, false>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const bf16*)g, (const bf16*)z, bn, coef, acc64, N, H, W);
-    } else {
-        if (zu) hipLaunchKernelGGL((k_c1_bwd2<float, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const float*)g, (const float*)z, bn, coef, acc64, N, H, W);
-        else hipLaunchKernelGGL((k_c1_bwd2<float, false>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const float*)g, (const float*)z, bn, coef, acc64, N, H, W);
-    }
+    const int grid = c1v2_grid(N, H, W, 5);
+    if (dtype == 1)
+        hipLaunchKernelGGL((k_c1_bwd2<bf16, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const bf16*)g, (const bf16*)z, bn, coef, acc64, N, H, W);
+    else
+        hipLaunchKernelGGL((k_c1_bwd2<float, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const float*)g, (const float*)z, bn, coef, acc64, N, H, W);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

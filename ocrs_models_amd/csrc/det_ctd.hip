@@ -156,8 +156,7 @@ __global__ __launch_bounds__(512) void k_ctd(const bf16* __restrict__ g, const v
 extern "C" {
 
 long det_ctd_supported(int Cup, int Cout, int dtype) {
-    static const int on = env_int("OCRS_CTD", 1);
-    return on && dtype == 1 && ((Cup == 256 && Cout == 128) || (Cup == 128 && Cout == 64) || (Cup == 64 && Cout == 32));
+    return dtype == 1 && ((Cup == 256 && Cout == 128) || (Cup == 128 && Cout == 64) || (Cup == 64 && Cout == 32));
 }
 
 int det_ctd_launch(const void* g, const void* wpk, void* dx, int Cup, int Cout, int N, int h, int w, int H, int W, hipStream_t st, const void* x,

@@ -134,8 +134,7 @@ __global__ __launch_bounds__(512) void k_ctf(const bf16* __restrict__ x, const f
 extern "C" {
 
 long det_ctf_supported(int Cup, int Cout, int dtype) {
-    static const int on = env_int("OCRS_CTF", 1);
-    return on && dtype == 1 && ((Cup == 256 && Cout == 128) || (Cup == 128 && Cout == 64) || (Cup == 64 && Cout == 32));
+    return dtype == 1 && ((Cup == 256 && Cout == 128) || (Cup == 128 && Cout == 64) || (Cup == 64 && Cout == 32));
 }
 
 int det_ctf_launch(const void* x, const float* tr, const void* wpk, const float* bias, void* out, int Cup, int Cout, int N, int h, int w, int H, int W,

@@ -211,8 +211,7 @@ __global__ __launch_bounds__(512) void k_dwf(Src2<bf16> x, const float* __restri
 extern "C" {
 
 long det_dwf_supported(int Cin, int Cout, int dtype) {
-    static const int on = env_int("OCRS_DWF", 1);
-    return on && dtype == 1 && (Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256) && (Cout == 64 || Cout == 128 || Cout == 256) && Cin * 8 >= Cout;
+    return dtype == 1 && (Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256) && (Cout == 64 || Cout == 128 || Cout == 256) && Cin * 8 >= Cout;
 }
 
 int det_dwf_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* wpk, void* z,

@@ -99,11 +99,8 @@ struct FwdPitch {
     static constexpr int V = CG * 8 + (Elem<T>::is_bf16 ? 8 : 4);
 };
 
-#ifndef OCRS_PIPE_BLOCKS
-#define OCRS_PIPE_BLOCKS 3
-#endif
 template <class T, int CG, int MT, bool ONE /* Cin == CG*8: a single K chunk (always true for CG < 4) */, bool POOL = false /* also write the 2x2 max-pool */>
-__global__ __launch_bounds__(256, (ONE && Elem<T>::is_bf16) ? OCRS_PIPE_BLOCKS : (MT <= 4 ? 4 : 2)) void k_dwpw_fwd(Src2<T> x, const float* __restrict__ tra, const float* __restrict__ trb,
+__global__ __launch_bounds__(256, (ONE && Elem<T>::is_bf16) ? 3 : (MT <= 4 ? 4 : 2)) void k_dwpw_fwd(Src2<T> x, const float* __restrict__ tra, const float* __restrict__ trb,
                                                                     const float* __restrict__ wdw /*master [CIN][1][3][3]*/,
                                                                     const void* __restrict__ wpk, T* __restrict__ z,
                                                                     double* __restrict__ gstat /*[2][COUT]*/, int CIN, int COUT, Tiling2 tg,
@@ -532,13 +529,11 @@ static int launch_dwpw_fwd(const void* xa, const void* xb, int Ca, int Cb, const
     const size_t smem = ((TP * FwdPitch<T, CG>::V * sizeof(T) + 15) & ~15) +
                         (HaloTile<FT::TW, FT::TH>::HP * CG * 8 + 12 * CIN + 4 * 2 * MT * 16) * sizeof(float);
     // every block ends with 2*COUT same-address fp64 atomics (~15 ns each, serialised): at the middle levels (a few thousand tiles)
-    // two tiles per block halve that tail; below that parallelism matters more (measured: OCRS_FWD_TPB sweep, profiles/README.md)
-    static const int fwd_tpb = env_int("OCRS_FWD_TPB", 0);
-    const int tpb = fwd_tpb > 0 ? fwd_tpb : (tg.ntiles >= 2048 ? 2 : 1);
+    // two tiles per block halve that tail; below that parallelism matters more (measured: tiles-per-block sweep, profiles/README.md)
+    const int tpb = tg.ntiles >= 2048 ? 2 : 1;
     // 4 blocks per CU are resident (registers <= 128, LDS 36 KB): a grid of exactly the resident blocks runs as ONE round (8 per CU = two rounds, each
     // block with its own prologue and 2*COUT fp64 atomics at the end: 4.66 -> 4.52 ms per step over all forward launches)
-    static const int fwd_bpc = env_int("OCRS_FWD_BPC", 4);
-    const int grid = persistent_grid(tg.ntiles / tpb > 0 ? tg.ntiles / tpb : 1, fwd_bpc);
+    const int grid = persistent_grid(tg.ntiles / tpb > 0 ? tg.ntiles / tpb : 1, 4);
     if (pooled) {
         if constexpr (FwdPx<MT>::PX == 2 && FT::TW >= 16)
             hipLaunchKernelGGL((k_dwpw_fwd<T, CG, MT, ONE, true>), dim3(grid), dim3(256), smem, st, x, tra, trb, wdw, wpk, (T*)z, gstat, CIN, COUT, tg,

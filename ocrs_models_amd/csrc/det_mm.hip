@@ -18,99 +18,10 @@
 #include "det_rs.h"
 #include <type_traits>
 
-// ---- tile-shape / residency knobs (measurement builds: tools/build_variant.sh; the defaults are the measured optimum, profiles/README.md)
-#ifndef OCRS_MM_TH
-#define OCRS_MM_TH 8       // backward tile rows, Cin and Cout <= 16 (16 halves the ring re-reads but spills at 128 registers); per-shape overrides:
-#endif
-#ifndef OCRS_MM_TH_8_8
-#define OCRS_MM_TH_8_8 12  // 12 rows: 476 of 512 threads hold a (z, g) item instead of 340 -- more bytes in flight from the same registers (650 -> 621 us)
-#endif
-#ifndef OCRS_MM_TH_16_8
-#define OCRS_MM_TH_16_8 12  // (round 3, after the index-arithmetic diet freed registers: 890 -> 840 us, no spills in the FULL instantiations)
-#endif
-#ifndef OCRS_MM_TH_8_16
-#define OCRS_MM_TH_8_16 12  // (946 -> 881 us; needs the single-buffered dgrad to fit 128 registers)
-#endif
-#ifndef OCRS_MM_TH_16_16
-#define OCRS_MM_TH_16_16 OCRS_MM_TH
-#endif
-#ifndef OCRS_MM_TH_16_16_P
-#define OCRS_MM_TH_16_16_P 12  // pooled gradient (the level-0 16 -> 16 block): round 2: 8 rows (1112 us) beat 12 (1151 us, 20 B of spills); round 3 (no spills after the index diet): 12 rows 1209 vs 1250 us
-#endif
-#define OCRS_MM_TH_OF(ci, co) ((ci) == 8 ? ((co) == 8 ? OCRS_MM_TH_8_8 : OCRS_MM_TH_8_16) : ((co) == 8 ? OCRS_MM_TH_16_8 : OCRS_MM_TH_16_16))
-#ifndef OCRS_MM_SW
-#define OCRS_MM_SW 1       // wave index in a scalar register
-#endif
-#ifndef OCRS_MM_EPI
-#define OCRS_MM_EPI 1      // dgrad epilogue store addressing (0: per-lane 64-bit pixel index, 1: scalar row + lane offset, 2: 1 with both row pointers pinned scalar)
-#endif
-#ifndef OCRS_MM_BDB_EXCL
-#define OCRS_MM_BDB_EXCL 1  // single-buffer the dgrad B fragments of the 12-row 8 -> 16 and pooled 16 -> 16 tiles (register diet)
-#endif
-#ifndef OCRS_MM_GPIPE
-#define OCRS_MM_GPIPE 0     // weight-gradient phase: explicit one-step-ahead fragment prefetch (1) or straight-line code scheduled by hipcc (0)
-#endif
-#ifndef OCRS_MM_B3_16_8
-#define OCRS_MM_B3_16_8 0   // backward, Cin = 16 -> Cout = 8: three blocks per CU (<= 85 registers: needs per-tile LDS statistics + single-buffered dgrad + 8 B of spills; measured 706 vs 673 us: off)
-#endif
-#ifndef OCRS_MM_C32_BPC
-#define OCRS_MM_C32_BPC 1  // backward blocks per CU, Cin = 32 AND Cout = 32 (1: full register file, 16-row tiles: 144 / 506 us; 2: 8-row tiles, ~150 B of
-                           // spills: 181 / 559 us).  Cin = 32, Cout = 16 always runs two blocks per CU (20-60 B of spills, 479 vs 529 us)
-#endif
-#ifndef OCRS_MM_S2G
-#define OCRS_MM_S2G 1  // the producers' second BatchNorm-backward sum S2 = sum ghat' x~ from the weight-gradient accumulators at the flush (as k_rs_bwd does):
-                       // sum_q dx~[q][c] x~[q][c] = sum_{tap,o} Weff[o][(tap,c)] G_tap[c][o] exactly (x~ [x~ > 0] = x~); the per-lane epilogue keeps S1 only.
-                       // S2 then sums the UNROUNDED dx~ (an unbiased 2^-9 / sqrt(pixels) relative difference, the same as in det_rs.hip)
-#endif
-#ifndef OCRS_MM_C32_N256
-#define OCRS_MM_C32_N256 1  // backward, Cin = 32 AND Cout = 32: TWO independent 256-thread workgroups per CU (256 registers each, 8-row tiles) instead of one
-                            // 512-thread workgroup -- the same two waves per SIMD, but the barrier waits / commit / epilogue of one workgroup (35-40 % of a
-                            // tile at one workgroup per CU: tools/runs/mm_prof.sh) run under the MFMA phases of the other
-#endif
-#ifndef OCRS_MM_C3216_N256
-#define OCRS_MM_C3216_N256 1  // the same form for Cin = 32 -> Cout = 16 (which spills 12-44 B per lane at two 512-thread workgroups per CU): 382 -> 366 us at level 1
-#endif
-#ifndef OCRS_MM_C32_MERGE
-#define OCRS_MM_C32_MERGE 1  // ... and both M tiles of the dgrad in ONE pass over the B fragments (the LDS reads of that phase halve: 16 more accumulator registers)
-#endif
-#ifndef OCRS_MM_C32_MERGE_BDB
-#define OCRS_MM_C32_MERGE_BDB 0  // ... with the B fragments single-buffered (double-buffered, the merged pass spills 12-36 B per lane)
-#endif
-#ifndef OCRS_MM_BDB
-#define OCRS_MM_BDB 1      // backward dgrad: double-buffer the B fragments across K chunks
-#endif
-#ifndef OCRS_MF_TH8
-#define OCRS_MF_TH8 16     // forward tile rows, Cin = 8 (measured: 16 rows x 2 blocks/CU 300 us, 8 rows x 3 blocks/CU 329 us, 8 x 2: 356 us at level 0)
-#endif
-#ifndef OCRS_MF_TH16
-#define OCRS_MF_TH16 8     // forward tile rows, Cin = 16 (16 spills)
-#endif
-#ifndef OCRS_MF_TH16_32
-#define OCRS_MF_TH16_32 8  // forward tile rows, Cin = 16 -> Cout = 32
-#endif
-#ifndef OCRS_MF_TH32
-#define OCRS_MF_TH32 8     // forward tile rows, Cin = 32
-#endif
-// forward tile rows must be a multiple of 8: the 8 waves share TH (row pair, column half) units (a 12-row build silently computes 8 rows --
-// MfCfg asserts it)
-#define OCRS_MF_TH_OF(ci, co, nst) ((nst) == 2 ? 8 : ((ci) == 32 ? OCRS_MF_TH32 : ((co) == 32 ? OCRS_MF_TH16_32 : ((ci) == 8 ? OCRS_MF_TH8 : OCRS_MF_TH16))))
-#ifndef OCRS_MF_BPC16_8
-#define OCRS_MF_BPC16_8 3  // forward blocks per CU, Cin = 16 -> Cout = 8 (80 registers: 490 -> 438 us at level 0; every other Cin = 16 shape spills at 85)
-#endif
-#ifndef OCRS_MF_BPC8
-#define OCRS_MF_BPC8 2     // forward blocks per CU, Cin = 8
-#endif
-
-// floor-measurement builds (tools/r3): drop the global loads / the stores / the MFMA phases of k_mm_bwd
-#ifndef OCRS_MM_NOLOAD
-#define OCRS_MM_NOLOAD 0
-#endif
-#ifndef OCRS_MM_NOSTORE
-#define OCRS_MM_NOSTORE 0
-#endif
-#ifndef OCRS_MM_NOCOMPUTE
-#define OCRS_MM_NOCOMPUTE 0
-#endif
+// Tile shapes and residency are the measured optimum (profiles/README.md; other shapes are measured on patched copies: tools/build_variant.sh).
+// Forward tile rows: 16 at Cin = 8 (16 rows x 2 blocks/CU 300 us, 8 rows x 3 blocks/CU 329 us, 8 x 2: 356 us at level 0), 8 everywhere else
+// (Cin = 16 spills at 16).  They must be a multiple of 8: the 8 waves share TH (row pair, column half) units (MfCfg asserts it).
+constexpr int mf_th(int cin, int cout, int nst) { return (nst != 2 && cin == 8 && cout != 32) ? 16 : 8; }
 
 namespace {
 
@@ -121,18 +32,22 @@ struct MmPitch {  // bf16 elements per pixel of an LDS tile: 16 / 32-byte rows a
 
 template <int CIN, int COUT, bool PPOOL = false>
 struct MmCfg {
-    static constexpr bool N256 = (OCRS_MM_C32_N256 && CIN == 32 && COUT == 32) || (OCRS_MM_C3216_N256 && CIN == 32 && COUT == 16);  // two 256-thread workgroups per CU with the full register file each
+    // Cin = 32 (two M tiles: 16-24 more live registers than fit 128 without spilling): TWO independent 256-thread workgroups per CU with 256
+    // registers each instead of one 512-thread workgroup -- the same two waves per SIMD, but the barrier waits / commit / epilogue of one
+    // workgroup (35-40 % of a tile at one workgroup per CU) run under the MFMA phases of the other (Cin = 32 -> Cout = 16: 382 -> 366 us at level 1)
+    static constexpr bool N256 = CIN == 32 && (COUT == 32 || COUT == 16);
     static constexpr int NT = N256 ? 256 : 512, NW = NT / 64;          // 8 (4) waves
-    // Cin = 32 (two M tiles, 16-24 more live registers than fit 128 without spilling -- and a scratch reload inside the pipelined loop waits for
-    // every prefetched load): ONE block per CU with the full register file and 16-row tiles; everything else: two blocks per CU, 8-row tiles
-    static constexpr bool T3 = OCRS_MM_B3_16_8 && CIN == 16 && COUT == 8 && !PPOOL;
-    static constexpr int BPC = N256 ? 2 : ((CIN == 32 && COUT == 32) ? OCRS_MM_C32_BPC : (T3 ? 3 : 2));  // resident blocks per CU (launch bound: BPC * NW / 4 waves per SIMD)
+    static constexpr int BPC = 2;                                      // resident blocks per CU (launch bound: BPC * NW / 4 waves per SIMD)
     static constexpr int TW = 32;
-    static constexpr int TH = N256 ? 8 : ((CIN == 32 || COUT == 32) ? (BPC == 1 ? 16 : 8) : ((PPOOL && CIN == 16 && COUT == 16) ? OCRS_MM_TH_16_16_P : OCRS_MM_TH_OF(CIN, COUT)));
-    static constexpr bool MERGE = N256 && OCRS_MM_C32_MERGE;            // dgrad: both M tiles per pass
+    // tile rows: 8 with a 32-channel side; 12 for the 8-channel shapes (476 of 512 threads hold a (z, g) item instead of 340: more bytes in
+    // flight from the same registers, 650 -> 621 us at 8 -> 8) and the pooled 16 -> 16 block (1250 -> 1209 us); 8 for 16 -> 16 (12 spills)
+    static constexpr int TH = (CIN == 32 || COUT == 32) ? 8 : ((CIN == 16 && COUT == 16 && !PPOOL) ? 8 : 12);
+    static constexpr bool MERGE = N256;                                // dgrad: both M tiles in ONE pass over the B fragments (LDS reads halve)
     static constexpr int TP = TW * TH;
     static constexpr bool T12P = CIN == 16 && COUT == 16 && TH == 12;  // 12-row 16 -> 16 tile (pooled or direct gradient): needs the two register diets below to fit 128
-    static constexpr bool BDB = OCRS_MM_BDB && (!OCRS_MM_BDB_EXCL || (!(CIN == 8 && COUT == 16 && TH == 12) && !T12P)) && !T3 && !(N256 && OCRS_MM_C32_MERGE && !OCRS_MM_C32_MERGE_BDB);  // dgrad B fragments double-buffered across K chunks
+    // dgrad B fragments double-buffered across K chunks, except where the registers do not allow it (the 12-row 8 -> 16 and 16 -> 16 tiles, and
+    // the merged pass, which spills 12-36 B per lane double-buffered)
+    static constexpr bool BDB = !(CIN == 8 && COUT == 16 && TH == 12) && !T12P && !N256;
     static constexpr int DW_ = TW + 2, DH_ = TH + 2, DP = DW_ * DH_;  // domain = tile + 1-pixel ring
     static constexpr int CGI = CIN / 8, CGO = COUT / 8;
     static constexpr int PD = MmPitch<COUT>::V, PX = MmPitch<CIN>::V;
@@ -215,7 +130,7 @@ __device__ __forceinline__ Raw8<bf16> raw8_of(const u32x4& v) {
 
 // forward: Cin = 8 needs < 80 registers and ~10 KB of LDS: three blocks per CU (more bytes in flight: these launches are latency-bound)
 template <int CINB, int COUT>
-constexpr int mm_fwd_lb() { return CINB == 8 ? 2 * OCRS_MF_BPC8 : ((CINB == 16 && COUT == 8) ? 2 * OCRS_MF_BPC16_8 : 4); }
+constexpr int mm_fwd_lb() { return (CINB == 16 && COUT == 8) ? 6 : 4; }
 // the last-workgroup finalisation of the forward statistics is compiled into every shape but Cin = 16 -> Cout = 8: at that shape's 80-register cap (three
 // blocks per CU) the extra code made hipcc spill a 64-bit index pair that the prefetch issue reloads from scratch -- behind an s_waitcnt vmcnt(0), i.e.
 // behind the acknowledgement of the previous tile's stores (397 -> 454-472 us at level 0); the launcher runs k_bn_finalize_parts for it instead
@@ -252,11 +167,7 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
     float* s_wp = s_w9 + 9 * CIN;                               // [COUT][CIN]
     const int H = tg.H, W = tg.W;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15;
-#if OCRS_MM_SW
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar register: wave-dependent branches and offsets become scalar code)
-#else
-    const int wave = tid >> 6;
-#endif
 
     // ---- prologue: parameters, effective-weight fragments
     fill_tr8(s_trx, x, tra, trb, CIN, tid);
@@ -356,10 +267,9 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                     const bool it_ok = (j + 1) * NT <= DP * CGO || tid + j * NT < DP * CGO;  // (a compile-time `true` for all but the last round)
                     const bool ok = it_ok && (decltype(INSIDE)::value || ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W));
                     const int goff = (dy * W + dx) * COUT + cgo * 8;
-                    const bool ld = ok && !OCRS_MM_NOLOAD;
-                    pf[SI][j * GW + 0] = ld16(ld ? zb + goff : z);
-                    pf[SI][j * GW + 1] = ld16(ld ? g1b + goff : g1);
-                    if constexpr (G2) pf[SI][j * GW + 2] = ld16(ld ? g2b + goff : g2);
+                    pf[SI][j * GW + 0] = ld16(ok ? zb + goff : z);
+                    pf[SI][j * GW + 1] = ld16(ok ? g1b + goff : g1);
+                    if constexpr (G2) pf[SI][j * GW + 2] = ld16(ok ? g2b + goff : g2);
                     okg |= ok ? 1u << j : 0u;
                 }
             };
@@ -375,14 +285,14 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const bool ok = it_ok && (unsigned)(h + (k >> 1)) < (unsigned)H && (unsigned)(w + (k & 1)) < (unsigned)W;
-                    zp[4 * j + k] = *reinterpret_cast<const uint2*>((ok && !OCRS_MM_NOLOAD) ? zb + goff + ((k >> 1) * W + (k & 1)) * COUT : z);
+                    zp[4 * j + k] = *reinterpret_cast<const uint2*>(ok ? zb + goff + ((k >> 1) * W + (k & 1)) * COUT : z);
                     okg |= ok ? 1u << (4 * j + k) : 0u;
                 }
                 const int ph = h >> 1, pw = w >> 1;
                 const bool gv = it_ok && h >= 0 && w >= 0 && ph < Hp && pw < Wp;  // floor mode: the last odd row / column is in no window
                 const long pp = (o.n * Hp + ph) * Wp + pw;
-                gp1[j] = *reinterpret_cast<const uint2*>((gv && !OCRS_MM_NOLOAD) ? g1 + pp * COUT + cq4 : g1);
-                if constexpr (G2) gp2[j] = *reinterpret_cast<const uint2*>((gv && !OCRS_MM_NOLOAD) ? g2 + pp * COUT + cq4 : g2);
+                gp1[j] = *reinterpret_cast<const uint2*>(gv ? g1 + pp * COUT + cq4 : g1);
+                if constexpr (G2) gp2[j] = *reinterpret_cast<const uint2*>(gv ? g2 + pp * COUT + cq4 : g2);
                 okg |= gv ? 1u << (16 + j) : 0u;
             }
         }
@@ -394,7 +304,7 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                 const int h = o.h0 + ORG + ty, w = o.w0 + ORG + tx;
                 const bool it_ok = (j + 1) * NT <= TP * CGI || tid + j * NT < TP * CGI;
                 const bool ok = it_ok && (decltype(INSIDE)::value || ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W));
-                pf[SI][NG * GW + j] = ld16((ok && !OCRS_MM_NOLOAD) ? xi_base + (long)(tb + ty * W + tx) * xi_pitch : xi_base);
+                pf[SI][NG * GW + j] = ld16(ok ? xi_base + (long)(tb + ty * W + tx) * xi_pitch : xi_base);
                 okx |= ok ? 1u << j : 0u;
             }
         };
@@ -459,25 +369,19 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
             for (int b = 0; b < NTO; ++b) accO[j][a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // producers' BatchNorm-backward sums: per-lane register accumulators (one M tile), or -- with two M tiles, where 16 more live registers
     // spill -- per-tile sums added to this wave's own LDS slots (single writer, fixed order: deterministic)
-    constexpr bool STL = STATS && (MT == 2 || C::T12P || C::T3);
+    constexpr bool STL = STATS && (MT == 2 || C::T12P);
     float* s_st = s_wp + COUT * CIN;  // [wave][2][MT*16] (STL only)
-    float st1[(STATS && !STL) ? MT : 1][4], st2[(STATS && !STL) ? MT : 1][4];
+    float st1[(STATS && !STL) ? MT : 1][4];
     if constexpr (STATS && !STL) {
 #pragma unroll
         for (int a = 0; a < MT; ++a)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) st1[a][i] = st2[a][i] = 0.f;
+            for (int i = 0; i < 4; ++i) st1[a][i] = 0.f;
     }
     if constexpr (STL) {
         for (int i = tid; i < C::NW * 2 * MT * 16; i += NT) s_st[i] = 0.f;  // (ordered before its first use by the tile loop's barriers)
     }
 
-#ifdef OCRS_MM_PROF  // (debug build: per-phase cycle totals of block 0 / thread 0 land in the first bytes of gxa)
-    unsigned long long pt[5] = {0, 0, 0, 0, 0}, pc = __builtin_readcyclecounter();
-#define MM_MARK(i) { const unsigned long long now_ = __builtin_readcyclecounter(); pt[i] += now_ - pc; pc = now_; }
-#else
-#define MM_MARK(i)
-#endif
     TileSched ts(tg.ntiles);
     TileIter<TW, TH> tit(tg, ts.first < ts.end ? ts.first : 0, ts.step);  // (points at the newest tile whose loads were issued)
     TileOrg orgs[PFD];
@@ -495,7 +399,6 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
             constexpr int YOUNGER = KI == 0 ? 0 : NSTORE;
             static_for_wait<NLOADS, YOUNGER>(pf[SI]);
         }
-        MM_MARK(4)
         // ================= phase 1: commit the prefetched tile: dz -> tileD, x~ -> tileX =================
         // Four channels at a time (the five per-channel coefficient vectors of a half are 20 registers instead of 40; 8-byte LDS stores).
         if constexpr (!PPOOL) {
@@ -597,14 +500,12 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        MM_MARK(0)
         if (t + ts.step < ts.end) {
             tit.next();
             orgs[SI] = tit.org();
             issue(orgs[SI], SET);
         }
         lds_barrier();
-        MM_MARK(1)
         // ================= phase 2a: dx~ = Weff * dz (shifted), MFMA; epilogue: store + the producers' BatchNorm-backward sums =================
         // One M tile (16 input channels) at a time: the second pass re-reads the B fragments from LDS instead of holding 2x the accumulators.
         {
@@ -635,8 +536,7 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                         if (!bv) dst[a] = make_uint4(0, 0, 0, 0);
                     }
                 };
-                if constexpr (OCRS_MM_NOCOMPUTE) {
-                } else if constexpr (C::BDB) {  // B fragments double-buffered across K chunks
+                if constexpr (C::BDB) {  // B fragments double-buffered across K chunks
                     load_b(bcur, 0);
 #pragma unroll
                     for (int kc = 0; kc < KC; ++kc) {
@@ -675,11 +575,11 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                 const int ms = (FULL && CIN == 8) ? (m0 & 7) : m0;  // (duplicate rows store to the address of the row they duplicate)
                 const bool in_a = ms < x.Ca;
                 const int voff = l15 * (in_a ? x.Ca : x.Cb) + (in_a ? ms : ms - x.Ca);  // element offset of this lane's 4 channels from the N tile's first pixel
-                float t1[4] = {0.f, 0.f, 0.f, 0.f}, t2[4] = {0.f, 0.f, 0.f, 0.f};
+                float t1[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int a = 0; a < NPW; ++a) {
                     const int k = wave * NPW + a, ty = k / (TW / 16), tx0 = (k % (TW / 16)) * 16;
-                    const bool pv = FULL || (!OCRS_MM_NOSTORE && (unsigned)(org.h0 + ORG + ty) < (unsigned)H && (unsigned)(org.w0 + ORG + tx0 + l15) < (unsigned)W);
+                    const bool pv = FULL || ((unsigned)(org.h0 + ORG + ty) < (unsigned)H && (unsigned)(org.w0 + ORG + tx0 + l15) < (unsigned)W);
                     const long srow = tb + ty * W + tx0;  // (scalar)
                     if constexpr (FULL) {  // unconditional store, no divergent branch around it
                         const f32x4 v = acc[a];
@@ -693,21 +593,8 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                     if (m0 < CIN) {
                         const f32x4 v = acc[a];
                         if (pv && !FULL) {
-#if OCRS_MM_EPI == 2
-                            bf16* pa = gxa + srow * x.Ca;
-                            bf16* pb = gxb + srow * x.Cb;
-                            asm volatile("" : "+s"(pa), "+s"(pb));  // both row pointers stay scalar (hipcc re-associates the select into a per-lane 64-bit multiply)
-                            store4((in_a ? pa : pb) + voff, v[0], v[1], v[2], v[3]);
-#elif OCRS_MM_EPI == 1
                             bf16* dst = (in_a ? gxa + srow * x.Ca : gxb + srow * x.Cb) + voff;
                             store4(dst, v[0], v[1], v[2], v[3]);
-#else
-                            const long pix = srow + l15;
-                            if (in_a)
-                                store4(gxa + pix * x.Ca + m0, v[0], v[1], v[2], v[3]);
-                            else
-                                store4(gxb + pix * x.Cb + (m0 - x.Ca), v[0], v[1], v[2], v[3]);
-#endif
                         }
                         if constexpr (STATS) {
                             float xq[4];
@@ -717,83 +604,38 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                                 // the producer's backward reads the STORED (rounded) gradient; x~ > 0 <=> bn(z) > 0 for the ReLU producers that ask
                                 const float gh = xq[i] > 0.f ? Elem<bf16>::round(v[i]) : 0.f;
                                 t1[i] += gh;
-                                if constexpr (!OCRS_MM_S2G) t2[i] = fmaf(gh, xq[i], t2[i]);
                             }
                         }
                     }
                 }
                 if constexpr (STATS && !STL) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        st1[b][i] += t1[i];
-                        if constexpr (!OCRS_MM_S2G) st2[b][i] += t2[i];
-                    }
+                    for (int i = 0; i < 4; ++i) st1[b][i] += t1[i];
                 }
                 if constexpr (STL) {
-                    float r1[4], r2[4];
+                    float r1[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        r1[i] = quad16_sum(t1[i]);
-                        if constexpr (!OCRS_MM_S2G) r2[i] = quad16_sum(t2[i]);
-                    }
+                    for (int i = 0; i < 4; ++i) r1[i] = quad16_sum(t1[i]);
                     if ((lane & 15) == 0) {
                         float* q1 = s_st + (wave * 2 + 0) * MT * 16 + m0;
                         f32x4 o1 = *reinterpret_cast<f32x4*>(q1);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) o1[i] += r1[i];
                         *reinterpret_cast<f32x4*>(q1) = o1;
-                        if constexpr (!OCRS_MM_S2G) {
-                            float* q2 = s_st + (wave * 2 + 1) * MT * 16 + m0;
-                            f32x4 o2 = *reinterpret_cast<f32x4*>(q2);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) o2[i] += r2[i];
-                            *reinterpret_cast<f32x4*>(q2) = o2;
-                        }
                     }
                 }
               }
             }
         }
-        MM_MARK(2)
         // ================= phase 2b: G_tap += x~^T dz(shifted), K = the tile's pixels, operands by LDS transpose reads =================
         // Straight-line code: the wave's own unit has a compile-time number of k-steps starting at a scalar first step, so every read address
         // is (per-tile base register + immediate) and hipcc can issue the transpose reads of the following steps under the current MFMAs.  (As a
         // loop over all k-steps with wave-uniform `continue`s every step was: 4 reads -> s_waitcnt lgkmcnt(0) -> 1 MFMA, a full LDS round trip
         // per MFMA.)
         {
-            constexpr int LOWN = OCRS_MM_NOCOMPUTE ? 0 : ((C::TAPU == 9) ? KS : KS / 2);
+            constexpr int LOWN = (C::TAPU == 9) ? KS : KS / 2;
             const bf16* xo = tileX + (ks_own0 * 32 + prow) * PX + pcol;
             const bf16* dq = tileD + ks_own0 * DW_ * PD + off_own[0];
-#if OCRS_MM_GPIPE
-            static_assert(NOWN == 1, "the explicit fragment pipeline is written for one own unit");
-            bf16x8 afc[MT], bfc[NTO];
-#pragma unroll
-            for (int a = 0; a < MT; ++a) afc[a] = lds_tr8(xo + a * 16, xo + a * 16 + 16 * PX);
-#pragma unroll
-            for (int bb = 0; bb < NTO; ++bb) bfc[bb] = lds_tr8(dq + bb * 16, dq + bb * 16 + 16 * PD);
-#pragma unroll
-            for (int i = 0; i < LOWN; ++i) {
-                bf16x8 afn[MT], bfn[NTO];
-                if (i + 1 < LOWN) {
-                    const bf16* xn = xo + (i + 1) * 32 * PX;
-                    const bf16* dn = dq + (i + 1) * DW_ * PD;
-#pragma unroll
-                    for (int a = 0; a < MT; ++a) afn[a] = lds_tr8(xn + a * 16, xn + a * 16 + 16 * PX);
-#pragma unroll
-                    for (int bb = 0; bb < NTO; ++bb) bfn[bb] = lds_tr8(dn + bb * 16, dn + bb * 16 + 16 * PD);
-                }
-#pragma unroll
-                for (int bb = 0; bb < NTO; ++bb)
-#pragma unroll
-                    for (int a = 0; a < MT; ++a) accO[0][a][bb] = mfma16(afc[a], bfc[bb], accO[0][a][bb]);
-                if (i + 1 < LOWN) {
-#pragma unroll
-                    for (int a = 0; a < MT; ++a) afc[a] = afn[a];
-#pragma unroll
-                    for (int bb = 0; bb < NTO; ++bb) bfc[bb] = bfn[bb];
-                }
-            }
-#else
 #pragma unroll
             for (int i = 0; i < LOWN; ++i) {
                 const bf16* xn = xo + i * 32 * PX;
@@ -812,17 +654,15 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
                     }
                 }
             }
-#endif
             // this wave's sub-tile of the shared last unit over its k-step range (1 .. KS / NKR + 1 steps)
             const bf16* xs0 = tileX + prow * PX + sh_a * 16 + pcol;
             const bf16* ds0 = tileD + off_sh;
-            for (int ks = sh_k0; ks < (OCRS_MM_NOCOMPUTE ? sh_k0 : sh_k1); ++ks) {
+            for (int ks = sh_k0; ks < sh_k1; ++ks) {
                 const bf16* xa = xs0 + ks * 32 * PX;
                 const bf16* da = ds0 + ks * DW_ * PD;
                 accS = mfma16(lds_tr8(xa, xa + 16 * PX), lds_tr8(da, da + 16 * PD), accS);
             }
         }
-        MM_MARK(3)
         lds_barrier();  // all readers of the tiles are done before the next commit
     };
     {
@@ -842,13 +682,6 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
             for (; t < ts.end; t += ts.step) tile_body(t, K2{}, I0{});
         }
     }
-#ifdef OCRS_MM_PROF
-    if (blockIdx.x == 0 && tid == 0 && gxa) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(gxa);
-        for (int i = 0; i < 5; ++i) o[i] = pt[i];
-        o[5] = (ts.end - ts.first + ts.step - 1) / ts.step;
-    }
-#endif
 
     // ================= flush: G slots -> dWpw / dWdw partials of this block (workspace); stats partials =================
     __syncthreads();
@@ -870,7 +703,7 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
         for (int a = 0; a < MT; ++a)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float v1 = quad16_sum(st1[a][i]), v2 = OCRS_MM_S2G ? 0.f : quad16_sum(st2[a][i]);
+                const float v1 = quad16_sum(st1[a][i]), v2 = 0.f;  // (S2 comes from G at the flush)
                 if ((lane & 15) == 0) {
                     sstat[(wave * 2 + 0) * MT * 16 + a * 16 + (lane >> 4) * 4 + i] = v1;
                     sstat[(wave * 2 + 1) * MT * 16 + a * 16 + (lane >> 4) * 4 + i] = v2;
@@ -919,7 +752,7 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
         float s = 0.f;
         if constexpr (STATS) {
             const int c = e >> 1, which = e & 1;
-            if (OCRS_MM_S2G && which) {  // S2 from G, with the bf16 effective weights the dgrad used
+            if (which) {  // S2 from G, with the bf16 effective weights the dgrad used
                 for (int tap = 0; tap < 9; ++tap)
                     for (int o = 0; o < COUT; ++o) s = fmaf(bf2f(f2bf(wdw[c * 9 + tap] * wpw[o * ldw + c])), Gval(tap, c, o), s);
             } else {
@@ -1001,15 +834,9 @@ static int mm_grid(int th, int N, int H, int W, int pooled, int bpc = 2) {
     const long ntiles = (long)N * ((W + pooled + 31) / 32) * ((H + pooled + th - 1) / th);
     return persistent_grid(ntiles, bpc);
 }
-static int mm_th(int Cin, int Cout, int nst) { return OCRS_MF_TH_OF(Cin, Cout, nst); }  // forward tiles
-static int mm_bwd_bpc(int Cin, int Cout, int pooled = 0) {
-    if (Cin == 32 && Cout == 32) return OCRS_MM_C32_N256 ? 2 : OCRS_MM_C32_BPC;
-    if (Cin == 32 && Cout == 16 && OCRS_MM_C3216_N256) return 2;
-    return (OCRS_MM_B3_16_8 && Cin == 16 && Cout == 8 && !pooled) ? 3 : 2;
-}
-static int mm_bwd_th(int Cin, int Cout, int pooled) {
-    if (Cin == 32 || Cout == 32) return (mm_bwd_bpc(Cin, Cout) == 1 && !(OCRS_MM_C32_N256 && Cin == 32 && Cout == 32)) ? 16 : 8;
-    return (pooled && Cin == 16 && Cout == 16) ? OCRS_MM_TH_16_16_P : OCRS_MM_TH_OF(Cin, Cout);
+static int mm_bwd_th(int Cin, int Cout, int pooled) {  // = MmCfg<Cin, Cout, pooled>::TH
+    if (Cin == 32 || Cout == 32) return 8;
+    return (Cin == 16 && Cout == 16 && !pooled) ? 8 : 12;
 }
 
 template <int CIN, int COUT, bool PPOOL, bool G2, bool STATS>
@@ -1021,9 +848,8 @@ static void mm_bwd_launch1(const Src2<bf16>& x, const float* tra, const float* t
     tg.H = H;
     tg.W = W;
     // (the attribute is set per call: it is per device, this runs on any thread, and it is a cheap host-side update -- ADVICE r02)
-    static const int full_on = env_int("OCRS_MM_FULL", 1);
     if constexpr (!PPOOL) {
-        if (full_on && W % CC::TW == 0) {  // every tile COLUMN inside the image: unconditional stores + hand-written prefetch waits
+        if (W % CC::TW == 0) {  // every tile COLUMN inside the image: unconditional stores + hand-written prefetch waits
             hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);
             OCRS_LAUNCH_T((k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, ldw, g1, g2, z, bn, coef,
                           gxa, gxb, ws, tg, fin, bl);
@@ -1053,8 +879,7 @@ static void mm_bwd_dispatch(const Src2<bf16>& x, const float* tra, const float* 
 // in-kernel finalisation state for one block-backward launch (off: raw = null) and the launch's second stage
 static BwdLast mm_bwd_last(bool want, int Cin, int Ca, double* gsA, double* gsB, const float* svA, const float* svB) {
     BwdLast bl{nullptr, nullptr, gsA, gsB, svA, svB, Ca, 0};
-    static const int on = env_int("OCRS_BWD_LAST", 1);
-    if (!want || !on) return bl;
+    if (!want) return bl;
     double* p = bwd_defer_scratch(BWD_LAST_SLOTS * 2 * Cin + 2);
     if (p) {
         bl.raw = p;
@@ -1086,7 +911,7 @@ long ocrs_mm_bwd_supported(int Ca, int Cb, int Cout, int dtype) {
 }
 long ocrs_mm_bwd_ws_floats(int Ca, int Cb, int Cout, int N, int H, int W) {
     const int Cin = (Ca == 32 && Cb == 32) ? 32 : Ca + Cb;
-    const int nb0 = mm_grid(mm_bwd_th(Cin, Cout, 0), N, H, W, 0, mm_bwd_bpc(Cin, Cout, 0)), nb1 = mm_grid(mm_bwd_th(Cin, Cout, 1), N, H, W, 1, mm_bwd_bpc(Cin, Cout, 1));
+    const int nb0 = mm_grid(mm_bwd_th(Cin, Cout, 0), N, H, W, 0), nb1 = mm_grid(mm_bwd_th(Cin, Cout, 1), N, H, W, 1);
     // per block: its partials + 4 KB of scratch lines (stores of rows below the image); a 32 | 32 concat input runs as two launches, each with its own half
     // (so that both second stages can be deferred: ocrs_bwd_defer_begin)
     const long tiled = (long)(nb0 > nb1 ? nb0 : nb1) * (Cout * Cin + 11 * Cin + 1024) * ((Ca == 32 && Cb == 32) ? 2 : 1);
@@ -1124,7 +949,7 @@ static int mm_bwd_impl(const void* xa, const void* xb, int Ca, int Cb, const flo
         const bool stats = gsA || gsB;
         const bool rs = !split && rs_bwd_supported(Ca, Cb, Cout, pooled, N, H, W);  // the row-streaming kernel (det_rs.hip) covers this launch
         const int nb = rs ? rs_bwd_blocks(Cin, Cout, N, H, W, g2 != nullptr)
-                          : mm_grid(mm_bwd_th(Cin, Cout, pooled ? 1 : 0), N, H, W, pooled ? 1 : 0, mm_bwd_bpc(Cin, Cout, pooled ? 1 : 0));
+                          : mm_grid(mm_bwd_th(Cin, Cout, pooled ? 1 : 0), N, H, W, pooled ? 1 : 0);
         const float* wd = wdw + c_off * 9;
         const float* wp = wpw + c_off;
         // deferred second stage (ocrs_bwd_defer_begin): the producers' sums by the last workgroup of the block kernel, the weight-gradient reduce queued
@@ -1236,7 +1061,7 @@ namespace {
 template <int CINB, int NST, int COUT>
 struct MfCfg {
     static constexpr int NT = 512, NW = 8;
-    static constexpr int TW = 32, TH = OCRS_MF_TH_OF(CINB, COUT, NST), TP = TW * TH;
+    static constexpr int TW = 32, TH = mf_th(CINB, COUT, NST), TP = TW * TH;
     static constexpr int DW_ = TW + 2, DH_ = TH + 2, DP = DW_ * DH_;
     static constexpr int CGB = CINB / 8;
     static constexpr int PX = MmPitch<CINB>::V;
@@ -1312,11 +1137,7 @@ __global__ __launch_bounds__(512, (mm_fwd_lb<CINB, COUT>())) void k_mm_fwd(Src2<
     float* s_stat = s_wp + COUT * CIN;                           // [wave][MT*16][2]
     const int H = tg.H, W = tg.W;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15;
-#if OCRS_MM_SW
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: tile rows / first columns of the wave's N tiles become scalar code)
-#else
-    const int wave = tid >> 6;
-#endif
 
     fill_tr8(s_trx, x, tra, trb, CIN, tid);
     for (int i = tid; i < 9 * CIN; i += NT) s_w9[i] = wdw[i];
@@ -1667,8 +1488,7 @@ static void mm_fwd_launch(const Src2<bf16>& x, const float* tra, const float* tr
     using CC = MfCfg<CINB, NST, COUT>;
     const Tiling2 tg = make_tiling2(N, H, W, CC::TW, CC::TH);
     // (set per call: the attribute is per device and this is called from any thread; it is a cheap host-side table update)
-    static const int full_on = env_int("OCRS_MM_FULL", 1);
-    const bool full = full_on && H % CC::TH == 0 && W % CC::TW == 0 && (!pooled || ((H | W) & 1) == 0);
+    const bool full = H % CC::TH == 0 && W % CC::TW == 0 && (!pooled || ((H | W) & 1) == 0);
 #define MF_LAUNCH(PO_, FU_)                                                                                                                          \
     {                                                                                                                                                \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mm_fwd<CINB, NST, COUT, PO_, FU_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM); \
@@ -1707,8 +1527,8 @@ long ocrs_mm_fwd_supported(int Ca, int Cb, int Cout, int dtype) {
 long ocrs_mm_fwd_nparts(int Ca, int Cb, int Cout, int N, int H, int W) {
     if (rs_fwd_supported(Ca, Cb, Cout, N, H, W)) return rs_fwd_blocks(N, H, W);  // (also the grid of the tiled kernel when such a launch pools: persistent, any size)
     const int cinb = (Ca == 32 && Cb == 32) ? 32 : Ca + Cb;
-    const int th = mm_th(cinb, Cout, (Ca == 32 && Cb == 32) ? 2 : 1);
-    return mm_grid(th, N, H, W, 0, cinb == 8 ? OCRS_MF_BPC8 : ((cinb == 16 && Cout == 8) ? OCRS_MF_BPC16_8 : 2));
+    const int th = mf_th(cinb, Cout, (Ca == 32 && Cb == 32) ? 2 : 1);
+    return mm_grid(th, N, H, W, 0, (cinb == 16 && Cout == 8) ? 3 : 2);
 }
 
 // DepthwiseConv block forward on the matrix cores up to the pre-BatchNorm output (replaces ocrs_dwpw_fwd for bf16, Cin / Cout in {8, 16, 32}

@@ -1,8 +1,8 @@
 // Pointwise (1x1) conv backward of a DepthwiseConv block at the DEEP U-Net levels (gfx950, bf16, Cin in {32..256}, Cout in {64..256}), all
-// channels of a tile at once.  Same contract as k_pw_bwd / k_pw_bwd8 (det_bwd.hip, det_pw8.hip):
+// channels of a tile at once.  Same contract as k_pw_bwd (det_bwd.hip):
 //     dz = A*ghat + B*z + C;   du = Wpw^T dz (written);   dWpw += u^T dz,  u = dw3x3(x~) recomputed.
 //
-// The deep launches are latency chains, not bandwidth problems (3.7 ms of the round-1 step for 2 % of its bytes): k_pw_bwd / k_pw_bwd8 walk a
+// The deep launches are latency chains, not bandwidth problems (3.7 ms of the round-1 step for 2 % of its bytes): k_pw_bwd walks a
 // 64-pixel tile through 32- / 64-channel chunks -- ~14 phases of (global load -> LDS -> barrier -> MFMA) per tile, 11-14 us each, and for 256
 // channels the weight gradient is split over grid.y = 4 blocks that each recompute dz.  Here ONE block does a whole tile in three barriers:
 //   A  every (g, z) vector of the tile's 64 pixels x Cout channels and the whole input tile + ring (100 pixels x Cin) are loaded at once
@@ -13,22 +13,13 @@
 //      (128 per wave at 256 x 256), flushed once per block as a partial for the deterministic reducer.
 #include "det_common.h"
 
-#ifndef OCRS_PWB_TH_SMALL
-#define OCRS_PWB_TH_SMALL 8  // tile rows at 64 input channels (32: always 8 -- eight waves need eight (M, N) tile pairs)
-#endif
-#ifndef OCRS_PWB_TH_BIG
-#define OCRS_PWB_TH_BIG 4  // tile rows at >= 128 channels (32-pixel tiles: half the per-thread items)
-#endif
-#ifndef OCRS_PWB_PF
-#define OCRS_PWB_PF 1  // prefetch the next tile's raw vectors behind barrier 1
-#endif
-
 namespace {
 template <int CIN, int COUT>
 struct PwbCfg {
     // (256-thread blocks -- more resident blocks to hide a tile's ~7 k-cycle latency chain -- double the per-thread items and spill 0.5-1 KB)
     static constexpr int NT = 512, NW = NT / 64;
-    static constexpr int TW = 8, TH = (CIN >= 128 || COUT > 128) ? OCRS_PWB_TH_BIG : (CIN == 64 ? OCRS_PWB_TH_SMALL : 8), TP = TW * TH, NNT = TP / 16, HWp = TW + 2, HP = HWp * (TH + 2);
+    // tile rows: 4 at >= 128 channels (32-pixel tiles: half the per-thread items), else 8 (32 channels: eight waves need eight (M, N) tile pairs)
+    static constexpr int TW = 8, TH = (CIN >= 128 || COUT > 128) ? 4 : 8, TP = TW * TH, NNT = TP / 16, HWp = TW + 2, HP = HWp * (TH + 2);
     static constexpr int CGI = CIN / 8, CGO = COUT / 8;
     static constexpr int PXC = CIN + 8, PZC = COUT + 8;              // bf16 pitches (16-byte pad: conflict-free fragment / transpose reads)
     static constexpr int NZI = (TP * CGO + NT - 1) / NT;             // (pixel, cout group) items per thread
@@ -38,7 +29,7 @@ struct PwbCfg {
     static constexpr int MPW = MTD >= NW ? MTD / NW : 1;             // dgrad M tiles per wave
     static constexpr int NPW = MTD >= NW ? NNT : NNT * MTD / NW;     // dgrad N tiles (16 pixels) per wave
     static constexpr int WTI = CIN / 16, WTO = COUT / 16, NTW = (WTI * WTO + NW - 1) / NW;  // wgrad output tiles: per wave
-    static constexpr bool PF = OCRS_PWB_PF && !(CIN == 256 && COUT == 256);  // next tile loads in flight under the MFMA phases (registers)
+    static constexpr bool PF = !(CIN == 256 && COUT == 256);  // next tile's raw vectors in flight behind barrier 1, under the MFMA phases (registers)
     static constexpr int OFF_DZ = HP * PXC * 2, OFF_U = OFF_DZ + TP * PZC * 2, OFF_PAR = (OFF_U + TP * PXC * 2 + 15) & ~15;
     static constexpr int SMEM = OFF_PAR + (3 * CIN + 9 * CIN + 6 * COUT) * 4;
     static_assert(NT % CGO == 0 && NT % CGI == 0 && (MTD >= 2) && NPW >= 1 && TP % 32 == 0, "role mapping");
@@ -272,23 +263,14 @@ __global__ __launch_bounds__(512, (pwb_bpc(CIN, COUT, PPOOL) * 2)) void k_pwb(Sr
         }
     };
 
-#ifdef OCRS_PWB_PROF
-    unsigned long long pt[6] = {0, 0, 0, 0, 0, 0}, pc = __builtin_readcyclecounter();
-#define PB_MARK(i) { const unsigned long long now_ = __builtin_readcyclecounter(); pt[i] += now_ - pc; pc = now_; }
-#else
-#define PB_MARK(i)
-#endif
     TileSched ts(tg.ntiles);
     Raw cur;
     if (ts.first < ts.end) issue(cur, tile_origin2<TW, C::TH>(tg, (int)ts.first));
     for (long t = ts.first; t < ts.end; t += ts.step) {
         const TileOrg org = tile_origin2<TW, C::TH>(tg, (int)t);
         if (!C::PF && t != ts.first) issue(cur, org);
-        PB_MARK(5)
         commit(cur, org);
-        PB_MARK(0)
         __syncthreads();  // (1) dzN, xs complete
-        PB_MARK(1)
         // ---- C1: du = Wpw^T dz.  ALL weight fragments of the wave are loaded before the next tile's prefetch is issued: vector loads retire in
         // order, so a fragment load behind the prefetch would wait for the whole prefetch (the first version ran 10-20 us per tile that way)
         {
@@ -325,7 +307,6 @@ __global__ __launch_bounds__(512, (pwb_bpc(CIN, COUT, PPOOL) * 2)) void k_pwb(Sr
                 }
             }
         }
-        PB_MARK(2)
         // ---- C2: u = dw3x3(x~) for this thread's (pixel, cin group) items: the nine weight vectors of the group are read once per tile
         {
             float u[NUI][8];
@@ -361,7 +342,6 @@ __global__ __launch_bounds__(512, (pwb_bpc(CIN, COUT, PPOOL) * 2)) void k_pwb(Sr
                 }
             }
         }
-        PB_MARK(3)
         __syncthreads();  // (2) uN complete
         // ---- E: dWpw += u^T dz, K = the tile's 64 pixels
 #pragma unroll
@@ -378,15 +358,7 @@ __global__ __launch_bounds__(512, (pwb_bpc(CIN, COUT, PPOOL) * 2)) void k_pwb(Sr
             }
         }
         __syncthreads();  // (3) tiles free for the next commit
-        PB_MARK(4)
     }
-#ifdef OCRS_PWB_PROF
-    if (blockIdx.x == 0 && tid == 0) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(du);
-        for (int i = 0; i < 6; ++i) o[i] = pt[i];
-        o[6] = (ts.end - ts.first + ts.step - 1) / ts.step;
-    }
-#endif
     // ---- flush the weight-gradient partial (master layout [COUT][CIN]): D[m = ci][n = co]
 #pragma unroll
     for (int j = 0; j < C::NTW; ++j) {
@@ -406,7 +378,7 @@ extern "C" {
 void k_wgrad_partials_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st);  // det_bwd.hip
 
 // blocks of the launch (= workspace slots of Cin * Cout floats each)
-static int pwb_th(int Cin, int Cout) { return (Cin >= 128 || Cout > 128) ? OCRS_PWB_TH_BIG : (Cin == 64 ? OCRS_PWB_TH_SMALL : 8); }
+static int pwb_th(int Cin, int Cout) { return (Cin >= 128 || Cout > 128) ? 4 : 8; }
 static int pwb_ny(int Cin) { return Cin == 256 ? 2 : 1; }  // 256 input channels: two channel ranges of the 128-channel kernel (grid.y)
 int det_pwb_gx(int Cin, int Cout, int N, int H, int W, int pooled) {
     const Tiling2 tg = make_tiling2(N, H, W, 8, pwb_th(Cin, Cout));
@@ -418,9 +390,8 @@ int det_pwb_gx(int Cin, int Cout, int N, int H, int W, int pooled) {
     return (int)g;
 }
 long det_pwb_supported(int Cin, int Cout, int dtype) {
-    static const int on = env_int("OCRS_PWB", 1);
-    // (the instantiations with Cin >= 128 spill at 256 registers -- up to 2 KB per lane at 256 x 256 -- and stay on k_pw_bwd8)
-    return on && dtype == 1 && (Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256) && (Cout == 64 || Cout == 128 || Cout == 256) && Cin * 8 >= Cout;
+    // (256 input channels: two channel ranges of the 128-channel kernel, see pwb_ny)
+    return dtype == 1 && (Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256) && (Cout == 64 || Cout == 128 || Cout == 256) && Cin * 8 >= Cout;
 }
 
 int det_pwb_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,

@@ -27,48 +27,12 @@
 #include "det_rs.h"
 #include <type_traits>
 
-#ifndef OCRS_RS_WPS
-#define OCRS_RS_WPS 3  // waves per SIMD the kernel is compiled for (register cap 512 / WPS) = resident 4-wave workgroups per CU.  Measured in the step (8 -> 8
-                       // channels, level 0): 3 per CU 480-507 us, 4 per CU 546 us, 2 per CU 480 us -- the memory side prefers fewer, more coherent streams
-#endif
-#ifndef OCRS_RS_LD_NT
-#define OCRS_RS_LD_NT 0          // 1: non-temporal prefetch loads (measurement knob)
-#endif
-#if OCRS_RS_LD_NT
-#define OCRS_RS_LD_HINT " nt"
-#else
-#define OCRS_RS_LD_HINT ""
-#endif
-#ifndef OCRS_RS_ST_AUX
-#define OCRS_RS_ST_AUX 0         // aux bits of the dx~ stores (measurement knob: 2 = nt)
-#endif
-#ifndef OCRS_RS_TICK_BARRIER
-#define OCRS_RS_TICK_BARRIER 0   // 1: the four waves of a workgroup meet at every tick (measurement knob: keeps their four adjacent strips in step)
-#endif
-#ifndef OCRS_RS_WPS_G2
-#define OCRS_RS_WPS_G2 3  // two gradient tensors: 8 more prefetch registers per set (139 VGPRs; at the 128 cap hipcc spills loop invariants, and a scratch reload is a vmcnt(0))
-#endif
-#ifndef OCRS_RS_8_16
-#define OCRS_RS_8_16 1  // 8 -> 16 channels on this kernel (two waves per SIMD, per-channel coefficients of the 16-channel side in vector registers): 772 -> 725 us at
-                        // level 0.  16 -> 8 and 16 -> 16 were measured too (-DOCRS_RS_16): 754 vs 645 us and 660 vs 227 us -- they stay on k_mm_bwd
-#endif
-#ifndef OCRS_RS_816_SC
-#define OCRS_RS_816_SC 1
-#endif
-#ifndef OCRS_RS_WPS_16
-#define OCRS_RS_WPS_16 2  // a 16-channel side: twice the prefetch registers / coefficient pairs / G accumulators (spills at the 168-register cap of 3)
-#endif
-#ifndef OCRS_RS_WPS_8_16
-#define OCRS_RS_WPS_8_16 2  // 8 -> 16 channels, one gradient tensor: fits 168 registers without spills, but three workgroups per CU measured 831 us against 725 us
-                            // with two (level 0; k_mm_bwd: 772 us) -- as for 8 -> 8 channels the memory side prefers fewer streams
-#endif
-template <int CIN, int COUT, bool G2>
-constexpr int rs_wps() {
-    return (CIN == 8 && COUT == 8) ? (G2 ? OCRS_RS_WPS_G2 : OCRS_RS_WPS) : ((CIN == 8 && COUT == 16 && !G2) ? OCRS_RS_WPS_8_16 : OCRS_RS_WPS_16);
-}
-static int rs_wps_rt(int Cin, int Cout, int g2) {
-    return (Cin == 8 && Cout == 8) ? (g2 ? OCRS_RS_WPS_G2 : OCRS_RS_WPS) : ((Cin == 8 && Cout == 16 && !g2) ? OCRS_RS_WPS_8_16 : OCRS_RS_WPS_16);
-}
+// Waves per SIMD the kernel is compiled for (register cap 512 / WPS) = resident 4-wave workgroups per CU.  The memory side prefers fewer, more
+// coherent streams.  8 -> 8 channels: 3 (measured in the step at level 0: 3 per CU 480-507 us, 4 per CU 546 us, 2 per CU 480 us; with two gradient
+// tensors 139 VGPRs -- at the 128 cap of 4 hipcc spills loop invariants, and a scratch reload is a vmcnt(0)).  A 16-channel side: 2 (twice the
+// prefetch registers / coefficient pairs / G accumulators, spills at the 168-register cap of 3; 8 -> 16 fits 168 without spills, but three
+// workgroups per CU measured 831 us against 725 us with two).
+constexpr int rs_wps(int cin, int cout) { return (cin == 8 && cout == 8) ? 3 : 2; }
 
 namespace {
 
@@ -162,26 +126,26 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* p, unsigned bytes) {
 // tools/check_rs_loads.py verifies that hipcc leaves the destination registers alone between the load and its wait.
 __device__ __forceinline__ u32x4 bload16_opaque(const i32x4& rsrc, int voff) {
     u32x4 r;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" OCRS_RS_LD_HINT : "=&v"(r) : "v"(voff), "s"(rsrc) : "memory");
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(r) : "v"(voff), "s"(rsrc) : "memory");
     return r;
 }
 __device__ __forceinline__ unsigned bload2_opaque(const i32x4& rsrc, int voff) {
     unsigned r;
-    asm volatile("buffer_load_ushort %0, %1, %2, 0 offen" OCRS_RS_LD_HINT : "=&v"(r) : "v"(voff), "s"(rsrc) : "memory");
+    asm volatile("buffer_load_ushort %0, %1, %2, 0 offen" : "=&v"(r) : "v"(voff), "s"(rsrc) : "memory");
     return r;
 }
 __device__ __forceinline__ unsigned bload4_opaque(const i32x4& rsrc, int voff) {
     unsigned r;
-    asm volatile("buffer_load_dword %0, %1, %2, 0 offen" OCRS_RS_LD_HINT : "=&v"(r) : "v"(voff), "s"(rsrc) : "memory");
+    asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=&v"(r) : "v"(voff), "s"(rsrc) : "memory");
     return r;
 }
 // in-place forms ("+v": the load's destination IS the variable's current register -- with a fresh "=&v" output hipcc may give the value a new register
 // and join the two at a loop header with a copy issued while the load is still in flight, which tools/check_rs_loads.py caught in k_rs_fwd)
 __device__ __forceinline__ void bload16_inplace(u32x4& r, const i32x4& rsrc, int voff) {
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" OCRS_RS_LD_HINT : "+v"(r) : "v"(voff), "s"(rsrc) : "memory");
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(r) : "v"(voff), "s"(rsrc) : "memory");
 }
 __device__ __forceinline__ void bload2_inplace(unsigned& r, const i32x4& rsrc, int voff) {
-    asm volatile("buffer_load_ushort %0, %1, %2, 0 offen" OCRS_RS_LD_HINT : "+v"(r) : "v"(voff), "s"(rsrc) : "memory");
+    asm volatile("buffer_load_ushort %0, %1, %2, 0 offen" : "+v"(r) : "v"(voff), "s"(rsrc) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void wait_vm(unsigned& r) {
@@ -291,7 +255,7 @@ __device__ __forceinline__ double rs_parts_chain_sum(const float* __restrict__ p
 // k_c1_bwd_fin combines them with the forward-only sums (k_c1_fwd2: sum u, u^2, u img(tap), img(tap)) once the batch sums S1 / S2 are complete.
 // This launch then stores no dx~ at all.
 template <int CIN, int COUT, bool G2, bool SPLIT, bool HEAD = false, bool XU = false, bool C1 = false>
-__global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArgs A) {
+__global__ __launch_bounds__(256, (rs_wps(CIN, COUT))) void k_rs_bwd(RsArgs A) {
     static_assert(!HEAD || (!G2 && COUT == 8), "head gradient: one 8-channel source");
     static_assert(!XU || (CIN == 8 && !SPLIT), "u plane: one 8-channel source");
     static_assert(!C1 || XU, "first-block sums: the block behind the first block");
@@ -357,7 +321,7 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
     };
     using BO = std::integral_constant<bool, SO>;
     using BI = std::integral_constant<bool, SI>;
-    using BC = std::integral_constant<bool, SO || (SI && OCRS_RS_816_SC)>;  // 8 -> 16 channels: the dz coefficients A, B stay scalar (32 SGPRs), the BatchNorm scale goes to vector registers
+    using BC = std::integral_constant<bool, SO || SI>;  // 8 -> 16 channels: the dz coefficients A, B stay scalar (32 SGPRs), the BatchNorm scale goes to vector registers
     f32x2 bs2[COUT / 2], bt2[COUT / 2], ca2[COUT / 2], cb2[COUT / 2], cc2[COUT / 2], sc2[CIN / 2], sh2[CIN / 2];
     float lo1[CIN];
 #pragma unroll
@@ -433,7 +397,7 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
     for (int a = 0; a < MTG; ++a)
 #pragma unroll
         for (int u = 0; u < NU; ++u) accG[a][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    constexpr bool WREG = KC <= 4 && rs_wps<CIN, COUT, G2>() <= 3;  // the A fragments stay in registers when they are few
+    constexpr bool WREG = KC <= 4 && rs_wps(CIN, COUT) <= 3;  // the A fragments stay in registers when they are few
     u32x4 wfr[WREG ? KC : 1];
     if constexpr (WREG) {
 #pragma unroll
@@ -466,9 +430,6 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
     }
     auto corner = [&](const RsTick& t) -> int {  // pixel index of (row 2q clamped into the image, column 30 s - 1): may be -1 / beyond a row end
         const int qc = t.q < 0 ? 0 : (t.q >= A.NP ? A.NP - 1 : t.q);
-#ifdef OCRS_RS_NOLOAD  // (floor-measurement build: every tick re-reads the same lines)
-        return (wave * 2) * W;
-#endif
         return (t.n * H + 2 * qc) * W + SW * t.s - 1;
     };
     auto issue = [&](auto ST, const RsTick& t) {
@@ -494,19 +455,11 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
         }
     };
     // operations a tick issues: its loads (behind its commit), then its compute's stores
-#ifdef OCRS_RS_NOCOMPUTE
-    constexpr int NLOADS = NZ * (G2 ? 3 : (HEAD ? 1 : 2)) + (HEAD ? 1 : 0) + NX + (C1 ? 1 : 0), NSTORE = 0;
-#else
     constexpr int NLOADS = NZ * (G2 ? 3 : (HEAD ? 1 : 2)) + (HEAD ? 1 : 0) + NX + (C1 ? 1 : 0), NSTORE = C1 ? 0 : NX;  // (C1: dx~ is consumed here, not stored)
-#endif
     auto commit = [&](auto ST, auto YOUNGER, const RsTick& t) {
         constexpr int S = decltype(ST)::value;
         {   // the hand-written wait: YOUNGER = operations issued after this set's last load (vector memory operations retire in order)
-#ifdef OCRS_RS_DRAIN  // (debug build: wait for everything)
-            constexpr int Y = 0;
-#else
             constexpr int Y = decltype(YOUNGER)::value;
-#endif
             if constexpr (XU) wait_vm<Y>(pxu[S]);
             else wait_vm<Y>(pxr[S][NX - 1]);
             if constexpr (C1) wait_vm<Y>(pim[S]);
@@ -602,11 +555,7 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
         }
         const int colbase = SW * t.s - 1;
         const int pix0 = (t.n * H + 2 * cp) * W + colbase;
-#ifdef OCRS_RS_NOSTORE  // (floor-measurement build: every store is dropped by the range check)
-        const bool comp = false;
-#else
         const bool comp = t.comp != 0;
-#endif
         // ================= dx~ = Weff^T (*) dz =================
         unsigned ra[4];
 #pragma unroll
@@ -656,7 +605,7 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
                 } else {
                     const bool in_a = !SPLIT || 8 * j < Ca;
                     const int off = pix0 * ((in_a ? Ca : Cb) * 2) + lxo[j];
-                    __builtin_amdgcn_raw_buffer_store_b128((u32x4){q.x, q.y, q.z, q.w}, in_a ? w_a : w_b, ok ? off : -1, 0, OCRS_RS_ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128((u32x4){q.x, q.y, q.z, q.w}, in_a ? w_a : w_b, ok ? off : -1, 0, 0);
                 }
             }
         }
@@ -741,15 +690,10 @@ __global__ __launch_bounds__(256, (rs_wps<CIN, COUT, G2>())) void k_rs_bwd(RsArg
     issue(S0{}, t0);
     issue(S1{}, t1);
     auto tick = [&](auto ST, auto YOUNGER, RsTick& t) __attribute__((always_inline)) {
-#if OCRS_RS_TICK_BARRIER
-        __builtin_amdgcn_s_barrier();  // (only valid while all four waves run the same number of ticks: a measurement build for full-size launches)
-#endif
         commit(ST, YOUNGER, t);
         const RsTick tn = gen.next();
         issue(ST, tn);
-#ifndef OCRS_RS_NOCOMPUTE  // (floor-measurement build: loads + commit only)
         compute(t);
-#endif
         t = tn;
     };
     // issue order: L0 L1 | [commit 0] L0' St | [commit 1] L1' St | ...: younger than a set's loads are the other set's loads and the stores of the
@@ -925,9 +869,6 @@ struct RsfArgs {
     int N, H, W, NS, NP, NB, PB, njobs;
     FwdFin fin;
 };
-#ifndef OCRS_RSF_WPS
-#define OCRS_RSF_WPS 3  // resident 4-wave workgroups per CU (per launch at level 0, XU | plain: 3: 240 | 226 us, 4: 255 | 254 us; the tiled kernel: 340 | 279 us)
-#endif
 template <int CIN, int COUT>
 struct RsfCfg {
     static_assert(CIN == 8 || (CIN == 16 && COUT == 8), "shapes of level 0: 8 -> 8 (| 16), 16 -> 8");
@@ -946,8 +887,10 @@ struct RsfCfg {
     static_assert(64 + (8 * 32 + 32) * 8 <= OFF_ST, "the finalisation's reduction area fits the dead rings");
 };
 
+// resident 4-wave workgroups per CU (per launch at level 0, XU | plain: 3: 240 | 226 us, 4: 255 | 254 us; the tiled kernel: 340 | 279 us)
+constexpr int kRsfWps = 3;
 template <int CIN, int COUT, bool XU>
-__global__ __launch_bounds__(256, OCRS_RSF_WPS) void k_rs_fwd(RsfArgs A) {
+__global__ __launch_bounds__(256, kRsfWps) void k_rs_fwd(RsfArgs A) {
     static_assert(!XU || CIN == 8, "u plane: the 8-channel output of the first block");
     using C = RsfCfg<CIN, COUT>;
     constexpr int PXB = C::PXB, ROWB = C::ROWB, RINGB = C::RINGB, KC = C::KC, NX = C::NX, NZ = C::NZ, SW = C::SW, G8 = C::G8, TPC = C::TPC, CPD = C::CPD;
@@ -1205,21 +1148,13 @@ __global__ __launch_bounds__(256, OCRS_RSF_WPS) void k_rs_fwd(RsfArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
-static int rs_env() {
-    static const int v = env_int("OCRS_RS", 1);
-    return v;
-}
 bool rs_bwd_supported(int Ca, int Cb, int Cout, int pooled, int N, int H, int W) {
-    if (!rs_env() || pooled) return false;
+    if (pooled) return false;
     const int Cin = Ca + Cb;
-    // (the kernel is written for Cin / Cout in {8, 16}, but only 8 -> 8 is instantiated: with 16 channels on either side the per-channel coefficients
+    // (the kernel is written for Cin / Cout in {8, 16}, but only 8 -> 8 and 8 -> 16 are instantiated (8 -> 16: 772 -> 725 us at level 0): with 16 channels on either side the per-channel coefficients
     //  no longer fit the scalar register file next to the descriptors -- hipcc spills SGPRs to scratch inside the tick loop, 256 VGPRs + 40-88 B of
     //  scratch -- and a scratch reload in that loop is a vmcnt(0); those shapes need LDS-resident coefficients first)
-#ifdef OCRS_RS_16
-    if (!((Cin == 8 || Cin == 16) && (Cout == 8 || Cout == 16))) return false;
-#else
-    if (!(Cin == 8 && (Cout == 8 || (OCRS_RS_8_16 && Cout == 16)))) return false;
-#endif
+    if (!(Cin == 8 && (Cout == 8 || Cout == 16))) return false;
     if (Cb != 0 && !(Ca == 8 && Cb == 8)) return false;
     const long bytes = (long)N * H * W * (Cin > Cout ? Cin : Cout) * 2;
     return bytes < (1L << 31) && H >= 2 && W >= 2;
@@ -1227,19 +1162,17 @@ bool rs_bwd_supported(int Ca, int Cb, int Cout, int pooled, int N, int H, int W)
 static void rs_geometry(int N, int H, int W, int wps, int& NS, int& NP, int& NB, int& PB, int& njobs, int& nblocks) {
     NS = (W + 29) / 30;
     NP = (H + 1) / 2;
-    static const int rb_env = env_int("OCRS_RS_RB", 64);          // rows per job (two warm-up ticks per job: 64 rows = 6 %)
-    static const int blocks_env = env_int("OCRS_RS_BLOCKS", 0);  // (tests: a small grid makes every wave run several jobs)
-    PB = rb_env / 2 > 0 ? rb_env / 2 : 1;
+    PB = 32;  // row pairs per job: 64 rows (two warm-up ticks per job = 6 %)
     NB = (NP + PB - 1) / PB;
     njobs = N * NB * NS;
-    const int cap = blocks_env > 0 ? blocks_env : kNumCU * wps;  // resident blocks (4 waves each) at wps waves per SIMD
+    const int cap = kNumCU * wps;  // resident blocks (4 waves each) at wps waves per SIMD
     const int need = (njobs + 3) / 4;
     nblocks = need < cap ? need : cap;
     if (nblocks >= 8) nblocks &= ~7;
 }
 int rs_bwd_blocks(int Cin, int Cout, int N, int H, int W, int g2) {
     int NS, NP, NB, PB, njobs, nb;
-    rs_geometry(N, H, W, rs_wps_rt(Cin, Cout, g2), NS, NP, NB, PB, njobs, nb);
+    rs_geometry(N, H, W, rs_wps(Cin, Cout), NS, NP, NB, PB, njobs, nb);
     return nb;
 }
 void rs_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, int ldw, const bf16* g1, const bf16* g2,
@@ -1259,7 +1192,7 @@ void rs_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, cons
     a.g1 = g1; a.g2 = g2; a.z = z; a.bn = bn; a.coef = coef; a.gxa = gxa; a.gxb = gxb; a.ws = ws;
     a.N = N; a.H = H; a.W = W;
     int nb;
-    rs_geometry(N, H, W, rs_wps_rt(x.Ca + x.Cb, Cout, g2 != nullptr), a.NS, a.NP, a.NB, a.PB, a.njobs, nb);
+    rs_geometry(N, H, W, rs_wps(x.Ca + x.Cb, Cout), a.NS, a.NP, a.NB, a.PB, a.njobs, nb);
     a.fin = fin;
     (void)stats;
     const int Cin = x.Ca + x.Cb;
@@ -1297,43 +1230,28 @@ void rs_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, cons
         OCRS_LAUNCH_T((k_rs_bwd<8, 8, false, false, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);
         return;
     }
-    const bool sp = x.Cb > 0;
 #define RS_CASE(CI_, CO_)                                                                 \
     if (Cin == CI_ && Cout == CO_) {                                                      \
-        if (g2) {                                                                         \
-            if (sp) RS_LAUNCH(CI_, CO_, true, (CI_ > 8)) else RS_LAUNCH(CI_, CO_, true, false)   \
-        } else {                                                                          \
-            if (sp) RS_LAUNCH(CI_, CO_, false, (CI_ > 8)) else RS_LAUNCH(CI_, CO_, false, false) \
-        }                                                                                 \
+        if (g2) RS_LAUNCH(CI_, CO_, true, false) else RS_LAUNCH(CI_, CO_, false, false)   \
     }
     RS_CASE(8, 8)
-#if OCRS_RS_8_16
     RS_CASE(8, 16)
-#endif
-#ifdef OCRS_RS_16
-    RS_CASE(16, 8) RS_CASE(16, 16)
-#endif
 #undef RS_CASE
 #undef RS_LAUNCH
 }
 
 // ---- row-streaming forward (k_rs_fwd): Cin = 8 (one source or the u plane) or 16 (one source or the 8 | 8 concat), Cout = 8, no fused pooling
 bool rs_fwd_supported(int Ca, int Cb, int Cout, int N, int H, int W) {
-    static const int on = env_int("OCRS_RSF", 1);
-    static const int on16 = env_int("OCRS_RSF_C16", 1);  // the 16 -> 8 channel block of level 0
-    // (Cout = 16 -- one pass per row, 12 MFMAs per tick; the kernel is written for it, -DOCRS_RSF_16 instantiates it at OCRS_RSF_WPS <= 3 -- measured
-    //  432 us against k_mm_fwd's 346 us at level 0: not built by default)
+    // (Cout = 16 -- one pass per row, 12 MFMAs per tick; the kernel is written for it, but measured 432 us against k_mm_fwd's 346 us at level 0:
+    //  not instantiated)
     const int Cin = Ca + Cb;
-    bool shape = (Ca == 8 && Cb == 0 && Cout == 8) || (on16 && Cin == 16 && (Cb == 0 || Ca == 8) && Cout == 8);
-#ifdef OCRS_RSF_16
-    shape = shape || (Ca == 8 && Cb == 0 && Cout == 16);
-#endif
-    if (!on || !shape) return false;
+    const bool shape = (Ca == 8 && Cb == 0 && Cout == 8) || (Cin == 16 && (Cb == 0 || Ca == 8) && Cout == 8);
+    if (!shape) return false;
     return (long)N * H * W * (Cin > Cout ? Cin : Cout) * 2 < (1L << 31) && H >= 2 && W >= 2;
 }
 int rs_fwd_blocks(int N, int H, int W) {
     int NS, NP, NB, PB, njobs, nb;
-    rs_geometry(N, H, W, OCRS_RSF_WPS, NS, NP, NB, PB, njobs, nb);
+    rs_geometry(N, H, W, kRsfWps, NS, NP, NB, PB, njobs, nb);
     return nb;
 }
 void rs_fwd_launch(const Src2<bf16>& x, const bf16* xu, const float* wexp, const float* tra, const float* trb, const float* wdw, const float* wpw, bf16* z, float* ws,
@@ -1342,7 +1260,7 @@ void rs_fwd_launch(const Src2<bf16>& x, const bf16* xu, const float* wexp, const
     a.xa = x.a; a.xb = x.b; a.Ca = x.Ca; a.Cb = x.Cb; a.xu = xu; a.wexp = wexp; a.tra = tra; a.trb = trb; a.wdw = wdw; a.wpw = wpw; a.z = z; a.ws = ws;
     a.N = N; a.H = H; a.W = W;
     int nb_geo;
-    rs_geometry(N, H, W, OCRS_RSF_WPS, a.NS, a.NP, a.NB, a.PB, a.njobs, nb_geo);
+    rs_geometry(N, H, W, kRsfWps, a.NS, a.NP, a.NB, a.PB, a.njobs, nb_geo);
     (void)nb_geo;  // (the caller's nb = rs_fwd_blocks(): the number of partials it allocated)
     a.fin = fin;
 #define RSF_LAUNCH(CI_, CO_, XU_)                                                                                                              \
@@ -1356,10 +1274,5 @@ void rs_fwd_launch(const Src2<bf16>& x, const bf16* xu, const float* wexp, const
     else if (Cout == 8) {
         if (xu) RSF_LAUNCH(8, 8, true) else RSF_LAUNCH(8, 8, false)
     }
-#ifdef OCRS_RSF_16
-    else {
-        if (xu) RSF_LAUNCH(8, 16, true) else RSF_LAUNCH(8, 16, false)
-    }
-#endif
 #undef RSF_LAUNCH
 }

@@ -1457,9 +1457,8 @@ __global__ __launch_bounds__(256, 2) void k_rs32_ctd(const Rs32CD A) {
 }
 
 namespace {
+constexpr int kRs32Rows = 64;  // rows per job of the block kernels (even: a pooling window's two rows belong to one job)
 static inline int rs32_grid(int njobs, int wg_per_cu) {
-    static const int bpc_env = env_int("OCRS_RS32_BPC", 0);
-    if (bpc_env > 0) wg_per_cu = bpc_env;
     long g = (long)kNumCU * wg_per_cu;
     const long need = (njobs + 3) / 4;
     if (need < g) g = need;
@@ -1492,15 +1491,8 @@ static double* rs32_last_scratch(int ndoubles, hipStream_t st) {
 extern "C" {
 // ---- ConvTranspose weight / bias gradient launcher for ocrs_convt_bwd_parts (det_bwd.hip): fp32, Cup in {16, 32}, Cout in {8, 16, 32}
 long det_rs32_ctw_supported(int Cup, int Cout, int dtype) {
-    static const int on = env_int("OCRS_RS32", 1), onc = env_int("OCRS_RS32_CTW", 1);
-    return (on && onc && dtype == 0 && (Cup == 16 || Cup == 32) && (Cout == 8 || Cout == 16 || Cout == 32)) ? 1 : 0;
+    return (dtype == 0 && (Cup == 16 || Cup == 32) && (Cout == 8 || Cout == 16 || Cout == 32)) ? 1 : 0;
 }
-}  // extern "C"
-static int rs32_ctw_rb() {
-    static const int rb_env = env_int("OCRS_RS32_CTW_RB", 32);
-    return rb_env > 0 ? rb_env : 32;
-}
-extern "C" {
 long det_rs32_ctw_ws_floats(int Cup, int Cout, int N, int h, int w, int dtype) {
     if (!det_rs32_ctw_supported(Cup, Cout, dtype)) return 0;
     const int CE = Cout >= 16 ? 16 : 8, nl = Cout / CE;
@@ -1511,7 +1503,7 @@ int det_rs32_ctw_launch(const float* x, const float* tr, const float* g, float* 
     OCRS_CHECK_ARG(det_rs32_ctw_supported(Cup, Cout, 0) && x && tr && g && dW && dbias && ws);
     OCRS_CHECK_ARG((long)N * H * W * Cout * 4 < (1L << 32) && (long)N * h * w * Cup * 4 < (1L << 32) && H <= 2 * h + 1 && W <= 2 * w + 1);
     const int CE = Cout >= 16 ? 16 : 8, nl = Cout / CE, MT = Cup / 16, NT = (9 * CE + 15) / 16;
-    const Rs32Jobs jb = rs32_jobs(N, h, w, 16, rs32_ctw_rb());
+    const Rs32Jobs jb = rs32_jobs(N, h, w, 16, 32);
     const int grid = rs32_grid(jb.njobs, 2);
     const int ne = Cup * 9 * CE + CE;
     size_t smem = (size_t)4 * 16 * (MT + NT) * RS32_TP * sizeof(float);
@@ -1540,8 +1532,7 @@ int det_rs32_ctw_launch(const float* x, const float* tr, const float* g, float* 
 
 // 1 if ocrs_rs32_fwd runs this block shape: fp32 storage; Cin = Ca + Cb in {8, 16, 32}, a concat split only as 8 | 8 or 16 | 16; Cout in {8, 16, 32}.
 long ocrs_rs32_fwd_supported(int Ca, int Cb, int Cout, int dtype) {
-    static const int on = env_int("OCRS_RS32", 1);
-    if (!on || dtype != 0) return 0;
+    if (dtype != 0) return 0;
     const int Cin = Ca + Cb;
     if (!(Cin == 8 || Cin == 16 || Cin == 32) || !(Cout == 8 || Cout == 16 || Cout == 32)) return 0;
     if (Cb && !((Ca == 8 && Cb == 8) || (Ca == 16 && Cb == 16))) return 0;
@@ -1561,9 +1552,7 @@ int ocrs_rs32_fwd(const float* xa, const float* xb, int Ca, int Cb, const float*
     OCRS_CHECK_ARG(N > 0 && H > 0 && W > 0 && (!pooled || gamma) && (!counter || (count > 0 && bn_w && bn_b && tr && saved)));
     const int Cin = Ca + Cb, Cmax = Cin > Cout ? Cin : Cout;
     OCRS_CHECK_ARG((long)N * H * W * Cmax * 4 < (1L << 32));  // 32-bit buffer offsets
-    static const int rb_env = env_int("OCRS_RS32_RB", 64);
-    const int rb = (rb_env > 1 ? rb_env : 64) & ~1;  // even: a pooling window's two rows belong to one job
-    Rs32F a{xa, xb, tra, trb, wdw, wpw, gamma, z, pooled, gstat, Ca, Cb, Cout, N, H, W, rs32_jobs(N, H, W, RS32_COLS, rb),
+    Rs32F a{xa, xb, tra, trb, wdw, wpw, gamma, z, pooled, gstat, Ca, Cb, Cout, N, H, W, rs32_jobs(N, H, W, RS32_COLS, kRs32Rows),
             FwdFin{counter, count, bn_w, bn_b, eps, momentum, tr, saved, run_mean, run_var, nbt, lo}};
     const int nset = Cin > 16 ? 2 : 1, mt = Cout > 16 ? 2 : 1;
     const int grid = rs32_grid(a.jb.njobs, nset * mt == 1 ? 3 : 2);
@@ -1583,18 +1572,12 @@ int ocrs_rs32_fwd(const float* xa, const float* xb, int Ca, int Cb, const float*
 
 // 1 if ocrs_rs32_bwd runs this block shape: fp32 storage, direct (not max-pooled) gradient source, Cin = Ca + Cb in {8, 16} (concat 8 | 8), Cout in {8, 16}
 long ocrs_rs32_bwd_supported(int Ca, int Cb, int Cout, int pooled, int dtype) {
-    static const int on = env_int("OCRS_RS32", 1), onb = env_int("OCRS_RS32_BWD", 1), onp = env_int("OCRS_RS32_BWDP", 1);
-    if (!on || !onb || dtype != 0 || (pooled && (!onp || Cb))) return 0;
+    if (dtype != 0 || (pooled && Cb)) return 0;
     const int Cin = Ca + Cb;
-    static const int onx = env_int("OCRS_RS32_BWDX", 1);
-    if (onx && !pooled && ((Ca == 16 && Cb == 16 && Cout == 16) || (Ca == 16 && Cb == 0 && Cout == 32))) return 1;  // level 1: two single-source passes / k_rs32_bwdx
+    if (!pooled && ((Ca == 16 && Cb == 16 && Cout == 16) || (Ca == 16 && Cb == 0 && Cout == 32))) return 1;  // level 1: two single-source passes / k_rs32_bwdx
     if (!(Cin == 8 || Cin == 16) || !(Cout == 8 || Cout == 16)) return 0;
     if (Cb && !(Ca == 8 && Cb == 8)) return 0;
     return 1;
-}
-static int rs32_bwd_rb() {
-    static const int rb_env = env_int("OCRS_RS32_RB", 64);
-    return (rb_env > 1 ? rb_env : 64) & ~1;
 }
 long ocrs_rs32_bwd_ws_floats(int Ca, int Cb, int Cout, int N, int H, int W) {
     const int Cin = Ca + Cb;
@@ -1615,7 +1598,7 @@ static int rs32_bwd_one(const float* x, const float* tr, const float* wdw, const
         bl.raw = p;
         bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
     }
-    Rs32B a{x, nullptr, tr, nullptr, wdw, wpw, g1, g2, z, bn, gx, nullptr, ws, Cin, 0, Cout, N, H, W, rs32_jobs(N, H, W, RS32_COLS, rs32_bwd_rb()),
+    Rs32B a{x, nullptr, tr, nullptr, wdw, wpw, g1, g2, z, bn, gx, nullptr, ws, Cin, 0, Cout, N, H, W, rs32_jobs(N, H, W, RS32_COLS, kRs32Rows),
             BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, ldw, nullptr, nullptr};
     const int grid = rs32_grid(a.jb.njobs, 3);
 #define RS32O_CASE(G2_, ST_)                                                                          \
@@ -1663,10 +1646,9 @@ int ocrs_rs32_bwd(const float* xa, const float* xb, int Ca, int Cb, const float*
         bl.raw = p;
         bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
     }
-    static const int dual_on = env_int("OCRS_RS32_DUAL", 1);
-    const bool dual = dual_on && !pooled && Cb == 0 && Cin == 8 && Cout == 8;  // two 14-column strips per wave (8-channel tensors fill half the lanes)
+    const bool dual = !pooled && Cb == 0 && Cin == 8 && Cout == 8;  // two 14-column strips per wave (8-channel tensors fill half the lanes)
     Rs32B a{xa, xb, tra, trb, wdw, wpw, g1, g2, z, bn, gxa, gxb, ws, Ca, Cb, Cout, N, H, W,
-            rs32_jobs(N, H, W, pooled ? RS32P_COLS : (dual ? 2 * RS32_COLS : RS32_COLS), rs32_bwd_rb()), BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, Cin, nullptr, nullptr};
+            rs32_jobs(N, H, W, pooled ? RS32P_COLS : (dual ? 2 * RS32_COLS : RS32_COLS), kRs32Rows), BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, Cin, nullptr, nullptr};
     const bool wide = Cin > 16 || Cout > 16;
     const int grid = rs32_grid(a.jb.njobs, (pooled || wide || (dual && g2)) ? 2 : 3);
     if (wide) {
@@ -1714,11 +1696,10 @@ int ocrs_rs32_bwd(const float* xa, const float* xb, int Ca, int Cb, const float*
     return OCRS_OK;
 }
 
-// 1 if ocrs_rs32_convt_fwd runs this shape: fp32, (Cup, Cout) in {(16, 8), (32, 16)} ((32, 32) is built and tested but slower than k_convt_fwd: OCRS_RS32_CTF_3232=1)
+// 1 if the model runs this shape through ocrs_rs32_convt_fwd: fp32, (Cup, Cout) in {(16, 8), (32, 16)}.  The entry point also takes (32, 32), but at
+// level 2 (256 MFMAs per strip row) that measured 296 us against 253 us on k_convt_fwd.
 long ocrs_rs32_convt_fwd_supported(int Cup, int Cout, int dtype) {
-    static const int on = env_int("OCRS_RS32", 1), onf = env_int("OCRS_RS32_CTF", 1);
-    static const int on32 = env_int("OCRS_RS32_CTF_3232", 0);  // (32, 32) at level 2: 256 MFMAs per strip row -- measured 296 us vs 253 us on k_convt_fwd: off
-    return (on && onf && dtype == 0 && ((Cup == 16 && Cout == 8) || (Cup == 32 && (Cout == 16 || (Cout == 32 && on32))))) ? 1 : 0;
+    return (dtype == 0 && ((Cup == 16 && Cout == 8) || (Cup == 32 && Cout == 16))) ? 1 : 0;
 }
 // ConvTranspose2d(Cup, Cout, kernel_size=3, stride=2) + bias, cropped to the skip tensor's H x W (models.py:76-78, 87), fp32, row-streaming form.
 //   x [N][h][w][Cup] with load transform tr [3][Cup]; wt: the fp32 master weight [Cup][Cout][3][3] (reference layout); out [N][H][W][Cout], H <= 2 h + 1.
@@ -1726,8 +1707,7 @@ int ocrs_rs32_convt_fwd(const float* x, const float* tr, const float* wt, const 
                         hipStream_t st) {
     OCRS_CHECK_ARG(((Cup == 16 && Cout == 8) || (Cup == 32 && (Cout == 16 || Cout == 32))) && x && tr && wt && bias && out && N > 0 && h > 0 && w > 0 && H <= 2 * h + 1 && W <= 2 * w + 1);
     OCRS_CHECK_ARG((long)N * H * W * Cout * 4 < (1L << 32) && (long)N * h * w * Cup * 4 < (1L << 32));
-    static const int rb_env = env_int("OCRS_RS32_CTF_RB", 32);
-    Rs32CF a{x, tr, wt, bias, out, Cup, Cout, N, h, w, H, W, rs32_jobs(N, h + 1, w + 1, 15, rb_env > 0 ? rb_env : 32)};
+    Rs32CF a{x, tr, wt, bias, out, Cup, Cout, N, h, w, H, W, rs32_jobs(N, h + 1, w + 1, 15, 32)};
     const int nset = Cup / 16, mt = 4 * Cout / 16;
     const int grid = rs32_grid(a.jb.njobs, 2);
     const size_t smem = (size_t)mt * 4 * nset * 64 * 4 * sizeof(float);
@@ -1750,8 +1730,7 @@ int ocrs_rs32_convt_fwd(const float* x, const float* tr, const float* wt, const 
 
 // 1 if ocrs_rs32_convt_dgrad runs this shape: fp32, (Cup, Cout) in {(16, 8), (32, 16)}
 long ocrs_rs32_convt_dgrad_supported(int Cup, int Cout, int dtype) {
-    static const int on = env_int("OCRS_RS32", 1), ond = env_int("OCRS_RS32_CTD", 1);
-    return (on && ond && dtype == 0 && ((Cup == 16 && Cout == 8) || (Cup == 32 && Cout == 16))) ? 1 : 0;
+    return (dtype == 0 && ((Cup == 16 && Cout == 8) || (Cup == 32 && Cout == 16))) ? 1 : 0;
 }
 // ConvTranspose2d input gradient in fp32, row-streaming form (the dx half of ocrs_convt_bwd_parts; autograd of models.py:76-78 as train_detection.py:96
 // runs it): g [N][H][W][Cout] the gradient w.r.t. the (cropped) output, wt the fp32 MASTER weight [Cup][Cout][3][3], dx [N][h][w][Cup] = dL/dx~.
@@ -1769,8 +1748,7 @@ int ocrs_rs32_convt_dgrad(const float* g, const float* wt, float* dx, const floa
         bl.raw = p;
         bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cup);
     }
-    static const int rb_env = env_int("OCRS_RS32_CTD_RB", 32);
-    Rs32CD a{g, wt, x, tr, dx, Cup, Cout, N, h, w, H, W, rs32_jobs(N, h, w, 16, rb_env > 0 ? rb_env : 32), bl};
+    Rs32CD a{g, wt, x, tr, dx, Cup, Cout, N, h, w, H, W, rs32_jobs(N, h, w, 16, 32), bl};
     const int grid = rs32_grid(a.jb.njobs, 2);
 #define CTD32_CASE(MT_, CE_, ST_)                                                               \
     if (Cup == 16 * MT_ && Cout == CE_ && stats == ST_) {                                       \
@@ -1785,8 +1763,7 @@ int ocrs_rs32_convt_dgrad(const float* g, const float* wt, float* dx, const floa
 
 // 1 if ocrs_rs32_bwd_head runs the block in front of out_conv: fp32, 8 -> 8, single source
 long ocrs_rs32_bwd_head_supported(int Ca, int Cb, int Cout, int dtype) {
-    static const int onh = env_int("OCRS_RS32_HEAD", 1);
-    return (onh && Cb == 0 && Ca == 8 && Cout == 8 && ocrs_rs32_bwd_supported(Ca, Cb, Cout, 0, dtype)) ? 1 : 0;
+    return (Cb == 0 && Ca == 8 && Cout == 8 && ocrs_rs32_bwd_supported(Ca, Cb, Cout, 0, dtype)) ? 1 : 0;
 }
 // ocrs_rs32_bwd for the block in front of out_conv (models.py:125-129): its output gradient is formed on the fly, g[p][c] = gl[p] * whead[c], from out_conv's
 // dL/dlogit gl [P] fp32 (ocrs_head_bwd_gl / ocrs_head_bwd_loss write 4 instead of 32 bytes per pixel) -- the same fp32 product ocrs_head_bwd stores, so every
@@ -1805,18 +1782,12 @@ int ocrs_rs32_bwd_head(const float* xa, int Ca, const float* tra, const float* w
         bl.raw = p;
         bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
     }
-    static const int dual_on = env_int("OCRS_RS32_DUAL", 1);
-    const bool dual = dual_on != 0;
+    // two 14-column strips per wave (8-channel tensors fill half the lanes)
     Rs32B a{xa, nullptr, tra, nullptr, wdw, wpw, nullptr, nullptr, z, bn, gxa, nullptr, ws, Ca, 0, Cout, N, H, W,
-            rs32_jobs(N, H, W, dual ? 2 * RS32_COLS : RS32_COLS, rs32_bwd_rb()), BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, Cin, gl, whead};
+            rs32_jobs(N, H, W, 2 * RS32_COLS, kRs32Rows), BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, Cin, gl, whead};
     const int grid = rs32_grid(a.jb.njobs, 3);
-    if (dual) {
-        if (stats) OCRS_LAUNCH_T((k_rs32_bwd<false, false, true, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
-        else OCRS_LAUNCH_T((k_rs32_bwd<false, false, false, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
-    } else {
-        if (stats) OCRS_LAUNCH_T((k_rs32_bwd<false, false, true, 1, false, true>), dim3(grid), dim3(256), 0, st, a);
-        else OCRS_LAUNCH_T((k_rs32_bwd<false, false, false, 1, false, true>), dim3(grid), dim3(256), 0, st, a);
-    }
+    if (stats) OCRS_LAUNCH_T((k_rs32_bwd<false, false, true, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
+    else OCRS_LAUNCH_T((k_rs32_bwd<false, false, false, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
     OCRS_LAUNCH_CHECK();
     bwd_reduce_or_defer(ws, grid, Cout * Cin + 9 * Cin, dwpw, Cout * Cin, Cin, Cin, dwdw, 9 * Cin, st);
     OCRS_LAUNCH_CHECK();

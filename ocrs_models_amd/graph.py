@@ -17,9 +17,9 @@ after a scheduler step); no gradient bucketer (single GPU).
 """
 from __future__ import annotations
 
-import os
-
 import torch
+
+from .models import _DetRun
 
 
 class GraphedTrainStep:
@@ -29,8 +29,8 @@ class GraphedTrainStep:
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
         self.x = example_input.clone()
         self.t = example_target.clone()
-        prev = os.environ.get("OCRS_OVERLAP")
-        os.environ["OCRS_OVERLAP"] = "0"  # (the side-stream overlap of the ConvTranspose weight gradients is a fork/join the capture does not need)
+        prev = _DetRun.overlap
+        _DetRun.overlap = False  # (the side-stream overlap of the ConvTranspose weight gradients is a fork/join the capture does not need)
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -50,10 +50,7 @@ class GraphedTrainStep:
                     if st:
                         st["step"] -= 1
         finally:
-            if prev is None:
-                os.environ.pop("OCRS_OVERLAP", None)
-            else:
-                os.environ["OCRS_OVERLAP"] = prev
+            _DetRun.overlap = prev
 
     def _body(self):
         self.opt.zero_grad(set_to_none=True)

@@ -14,8 +14,6 @@ from __future__ import annotations
 
 import math
 
-import os
-
 import torch
 from torch import nn
 
@@ -98,6 +96,16 @@ class _DetRun:
     """One forward (and later backward) pass of the detection network on the current stream."""
 
     capture = None  # (test tap, see __init__)
+    # deep-level ConvTranspose weight gradients on a side stream (they overlap the latency-bound kernels that follow); GraphedTrainStep turns it
+    # off around its warm-up and capture (a fork / join the graph does not need)
+    overlap = True
+    # round-5 rank-one ends of the network, each compared bit for bit against the path it replaced
+    # (tests/test_edge_cases_gpu.py::test_rank_one_ends_of_the_network_are_bit_identical_to_the_stored_paths):
+    #   c1_u: the first block also writes its 2-byte-per-pixel u plane (read by in_conv.seq.1's forward and backward instead of z)
+    #   c1_noz: ... and does not store its 8-channel output at all when every consumer takes the u plane
+    #   c1_fuse: the first block's weight gradient from sums accumulated by in_conv.seq.1's backward (no dL/dx~ store, no k_c1_bwd2 pass)
+    #   head_gl: out_conv's backward hands the last block gl (4 B / pixel) instead of its 8-channel gradient
+    _switches = {"c1_u": True, "c1_noz": True, "c1_fuse": True, "head_gl": True}
 
     def __init__(self, mod, x, names, params, train):
         self.L = lib()
@@ -112,21 +120,12 @@ class _DetRun:
         self.N = x.shape[0]
         self.recs = {}
         self.fused = {}  # block prefix -> fp64 [2][C] BatchNorm-backward sums accumulated by its consumers' dw_bwd
-        self.fuse_bn_bwd = os.environ.get("OCRS_FUSE_BN_BWD", "1") != "0"
-        # block backward on the matrix cores (csrc/det_mm.hip): bf16, levels 0-2
-        self.use_mm = os.environ.get("OCRS_MM", "1") != "0"
-        # max-pool written by the producing block's forward kernel (levels 0-2) instead of a separate pass over the full-size z
-        self.fuse_pool = os.environ.get("OCRS_FUSE_POOL", "1") != "0"
-        # deep-level ConvTranspose weight gradients on a side stream (they overlap the latency-bound kernels that follow)
-        self.overlap = os.environ.get("OCRS_OVERLAP", "1") != "0"
-        # BatchNorm-backward finalisation in the prologue of the matrix-core block backward instead of its own launch
-        self.fold_fin = os.environ.get("OCRS_FOLD_FIN", "1") != "0"
-        self.fold_fwd_fin = os.environ.get("OCRS_FOLD_FWD_FIN", "1") != "0"
-        self.c1_noz = os.environ.get("OCRS_C1_NOZ", "1") != "0"  # ... and does not store its 8-channel output at all when every consumer takes the u plane
-        self.c1_fuse = os.environ.get("OCRS_C1_FUSE", "1") != "0"  # the first block's weight gradient from sums accumulated by in_conv.seq.1's backward (no dL/dx~ store, no k_c1_bwd2 pass)
-        self.c1_u = os.environ.get("OCRS_C1_U", "1") != "0"  # the first block also writes its 2-byte-per-pixel u plane (read by in_conv.seq.1's backward instead of z)
-        self.use_rs32 = os.environ.get("OCRS_RS32", "1") != "0"  # fp32: the wide-level blocks as row-streaming waves (csrc/det_rs32.hip, round 6)
-        self.head_gl = os.environ.get("OCRS_HEAD_GL", "1") != "0"  # out_conv's backward hands the last block gl (4 B / pixel) instead of its 8-channel gradient  # BatchNorm statistics finalised inside the matrix-core forward launch
+        # routing switches, all on; tests/test_det_ops_gpu.py turns them off on a run to compare the paths: the matrix-core block kernels
+        # (csrc/det_mm.hip, bf16 levels 0-2), the fp32 row-streaming kernels (csrc/det_rs32.hip), BatchNorm-backward sums produced by the
+        # consumers' backward pass instead of a bn_bwd_reduce pass, BatchNorm statistics finalised inside the forward launch
+        self.use_mm = self.use_rs32 = self.fuse_bn_bwd = self.fold_fwd_fin = True
+        sw = _DetRun._switches
+        self.c1_u, self.c1_noz, self.c1_fuse, self.head_gl = sw["c1_u"], sw["c1_noz"], sw["c1_fuse"], sw["head_gl"]
         self.pooled_by_block = None
         self.x = x
         # test tap (tests/test_det_bf16_layerwise_gpu.py): when the module carries a dict ``_capture`` every backward stage records the gradient
@@ -256,26 +255,24 @@ class _DetRun:
         wdw, wpw = P[f"{prefix}.seq.0.weight"], P[f"{prefix}.seq.1.weight"]
         z = self.empty(N, H, W, Cout)
         Cb = b.C if b is not None else 0
+        bnp, Bf = f"{prefix}.seq.2", self.Bf
+        # (training: the BatchNorm statistics are finalised by the last workgroup of the forward launch, bit-identical to the separate finalisation)
         if self.use_mm and L.mm_fwd_supported(a.C, Cb, Cout, self.dt):
             # depthwise + pointwise as ONE implicit GEMM on the matrix cores; batch statistics as deterministic per-block partials
             pooled = gamma = None
-            if pool and self.fuse_pool:
+            if pool:  # max-pool written by the same kernel instead of a separate pass over the full-size z
                 pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
             self.pooled_by_block = pooled
             nparts = L.mm_fwd_nparts(a.C, Cb, Cout, N, H, W)
             parts = self.empty(nparts * 2 * Cout, dtype=torch.float32)
-            bnp = f"{prefix}.seq.2"
             if self.train and self.fold_fwd_fin and a.u is not None and b is None and pooled is None and Cout in (8, 16):
                 # the block behind the first block: its input is rebuilt from the first block's u plane (2 instead of 16 bytes per pixel)
                 tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-                Bf = self.Bf
                 L.mm_fwd_fin_xu(ptr(a.u), ptr(a.wexp), ptr(a.tr), ptr(wdw), ptr(wpw), ptr(z), ptr(parts), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]),
                                 ptr(P[f"{bnp}.bias"]), 1e-5, 0.1, ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]),
                                 ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0, Cout, N, H, W, self.dt)
             elif self.train and self.fold_fwd_fin:
-                # the BatchNorm statistics are finalised by the last workgroup of the same launch (bit-identical to ocrs_bn_finalize_parts)
                 tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-                Bf = self.Bf
                 L.mm_fwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
                              ptr(z), ptr(parts), ptr(gamma), ptr(pooled), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]), ptr(P[f"{bnp}.bias"]),
                              1e-5, 0.1, ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]),
@@ -284,18 +281,13 @@ class _DetRun:
                 L.mm_fwd(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
                          ptr(z), ptr(parts), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
                 tr, saved = self.bn_tr(bnp, parts, N * H * W, Cout, nparts=nparts)
-            r = _BlockRec()
-            r.prefix, r.a, r.b, r.z, r.tr, r.saved, r.Cin, r.Cout, r.H, r.W = prefix, a, b, z, tr, saved, Cin, Cout, H, W
-            self.recs[prefix] = r
-            return _Act(z, tr, Cout, H, W, src=prefix)
-        if self.use_rs32 and L.rs32_fwd_supported(a.C, Cb, Cout, self.dt) and N * H * W * max(Cin, Cout) * 4 < 2 ** 32:  # (32-bit buffer offsets)
+        elif self.use_rs32 and L.rs32_fwd_supported(a.C, Cb, Cout, self.dt) and N * H * W * max(Cin, Cout) * 4 < 2 ** 32:  # (32-bit buffer offsets)
             # fp32 (parity mode), wide levels: register-resident row-streaming waves (csrc/det_rs32.hip) -- no LDS tile, exact-fp32 matrix cores
             pooled = gamma = None
-            if pool and self.fuse_pool:
+            if pool:
                 pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
             self.pooled_by_block = pooled
             gstat = self.zeros64(2 * Cout)
-            bnp, Bf = f"{prefix}.seq.2", self.Bf
             common = (ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw), ptr(z),
                       ptr(gstat), ptr(gamma), ptr(pooled))
             if self.train and self.fold_fwd_fin:
@@ -305,29 +297,23 @@ class _DetRun:
             else:
                 L.rs32_fwd(*common, None, 0, None, None, 0.0, 0.0, None, None, None, None, None, 0.0, Cout, N, H, W)
                 tr, saved = self.bn_tr(bnp, gstat, N * H * W, Cout)
-            r = _BlockRec()
-            r.fsum = None
-            r.prefix, r.a, r.b, r.z, r.tr, r.saved, r.Cin, r.Cout, r.H, r.W = prefix, a, b, z, tr, saved, Cin, Cout, H, W
-            self.recs[prefix] = r
-            return _Act(z, tr, Cout, H, W, src=prefix)
-        wpk = self.pack(wpw, 0, Cin, Cout, Cin, 0, 1, Cin)
-        gstat = self.zeros64(2 * Cout)
-        pooled = gamma = None
-        if pool and self.fuse_pool and L.dwpw_fwd_pool_supported(Cin, Cout):
-            pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
-        self.pooled_by_block = pooled
-        if self.train and self.fold_fwd_fin and pooled is None and L.dwpw_fwd_fin_supported(Cin, Cout, self.dt):
-            # deep levels: the BatchNorm statistics are finalised by the last workgroup of the forward launch (ocrs_bn_finalize's arithmetic)
-            bnp, Bf = f"{prefix}.seq.2", self.Bf
-            tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-            L.dwpw_fwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, a.C, b.C if b is not None else 0, ptr(a.tr), ptr(b.tr) if b is not None else None,
-                           ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]), ptr(P[f"{bnp}.bias"]), 1e-5, 0.1,
-                           ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]), ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0,
-                           Cout, N, H, W, self.dt)
         else:
-            L.dwpw_fwd(ptr(a.t), ptr(b.t) if b is not None else None, a.C, b.C if b is not None else 0, ptr(a.tr),
-                       ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
-            tr, saved = self.bn_tr(f"{prefix}.seq.2", gstat, N * H * W, Cout)
+            wpk = self.pack(wpw, 0, Cin, Cout, Cin, 0, 1, Cin)
+            gstat = self.zeros64(2 * Cout)
+            pooled = gamma = None
+            if pool and L.dwpw_fwd_pool_supported(Cin, Cout):
+                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
+            self.pooled_by_block = pooled
+            if self.train and self.fold_fwd_fin and pooled is None and L.dwpw_fwd_fin_supported(Cin, Cout, self.dt):  # deep levels (ocrs_bn_finalize's arithmetic)
+                tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
+                L.dwpw_fwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None,
+                               ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]), ptr(P[f"{bnp}.bias"]), 1e-5, 0.1,
+                               ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]), ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0,
+                               Cout, N, H, W, self.dt)
+            else:
+                L.dwpw_fwd(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr),
+                           ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
+                tr, saved = self.bn_tr(bnp, gstat, N * H * W, Cout)
         r = _BlockRec()
         r.fsum = None
         r.prefix, r.a, r.b, r.z, r.tr, r.saved, r.Cin, r.Cout, r.H, r.W = prefix, a, b, z, tr, saved, Cin, Cout, H, W
@@ -343,7 +329,7 @@ class _DetRun:
             uplane = torch.empty(N, H, W, dtype=torch.bfloat16, device=self.dev)
             # when every consumer of this block's output takes the u plane -- in_conv.seq.1's forward (ocrs_mm_fwd_fin_xu) and backward
             # (ocrs_mm_bwd_fin_xu), this block's own backward (rebuilds z) -- the 8-channel tensor is never written at all
-            if (self.c1_noz and self.capture is None and self.fold_fwd_fin and self.fold_fin and self.fuse_bn_bwd and L.mm_fwd_supported(8, 0, 8, self.dt)
+            if (self.c1_noz and self.capture is None and self.fold_fwd_fin and self.fuse_bn_bwd and L.mm_fwd_supported(8, 0, 8, self.dt)
                     and L.mm_bwd_head_supported(8, 0, 8, N, H, W, self.dt)):
                 z = None
             # round 5: with no stored 8-channel output the block's backward can also be fused away -- in_conv.seq.1's backward accumulates the first
@@ -434,14 +420,15 @@ class _DetRun:
             L.bn_bwd_reduce(ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(r.saved), ptr(gsum), C, N, H, W, self.dt)
         gam, dgam, dbet = P[f"{prefix}.seq.2.weight"], self.G[f"{prefix}.seq.2.weight"], self.G[f"{prefix}.seq.2.bias"]
         a, b = r.a, r.b
+        # block backward on the matrix cores (csrc/det_mm.hip): bf16, levels 0-2
         use_mm = (r.Cin != 1 and self.use_mm and need_gx and H >= 2 and W >= 2
                   and L.mm_bwd_supported(a.C, b.C if b is not None else 0, C, self.dt))
         coef = None
-        fold = use_mm and self.fold_fin
-        fold_pw = (not use_mm) and r.Cin != 1 and self.fold_fin  # ocrs_pw_bwd_fin: finalize + pointwise backward in one call
-        if not fold:  # (the matrix-core kernel derives the coefficients from gsum in its prologue: one launch less per block)
+        # BatchNorm-backward finalisation: derived from gsum in the prologue of the matrix-core kernel, inside ocrs_pw_bwd_fin on the generic
+        # path (which needs coef as scratch); its own launch only for the first block
+        if not use_mm:
             coef = self.empty(3, C, dtype=torch.float32)
-            if not fold_pw:
+            if r.Cin == 1:
                 L.bn_bwd_finalize(ptr(gsum), N * H * W, C, ptr(gam), ptr(r.saved), ptr(coef), ptr(dgam), ptr(dbet))
         wdw, wpw = P[f"{prefix}.seq.0.weight"], P[f"{prefix}.seq.1.weight"]
         if r.Cin == 1:
@@ -481,7 +468,7 @@ class _DetRun:
                                   ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]),
                                   ptr(ws), ptr(sva), ptr(gsa), C, N, H, W, self.dt)
                 return gxa, gxb
-            if (fold and a.u is not None and b is None and not pooled and L.mm_bwd_head_supported(Ca, 0, C, N, H, W, self.dt)):
+            if (a.u is not None and b is None and not pooled and L.mm_bwd_head_supported(Ca, 0, C, N, H, W, self.dt)):
                 # the block behind the first block: its input is rebuilt from the first block's u plane (2 instead of 16 bytes per pixel)
                 r1 = self.recs.get(a.src) if a.src is not None else None
                 if r1 is not None and getattr(r1, "fsum", None) is not None and C == 8 and sva is not None and self.capture is None:
@@ -496,15 +483,10 @@ class _DetRun:
                                 ptr(dgam), ptr(dbet), ptr(gxa), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws),
                                 ptr(sva), ptr(gsa), C, N, H, W, self.dt)
                 return gxa, gxb
-            if fold:
-                L.mm_bwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
-                             ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(gxb),
-                             ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb),
-                             C, N, H, W, self.dt)
-            else:
-                L.mm_bwd(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
-                         ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(gxa), ptr(gxb), ptr(self.G[f"{prefix}.seq.1.weight"]),
-                         ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb), C, N, H, W, self.dt)
+            L.mm_bwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
+                         ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(gxb),
+                         ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb),
+                         C, N, H, W, self.dt)
             return gxa, gxb
         if (self.use_rs32 and need_gx and L.rs32_bwd_supported(Ca, Cb, C, 1 if pooled else 0, self.dt) and N * H * W * max(r.Cin, C) * 4 < 2 ** 32
                 and (not pooled or (H >= 2 and W >= 2))):
@@ -533,14 +515,9 @@ class _DetRun:
         du = self.empty(N, H, W, r.Cin)
         ws = self.empty(L.pw_bwd_ws_floats(r.Cin, C, N, H, W), dtype=torch.float32)
         self._hold(ws)  # (its reduction may be queued until the end of the backward)
-        if fold_pw:
-            L.pw_bwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(g1),
-                         ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(wpk_d), ptr(du),
-                         ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(ws), C, N, H, W, self.dt)
-        else:
-            L.pw_bwd(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(g1),
-                     ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(wpk_d), ptr(du), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(ws), C, N, H, W,
-                     self.dt)
+        L.pw_bwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(g1),
+                     ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(wpk_d), ptr(du),
+                     ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(ws), C, N, H, W, self.dt)
         gxa = self.empty(N, H, W, Ca) if need_gx else None
         gxb = self.empty(N, H, W, Cb) if (need_gx and b is not None) else None
         ws = self.empty(L.dw_bwd_ws_floats(r.Cin, N, H, W), dtype=torch.float32)
@@ -577,12 +554,12 @@ class _DetRun:
             stage_end[stage] = off
         bucketer = getattr(self.mod, "_grad_bucketer", None)
         self._flat, self._folds = flat, []
-        self._defer_folds = bucketer is None and self.capture is None and os.environ.get("OCRS_DEFER_FOLDS", "1") != "0"
+        self._defer_folds = bucketer is None and self.capture is None
         # Deferred second stage (ocrs_bwd_defer_begin): the block kernels finalise the BatchNorm-backward sums they produce in their last workgroup and
         # the ~27 single-writer weight-gradient reductions of a backward run as ONE launch at its end.  Not with a gradient bucketer (a stage's
         # gradients must be complete when it is reported).  The workspaces must outlive the flush: self._keep_ws.
         self._keep_ws = []
-        if bucketer is None and self.capture is None and os.environ.get("OCRS_BWD_DEFER", "1") != "0":
+        if bucketer is None and self.capture is None:
             scratch = _bwd_scratch(self.dev)
             L.bwd_defer_begin(ptr(scratch), scratch.numel())
             self._deferring = True
@@ -624,7 +601,7 @@ class _DetRun:
         # out_conv's backward hands the last block either its 8-channel gradient g (16 B per pixel) or -- when that block's backward can form
         # g = round(gl * w[c]) itself (ocrs_mm_bwd_fin_head: the row-streaming kernel) -- only gl = dL/dlogit (4 B per pixel)
         r_up = self.recs.get(up.src) if up.src is not None else None
-        head_gl = (self.head_gl and self.capture is None and gs_head is not None and r_up is not None and r_up.b is None and self.use_mm and self.fold_fin
+        head_gl = (self.head_gl and self.capture is None and gs_head is not None and r_up is not None and r_up.b is None and self.use_mm
                    and L.mm_bwd_head_supported(r_up.a.C, 0, r_up.Cout, N, H, W, self.dt))
         if not head_gl and self.dt == 0:  # fp32 (round 6): the same hand-over on the row-streaming backward (ocrs_rs32_bwd_head; exactly _block_bwd's routing test)
             head_gl = bool(self.head_gl and self.capture is None and gs_head is not None and r_up is not None and r_up.b is None and self.use_rs32

@@ -733,8 +733,7 @@ def test_last_block_backward_from_head_gl_is_bit_identical(dev, shape):
     whead = torch.randn(8, generator=g).to(dev)
     pred = torch.rand(P_, generator=g).to(dev)
     gpred = torch.randn(P_, generator=g).to(dev)
-    if not L.mm_bwd_head_supported(8, 0, 8, N, H, W, 1):
-        pytest.skip("row-streaming backward switched off (OCRS_RS=0)")
+    assert L.mm_bwd_head_supported(8, 0, 8, N, H, W, 1)
     outs = []
     for head in (False, True):
         acc = torch.zeros(9, dtype=torch.float64, device=dev)

@@ -188,16 +188,16 @@ def test_awkward_shapes_two_train_steps_fp32_vs_bf16(B, H, W):
     assert abs(losses[0] - losses[1]) < 0.05 * abs(losses[0]) + 1e-3, losses
 
 
-def test_rank_one_ends_of_the_network_are_bit_identical_to_the_stored_paths(dev):
+def test_rank_one_ends_of_the_network_are_bit_identical_to_the_stored_paths(dev, monkeypatch):
     """Round 5: the two single-channel ends of the U-Net travel in compact form -- the first block's output as its u plane (2 B per pixel; in_conv.seq.1's
     backward rebuilds x = round(wexp[c] * u)), out_conv's input gradient as gl = dL/dlogit (4 B per pixel; the last block's backward forms round(gl * w[c]))
     -- and the first block's backward rebuilds z from its recomputed depthwise output.  With the switches off the 16-byte-per-pixel tensors are
     read instead: prediction, loss and EVERY parameter gradient of a bf16 train step must be identical bit for bit (sizes with whole and with cut
     strips / row blocks)."""
     import copy
-    import os
 
     import ocrs_models_amd as oa
+    from ocrs_models_amd.models import _DetRun
 
     for (B, H, W) in [(2, 128, 192), (1, 66, 64)]:
         m, _, _ = _det(48, dev, torch.bfloat16)
@@ -207,23 +207,18 @@ def test_rank_one_ends_of_the_network_are_bit_identical_to_the_stored_paths(dev)
         t = (torch.rand(B, 1, H, W, generator=g) > 0.9).float().to(dev)
         sd = copy.deepcopy(m.state_dict())
         outs = []
-        for c1u, noz, hgl, fuse in (("1", "1", "1", "0"), ("0", "0", "0", "0"), ("1", "0", "0", "0"), ("0", "0", "1", "0"), ("1", "1", "0", "0"), ("1", "1", "1", "1")):
-            # (OCRS_C1_NOZ: the first block does not store its 8-channel output at all -- in_conv.seq.1's forward reads the u plane too;
-            #  OCRS_C1_FUSE, the last variant: the first block's weight gradient from sums accumulated by in_conv.seq.1's backward -- see below)
-            os.environ["OCRS_C1_U"], os.environ["OCRS_C1_NOZ"], os.environ["OCRS_HEAD_GL"], os.environ["OCRS_C1_FUSE"] = c1u, noz, hgl, fuse
-            try:
-                m.load_state_dict(sd)
-                m.zero_grad()
-                pred = m(x)
-                loss = oa.balanced_cross_entropy_loss(pred, t)
-                loss.backward()
-                torch.cuda.synchronize()
-                outs.append((pred.detach().clone(), loss.item(), {k: p.grad.clone() for k, p in m.named_parameters()}))
-            finally:
-                os.environ.pop("OCRS_C1_U", None)
-                os.environ.pop("OCRS_C1_NOZ", None)
-                os.environ.pop("OCRS_HEAD_GL", None)
-                os.environ.pop("OCRS_C1_FUSE", None)
+        for c1u, noz, hgl, fuse in ((1, 1, 1, 0), (0, 0, 0, 0), (1, 0, 0, 0), (0, 0, 1, 0), (1, 1, 0, 0), (1, 1, 1, 1)):
+            # (c1_noz: the first block does not store its 8-channel output at all -- in_conv.seq.1's forward reads the u plane too;
+            #  c1_fuse, the last variant: the first block's weight gradient from sums accumulated by in_conv.seq.1's backward -- see below)
+            for k, v in (("c1_u", c1u), ("c1_noz", noz), ("head_gl", hgl), ("c1_fuse", fuse)):
+                monkeypatch.setitem(_DetRun._switches, k, bool(v))
+            m.load_state_dict(sd)
+            m.zero_grad()
+            pred = m(x)
+            loss = oa.balanced_cross_entropy_loss(pred, t)
+            loss.backward()
+            torch.cuda.synchronize()
+            outs.append((pred.detach().clone(), loss.item(), {k: p.grad.clone() for k, p in m.named_parameters()}))
         for o in outs[1:-1]:
             assert torch.equal(o[0], outs[0][0]) and o[1] == outs[0][1]
             for k in o[2]:
