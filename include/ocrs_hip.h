@@ -318,7 +318,9 @@ int ocrs_gru_layer_bwd(const float* dout, const float* saved, const float* out, 
    xws: ocrs_gru_seq_ws_floats(N) floats, the per-step exchange buffer (MFMA-fragment order; initialised by the call);
    err: ONE caller-owned 32-bit word, zeroed once by the caller and sticky -- set if a wait inside a launch timed out (outputs incomplete);
    exact != 0: fp32 MFMA (reference arithmetic), 0: split-bf16 x3 (fp32-class).  ocrs_gru_seq_supported: 1 when every workgroup of the launch
-   can be resident on the current device (otherwise use the per-step entry points above; OCRS_GRU_SEQ=0 forces that). */
+   can be resident on the current device with 64 workgroup slots to spare (otherwise use the per-step entry points above).
+   Test hook: with the environment variable OCRS_GRU_SEQ_FAST=0 (read at every launch) every group keeps the agent-scope exchange, also when
+   its workgroups share one XCD and would take the L2-local path -- the tests compare the two paths in one process. */
 long ocrs_gru_seq_supported(int N);
 long ocrs_gru_seq_sync_words(int N);
 long ocrs_gru_seq_ws_floats(int N);
@@ -343,14 +345,6 @@ int ocrs_ctc_fwd_ab(const float* lp, const int* targets, const long long* in_len
                     float* loss, int T, int N, int C, int Lpad, int Smax, hipStream_t st);
 int ocrs_ctc_grad_ab(const float* lp, const int* targets, const long long* in_len, const long long* tg_len, const float* alpha, const float* beta,
                      const float* nll, const float* gout, float* grad, int T, int N, int C, int Lpad, int Smax, hipStream_t st);
-/* torch.nn.CTCLoss() forward AND gradient in one launch (train_rec.py:104,121 + the backward of train_rec.py:140), lattice and log-probabilities
- * in LDS.  ocrs_ctc_fused_lds_bytes: LDS bytes a sample needs, 0 = shape not covered (use ocrs_ctc_fwd / ocrs_ctc_bwd).
- * grad_pre [T][N][C] (nullable: loss only) = dloss/dlog_probs for an upstream gradient of 1. */
-long ocrs_ctc_fused_lds_bytes(int T, int C, int Smax);
-int ocrs_ctc_fused(const float* lp, const int* targets, const long long* in_len, const long long* tg_len, float* nll, float* loss, float* grad_pre, int T,
-                   int N, int C, int Lpad, int Smax, hipStream_t st);
-/* out[i] = in[i] * g[0], g a device scalar: the upstream gradient of loss.backward() applied to grad_pre. */
-int ocrs_scale_by_dev(const float* in, const float* g, float* out, long n, hipStream_t st);
 /* The same with the alpha lattice kept for the backward in fp16 (BASELINE configs[4] "fp16 CTC alpha/beta"; SURVEY D5: a separately-toleranced
  * variant): alpha16 [N][T][Smax] fp16 = alpha - rowmax, rowmax [N][T] fp32 (row maximum per time step).  The recursion and the loss stay fp32
  * (identical loss bits); the gradient sees the fp16 rounding of the lattice (~1e-3 relative). */

@@ -60,9 +60,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
         # destination registers alone until the wait
         chk = os.path.join(os.path.dirname(HERE), "tools", "check_rs_loads.py" if asm_src == "det_rs.hip" else "check_opaque_loads.py")
         if not os.path.exists(chk):
-            hint = ", or run with OCRS_CONV_ROWS=0 to use the compiler-waited kernels" if asm_src == "rec_conv3.hip" else ""
             print(f"WARNING: {os.path.basename(chk)} not found -- {asm_src}'s hand-waited asm loads were NOT verified against this "
-                  f"compiler's register allocation (build from the repository tree{hint})", file=sys.stderr, flush=True)
+                  f"compiler's register allocation (build from the repository tree)", file=sys.stderr, flush=True)
         else:
             r = subprocess.run([sys.executable, chk], capture_output=True, text=True,
                                env={**os.environ, "OCRS_CHECK_HIPCC": hipcc, "OCRS_CHECK_FLAGS": " ".join(FLAGS), "OCRS_CHECK_SRC": asm_src})

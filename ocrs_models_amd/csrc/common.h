@@ -405,10 +405,6 @@ OcrsProf& ocrs_prof();
         }                                                                                                   \
     } while (0)
 
-static inline int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
 static inline int persistent_grid(long ntiles, int blocks_per_cu) {
     long cap = (long)kNumCU * blocks_per_cu;
     long g = ntiles < cap ? ntiles : cap;

@@ -1260,11 +1260,6 @@ __global__ __launch_bounds__(256) void k_gemm_x3(const float* __restrict__ X, in
         }
     };
     auto split_store = [&](const float4& v, bf16* hi, bf16* lo, int off) {
-#ifdef X3_FLOOR  // (measurement build: what the kernel would cost if its operands arrived pre-split -- one v_perm per pair instead of the split)
-        const unsigned b0 = __float_as_uint(v.x), b1 = __float_as_uint(v.y), b2 = __float_as_uint(v.z), b3 = __float_as_uint(v.w);
-        *reinterpret_cast<uint2*>(hi + off) = make_uint2(__builtin_amdgcn_perm(b1, b0, 0x07060302u), __builtin_amdgcn_perm(b3, b2, 0x07060302u));
-        *reinterpret_cast<uint2*>(lo + off) = make_uint2(__builtin_amdgcn_perm(b1, b0, 0x05040100u), __builtin_amdgcn_perm(b3, b2, 0x05040100u));
-#else
         const float x[4] = {v.x, v.y, v.z, v.w};
         float h[4], l[4];
 #pragma unroll
@@ -1274,7 +1269,6 @@ __global__ __launch_bounds__(256) void k_gemm_x3(const float* __restrict__ X, in
         }
         *reinterpret_cast<uint2*>(hi + off) = make_uint2(pack2bf(h[0], h[1]), pack2bf(h[2], h[3]));
         *reinterpret_cast<uint2*>(lo + off) = make_uint2(pack2bf(l[0], l[1]), pack2bf(l[2], l[3]));
-#endif
     };
     const int wm = wave & 1, wn = wave >> 1;  // 2 x 2 waves: 4 m-tiles x 4 pixel-tiles each
     const int i16 = lane & 15, kg = lane >> 4;
@@ -1483,16 +1477,11 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_gather_tr(const bf16* __restri
         }
 }
 
-// bf16 with a workspace: k_wgrad_gather_tr (OCRS_WGRAD_GATHER_TR=0: the transposed-tile kernel everywhere)
-static bool wgrad_gather_tr_on(int dtype) {
-    static const int on = env_int("OCRS_WGRAD_GATHER_TR", 1);
-    return on && dtype == 1;
-}
 static void wgrad_gather_tr_grid(int CA, int CB, int ntaps, long P, int& gx, int& gy, int& tiles_a, int& cpb) {
     tiles_a = (((CA + 7) & ~7) + 127) / 128;
     gy = tiles_a * ((ntaps * CB + 127) / 128);
     const long nchunks = (P + 31) / 32;
-    static const int target = env_int("OCRS_WGRAD_TR_BLOCKS", 1024);  // K splits: >= 8 chunks per block, ~4 blocks per CU in total
+    constexpr int target = 1024;  // K splits: >= 8 chunks per block, ~4 blocks per CU in total
     long g = target / gy;
     if (g > nchunks / 8) g = nchunks / 8;
     // every K split writes (and the reducer re-reads) a full ntaps * CB * CA8 partial: keep the workspace around 16 MB
@@ -1503,7 +1492,7 @@ static void wgrad_gather_tr_grid(int CA, int CB, int ntaps, long P, int& gx, int
     gx = (int)((nchunks + cpb - 1) / cpb);
 }
 static void wgrad_gather_grid(int CA, int CB, int ntaps, long P, int dtype, long& gx, int& gy) {
-    if (wgrad_gather_tr_on(dtype)) {
+    if (dtype == 1) {  // bf16: k_wgrad_gather_tr
         int g, ta, cpb;
         wgrad_gather_tr_grid(CA, CB, ntaps, P, g, gy, ta, cpb);
         gx = g;
@@ -1513,7 +1502,7 @@ static void wgrad_gather_grid(int CA, int CB, int ntaps, long P, int dtype, long
     const long ntiles = (P + TP - 1) / TP;
     const int CA8 = (CA + 7) & ~7;
     gy = ((CA8 + 127) / 128) * ((ntaps * CB + 127) / 128);
-    static const int target = env_int("OCRS_WGRAD_BLOCKS", 512);  // two 4-wave blocks per CU (round 4: one wave per SIMD cannot keep the MFMA pipe busy -- tools/probes/mfma_issue_probe.hip; 256 -> 512: 0.563 -> 0.496 ms per step, 768: 0.59)  // few flushing blocks, each loops over many tiles
+    constexpr int target = 512;  // two 4-wave blocks per CU (round 4: one wave per SIMD cannot keep the MFMA pipe busy -- tools/probes/mfma_issue_probe.hip; 256 -> 512: 0.563 -> 0.496 ms per step, 768: 0.59)  // few flushing blocks, each loops over many tiles
     gx = ntiles / 4;
     if (gx < 1) gx = 1;
     long cap = target / gy;
@@ -1550,7 +1539,7 @@ int ocrs_wgrad_gather(const void* A, int ldA, int CA, const float* trA, const vo
             return OCRS_ERR_HIP;
         attr_set.done();
     }
-    if (dtype == 1 && ws && wgrad_gather_tr_on(dtype)) {
+    if (dtype == 1 && ws) {
         int g, gy2, ta, cpb;
         wgrad_gather_tr_grid(CA, CB, KH * KW, P, g, gy2, ta, cpb);
         hipLaunchKernelGGL(k_wgrad_gather_tr, dim3(g, gy2), dim3(256), 0, st, (const bf16*)A, ldA, CA, trA, (const bf16*)B, ldB, CB, N, hA, wA, HB, WB, stride,
@@ -1606,11 +1595,6 @@ __global__ __launch_bounds__(256) void k_wgrad_gemm_x3(const float* __restrict__
         }
     };
     auto split_store = [&](const float4& v, bf16* hi, bf16* lo, int off) {
-#ifdef X3_FLOOR  // (measurement build: what the kernel would cost if its operands arrived pre-split -- one v_perm per pair instead of the split)
-        const unsigned b0 = __float_as_uint(v.x), b1 = __float_as_uint(v.y), b2 = __float_as_uint(v.z), b3 = __float_as_uint(v.w);
-        *reinterpret_cast<uint2*>(hi + off) = make_uint2(__builtin_amdgcn_perm(b1, b0, 0x07060302u), __builtin_amdgcn_perm(b3, b2, 0x07060302u));
-        *reinterpret_cast<uint2*>(lo + off) = make_uint2(__builtin_amdgcn_perm(b1, b0, 0x05040100u), __builtin_amdgcn_perm(b3, b2, 0x05040100u));
-#else
         const float x[4] = {v.x, v.y, v.z, v.w};
         float h[4], l[4];
 #pragma unroll
@@ -1620,7 +1604,6 @@ __global__ __launch_bounds__(256) void k_wgrad_gemm_x3(const float* __restrict__
         }
         *reinterpret_cast<uint2*>(hi + off) = make_uint2(pack2bf(h[0], h[1]), pack2bf(h[2], h[3]));
         *reinterpret_cast<uint2*>(lo + off) = make_uint2(pack2bf(l[0], l[1]), pack2bf(l[2], l[3]));
-#endif
     };
     const int wm = wave & 1, wn = wave >> 1;  // 2 x 2 waves, each 4 x 4 MFMA tiles of 16 x 16
     const int prow = 4 * (lane >> 4) + ((lane & 15) >> 2), pcol = (lane & 3) * 4;
@@ -1678,7 +1661,7 @@ static void wgrad_x3_grid(int CA, int CB, long P, int& gx, int& gy, int& tiles_a
     tiles_a = (CA + 127) / 128;
     gy = tiles_a * ((CB + 127) / 128);
     const long nchunks = (P + 31) / 32;
-    static const int target = env_int("OCRS_WGRAD_X3_BLOCKS", 512);  // (two resident 4-wave workgroups per CU; 384 / 768 / 1024 measured: no better)
+    constexpr int target = 512;  // (two resident 4-wave workgroups per CU; 384 / 768 / 1024 measured: no better)
     long g = target / gy;
     if (g < 1) g = 1;
     if (g > nchunks) g = nchunks;
@@ -1689,7 +1672,7 @@ static void wgrad_x3_grid(int CA, int CB, long P, int& gx, int& gy, int& tiles_a
 static int wgrad3x3_gx(int Cin, int N, int H, int W) {
     const int ntiles = N * ((W + 15) / 16) * ((H + 7) / 8);
     const int gy = Cin / 32;
-    static const int target = env_int("OCRS_WGRAD_BLOCKS", 512);  // two 4-wave blocks per CU (round 4: one wave per SIMD cannot keep the MFMA pipe busy -- tools/probes/mfma_issue_probe.hip; 256 -> 512: 0.563 -> 0.496 ms per step, 768: 0.59)
+    constexpr int target = 512;  // two 4-wave blocks per CU (see wgrad_gather_grid)
     long gx = ntiles / 4;
     if (gx < 1) gx = 1;
     long cap = target / gy;
@@ -1762,14 +1745,11 @@ int ocrs_conv3x3_wgrad(const void* dz, int Cout, const void* x, int Cin, float* 
     static DevOnce attr_set;
     if (attr_set.need()) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wgrad<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wgrad<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) !=
-                hipSuccess)
+            hipSuccess)
             return OCRS_ERR_HIP;
         attr_set.done();
     }
-    static const int use_tr = env_int("OCRS_WGRAD3X3_TR", 1);
-    if (dtype == 1 && use_tr) {
+    if (dtype == 1) {
         static bool attr2 = false;
         if (!attr2) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wgrad_tr<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
@@ -1785,10 +1765,7 @@ int ocrs_conv3x3_wgrad(const void* dz, int Cout, const void* x, int Cin, float* 
         else
             hipLaunchKernelGGL(k_conv3x3_wgrad_tr<64>, dim3((int)gx, gy), dim3(256), (128 * 72 + 180 * 40) * 2, st, (const bf16*)dz, Cout, (const bf16*)x,
                                Cin, dW, N, H, W, ws);
-    } else if (dtype == 1)
-        hipLaunchKernelGGL(k_conv3x3_wgrad<bf16>, dim3((int)gx, gy), dim3(256), (128 * 136 + 96 * 168) * 2, st, (const bf16*)dz, Cout, (const bf16*)x, Cin,
-                           dW, N, H, W, ws);
-    else
+    } else
         hipLaunchKernelGGL(k_conv3x3_wgrad<float>, dim3((int)gx, gy), dim3(256), (128 * 132 + 96 * 164) * 4, st, (const float*)dz, Cout,
                            (const float*)x, Cin, dW, N, H, W, ws);
     if (ws) hipLaunchKernelGGL(k_wgrad3x3_reduce, dim3((9 * Cin * Cout + 31) / 32), dim3(256), 0, st, ws, (int)gx, Cout, Cin, dW);
@@ -1832,10 +1809,7 @@ int ocrs_conv0_bwd(const float* img, const float* w, const float* bias, const vo
         hipLaunchKernelGGL(KERNEL<float>, dim3(GRID), dim3(256), SMEM, st, __VA_ARGS__);
 
 // BN+ReLU(+MaxPool PHxPW) forward on a pre-BN tensor z (models.py:197-199, 214-216, 231-233); tr = [3][C] load transform.
-static bool window_fast() {  // OCRS_REC_WINDOW_FAST=0: the generic (run-time window shape) kernels everywhere
-    static const int on = env_int("OCRS_REC_WINDOW_FAST", 1);
-    return on != 0;
-}
+// The window-templated kernels take the shapes they cover, the generic (run-time window shape) kernels the rest.
 int ocrs_act_pool_fwd(const void* z, const float* tr, void* out, int C, int N, int H, int W, int PH, int PW, int dtype, hipStream_t st) {
     OCRS_CHECK_ARG(z && tr && out && C % 8 == 0 && PH * PW <= 4 && PH >= 1 && PW >= 1);
     const int grid = ew_grid((long)N * (H / PH) * (W / PW) * (C / 8));
@@ -1845,7 +1819,7 @@ int ocrs_act_pool_fwd(const void* z, const float* tr, void* out, int C, int N, i
         OCRS_LAUNCH_CHECK();                                                                                                       \
         return OCRS_OK;                                                                                                            \
     }
-    if (window_fast() && 256 % (C / 8) == 0) {
+    if (256 % (C / 8) == 0) {
         if (dtype == 1) { APF(bf16, 2, 2) APF(bf16, 2, 1) } else { APF(float, 2, 2) APF(float, 2, 1) }
     }
 #undef APF
@@ -1861,7 +1835,7 @@ int ocrs_rec_bn_reduce(const void* g, const void* z, const float* bn, const floa
                        int dtype, hipStream_t st) {
     OCRS_CHECK_ARG(g && z && bn && saved && gsum && C % 8 == 0 && 256 % (C / 8) == 0 && PH * PW <= 4);
     int grid = ew_grid((long)N * (H / PH) * (W / PW) * (C / 8));
-    static const int bpc = env_int("OCRS_REC_REDUCE_BPC", 4);  // every block ends in 2 C same-address fp64 atomics (~11 ns each, serial per address)
+    constexpr int bpc = 4;  // every block ends in 2 C same-address fp64 atomics (~11 ns each, serial per address)
     if (grid > bpc * kNumCU) grid = bpc * kNumCU;
 #define RBR(T_, PH_, PW_)                                                                                                                      \
     if (PH == PH_ && PW == PW_) {                                                                                                              \
@@ -1869,7 +1843,7 @@ int ocrs_rec_bn_reduce(const void* g, const void* z, const float* bn, const floa
         OCRS_LAUNCH_CHECK();                                                                                                                   \
         return OCRS_OK;                                                                                                                        \
     }
-    if (window_fast() && H % PH == 0 && W % PW == 0) {
+    if (H % PH == 0 && W % PW == 0) {
         if (dtype == 1) { RBR(bf16, 2, 2) RBR(bf16, 2, 1) RBR(bf16, 1, 1) } else { RBR(float, 2, 2) RBR(float, 2, 1) RBR(float, 1, 1) }
     }
 #undef RBR
@@ -1887,12 +1861,11 @@ int ocrs_dz_apply(const void* g, const void* z, const float* bn, const float* co
                   float* dsum, hipStream_t st) {
     OCRS_CHECK_ARG(g && z && bn && coef && dz && C % 8 == 0 && PH * PW <= 4);
     int grid = ew_grid((long)N * ((H + PH - 1) / PH) * ((W + PW - 1) / PW) * (C / 8));
-    const bool fast = window_fast() && H % PH == 0 && W % PW == 0 && 256 % (C / 8) == 0;
-    static const int ds_bpc = env_int("OCRS_DZ_DSUM_BPC", 1);
+    const bool fast = H % PH == 0 && W % PW == 0 && 256 % (C / 8) == 0;
     float* dsum_ws = nullptr;
     if (dsum && fast) {  // 1024-thread blocks, every one ending in C same-address atomics
         grid = (grid + 3) / 4;
-        if (grid > ds_bpc * kNumCU) grid = ds_bpc * kNumCU;
+        if (grid > kNumCU) grid = kNumCU;  // one block per CU
         if ((PH == 2 && (PW == 2 || PW == 1)) || (PH == 1 && PW == 1)) dsum_ws = rec_defer_partials(grid, C, dsum);  // (the shapes DZA covers)
     }
 #define DZA(T_, PH_, PW_)                                                                                                                    \

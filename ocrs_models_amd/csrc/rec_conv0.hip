@@ -15,9 +15,6 @@
 // execute in order, so there is no workgroup barrier in the loop.  The next step's image rows and gradient vectors are register-prefetched.
 #include "det_common.h"
 
-#ifndef C0_ABL
-#define C0_ABL 0  // measurement builds: 1 no GEMM 2, 2 no a / patch writes and no GEMM 2, 3 no GEMM 1 MFMAs, 4 no prefetch loads in the loop
-#endif
 namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(256, 3) void k_conv0_bwd_mm(const float* __restrict
             for (int q = 0; q < 4; ++q) gq[q] = make_uint2(pv ? pg[q].x : 0u, pv ? pg[q].y : 0u);
         }
         wave_lds_fence();
-        if (C0_ABL != 4) issue(s + nw);
+        issue(s + nw);
         // ---- GEMM 1: the four pre-activation maps of the window, 16 channels of pixel n per lane
         f32x16 sacc[4];
         unsigned hv[4][5];  // the same operands as (hi | lo << 16) words
@@ -143,8 +140,7 @@ __global__ __launch_bounds__(256, 3) void k_conv0_bwd_mm(const float* __restrict
                     hw = kone ? 0x00003f80u : hw;
                 }
                 hv[o][i] = hw;
-                if (C0_ABL != 3) sacc[o] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[i], b, sacc[o], 0, 0, 0);
-                else sacc[o][i] += aw[i] * b;
+                sacc[o] = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[i], b, sacc[o], 0, 0, 0);
             }
         }
         // ---- two phases of two pooling positions each: a / patch rows of 64 (position, pixel) pairs -> GEMM 2 over K = 64.  (Half the LDS per wave: three
@@ -174,7 +170,6 @@ __global__ __launch_bounds__(256, 3) void k_conv0_bwd_mm(const float* __restrict
             for (int ol = 0; ol < 2; ++ol) {
                 const int o = 2 * ph + ol;
                 const unsigned x = (wsel[0][o] ? g0l : 0u) | (wsel[1][o] ? g0h : 0u), y = (wsel[2][o] ? g1l : 0u) | (wsel[3][o] ? g1h : 0u);
-                if (C0_ABL != 2 || x == 0x1234)
                 *reinterpret_cast<uint2*>(S2 + (ol * 32 + n) * 32 + (((q * 2 + half) ^ ((n >> 2) & 7)) << 2)) = make_uint2(x, y);
             }
         }
@@ -189,12 +184,12 @@ __global__ __launch_bounds__(256, 3) void k_conv0_bwd_mm(const float* __restrict
                 const int o = 2 * ph + ol;
                 const auto sw = __builtin_amdgcn_permlane32_swap(hv[o][i], hv[o][i], false, false);  // sw[0]: column 2 i, sw[1]: column 2 i + 1
                 const unsigned word = __builtin_amdgcn_perm(sw[1], sw[0], psel);
-                if (C0_ABL != 2 || word == 0x1234) reinterpret_cast<unsigned*>(half ? Bl : Bh)[(ol * 32 + n) * 8 + ((i + 2 * (n >> 3)) & 7)] = word;
+                reinterpret_cast<unsigned*>(half ? Bl : Bh)[(ol * 32 + n) * 8 + ((i + 2 * (n >> 3)) & 7)] = word;
             }
         wave_lds_fence();
         // ---- GEMM 2: dW[ch][k] += a^T patch, K = 64 (pixel, position) rows per phase
 #pragma unroll
-        for (int ks = 0; ks < ((C0_ABL == 1 || C0_ABL == 2) ? 0 : 2); ++ks) {
+        for (int ks = 0; ks < 2; ++ks) {
             const int r0 = ks * 32 + trow;
             // (rows r0 .. r0 + 3 and r0 + 4 .. r0 + 7: n = row & 31; both groups of four share (n >> 3), each shares its (n >> 2))
             const int nb0 = r0 & 31, nb1 = (r0 + 4) & 31;
@@ -234,17 +229,15 @@ __global__ __launch_bounds__(256, 3) void k_conv0_bwd_mm(const float* __restrict
 
 // launcher for ocrs_conv0_bwd (rec_conv.hip): 1 if this kernel took the call (bf16 gradient, even H and W)
 extern "C" int conv0_bwd_mm_launch(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype, hipStream_t st) {
-    static const int on = env_int("OCRS_CONV0_MM", 1);
-    if (!on || dtype != 1 || (H & 1) || (W & 1) || H < 2 || W < 2 || (long)N * (H / 2) * (((W / 2) + 31) / 32) >= (1L << 30)) return 0;
+    if (dtype != 1 || (H & 1) || (W & 1) || H < 2 || W < 2 || (long)N * (H / 2) * (((W / 2) + 31) / 32) >= (1L << 30)) return 0;
     static DevOnce attr;
     if (attr.need()) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv0_bwd_mm), hipFuncAttributeMaxDynamicSharedMemorySize, C0_SMEM);
         attr.done();
     }
     const long nsteps = (long)N * (H / 2) * (((W / 2) + 31) / 32);
-    static const int bpc = env_int("OCRS_CONV0_MM_BPC", 3);
     long grid = (nsteps + 3) / 4;
-    if (grid > (long)kNumCU * bpc) grid = (long)kNumCU * bpc;
+    if (grid > (long)kNumCU * 3) grid = (long)kNumCU * 3;  // three workgroups per CU (see the LDS note in the kernel)
     // deferring (ocrs_bwd_defer_begin): per-block partials + one queued fixed-order column sum instead of 320 float atomics per workgroup
     float* ws = bwd_defer_ws(grid * 320);
     if (ws && !bwd_defer_reduce(ws, (int)grid, 320, dW, 288, 288, 288, db, 32)) ws = nullptr;

@@ -14,14 +14,9 @@
 // Waves: 2 (M halves) x 2 (row halves).  Two blocks per CU (73 KB of LDS, <= 256 registers).
 #include "det_common.h"
 
-#ifndef OCRS_C128_UNROLL
-#define OCRS_C128_UNROLL 1   // tap loop unroll factor
-#endif
-#ifndef OCRS_C128_SPLIT
-#define OCRS_C128_SPLIT 4    // N tiles whose MFMAs are issued before the LDS commit of the prefetched data (8 = all; 4: 149 -> 145 us)
-#endif
-
 namespace {
+constexpr int C2_UNROLL = 1;  // tap loop unroll factor
+constexpr int C2_SPLIT = 4;   // N tiles whose MFMAs are issued before the LDS commit of the prefetched data (8 = all; 4: 149 -> 145 us)
 constexpr int C2_TW = 16, C2_ROWS = 16, C2_HW = C2_TW + 2;  // tile width, stacked rows, halo width
 constexpr int C2_PITCH = Mma<bf16>::LDS_PITCH;              // 40 bf16 = 80 B per staged pixel
 constexpr int C2_MAXHP = 2 * 10 * C2_HW;                    // staged pixels: NI * (TH + 2) * 18 -- 324 (1 x 16 rows) or 360 (2 x 8 rows)
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c128(const bf16* __restrict_
         for (int cc = 0; cc < ncc; ++cc) {
             const bool last_cc = cc + 1 == ncc;
             const bool pre_x = !last_cc || has_next;  // a chunk follows (next chunk of this tile, or chunk 0 of the next tile)
-#pragma unroll OCRS_C128_UNROLL
+#pragma unroll C2_UNROLL
             for (int tap = 0; tap < 9; ++tap, ++g) {
                 // ---- issue (registers): weights of step g + 2, group `tap` of the next chunk's input tile
                 nxt.w = g + 2 < S;
@@ -155,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c128(const bf16* __restrict_
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int b = 0; b < OCRS_C128_SPLIT; ++b)
+                for (int b = 0; b < C2_SPLIT; ++b)
 #pragma unroll
                     for (int a = 0; a < 4; ++a)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[a]), __builtin_bit_cast(bf16x8, bfr[b]), acc[a][b], 0, 0, 0);
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c128(const bf16* __restrict_
                 if (cur.xbuf_i >= 0) store_x(cur.xit, cur.xbuf_i, cur.xv);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int b = OCRS_C128_SPLIT; b < 8; ++b)
+                for (int b = C2_SPLIT; b < 8; ++b)
 #pragma unroll
                     for (int a = 0; a < 4; ++a)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[a]), __builtin_bit_cast(bf16x8, bfr[b]), acc[a][b], 0, 0, 0);
@@ -234,8 +229,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c128(const bf16* __restrict_
 
 // 1 if ocrs_conv_igemm's arguments describe a layer this kernel covers
 bool conv3x3_c128_supported(int ldx, int ldo, int Cin, int M, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw, int dtype) {
-    static const int on = env_int("OCRS_CONV_C128", 1);
-    return on && dtype == 1 && M == 128 && Cin % 32 == 0 && Cin >= 64 && KH == 3 && KW == 3 && padh == 1 && padw == 1 && Ho == Hi && Wo == Wi && Hi >= 8 &&
+    return dtype == 1 && M == 128 && Cin % 32 == 0 && Cin >= 64 && KH == 3 && KW == 3 && padh == 1 && padw == 1 && Ho == Hi && Wo == Wi && Hi >= 8 &&
            ldx % 8 == 0 && ldo % 4 == 0;
 }
 

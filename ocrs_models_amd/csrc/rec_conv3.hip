@@ -28,26 +28,6 @@
 // 2 x 2 kernels and padding 0 / 1 (the CRNN's last conv and its dgrad) run through the same code with 4 steps per chunk.
 #include "det_common.h"
 
-#ifndef R3_ABL
-#define R3_ABL 0  // ablation mask (measurement builds only): 1 no halo DMA, 2 no weight DMA, 4 no barrier / vmcnt wait, 8 no MFMA, 16 no B fragment reads
-#endif
-#ifndef R3_STAGGER
-#define R3_STAGGER 0  // 1: stagger (measured: 89 -> 146 us, the older wave of a SIMD then waits for the younger at every barrier); 0: both waves of a SIMD take the step barrier at tile 1
-#endif
-#ifndef R3_SETPRIO
-#define R3_SETPRIO 0  // s_setprio 1 around a step's MFMA / fragment-refill block
-#endif
-#ifndef R3_NT_OUT
-#define R3_NT_OUT 1  // non-temporal output stores: the kernel 3-4 % faster (77.9 -> 75.1, 145 -> 139 us), CRNN step 4.92 -> 4.88 ms in A/B runs (the
-                     // same in k_conv3x3_tile: no further change; in k_gemm_x3p, whose output the persistent GRU reads next: slower)
-#endif
-#ifndef R3_DBG
-#define R3_DBG 0  // 1: per-phase cycle counters of every wave of block 0 (measurement builds; read with ocrs_conv_rows_dbg)
-#endif
-#if R3_DBG
-__device__ long long g_r3dbg[8][8];
-#define R3_T() __builtin_readcyclecounter()
-#endif
 namespace {
 constexpr int R3_HPMAX = 1024;   // staged halo pixels per plane (<= 64 KB per 32-channel chunk, two chunks)
 __device__ uint4 g_zero64[4];    // 64 zero bytes: source of the padding lanes' DMA (four channel groups)
@@ -129,9 +109,6 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
     if (gstat) {
         for (int i = tid; i < WN * 2 * MTB * 16; i += 512) s_stat[i] = 0.f;
     }
-#if R3_DBG
-    long long t_start = R3_T(), t_bar = 0, t_epi = 0, t_pro = 0, t_x = 0;
-#endif
 
     // ---- per-lane constants.  B fragment of N tile j (tile index j * WN + wn, pixel p = tile * 16 + l15 of the pass): LDS byte offset of
     // the pixel's halo position (tap (0, 0)) in plane kq
@@ -203,9 +180,6 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
     load_af(afB, wbase + tapstride);  // step 1
 #pragma unroll
     for (int b = 0; b < NTW; ++b) bq[b] = lds16(baddr[b]);
-#if R3_DBG
-    t_pro = R3_T() - t_start;
-#endif
 
     // run-time step state, kept to a few scalar instructions per step (the first version's (tap, chunk, pass) state machine with its
     // divisions and 64-bit address arithmetic cost ~200 scalar + ~100 vector instructions per step -- as much issue time as the 28 MFMAs)
@@ -229,36 +203,21 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
     auto step = [&](auto first_tag, r3_u32x4 (&af)[MH], r3_u32x4 (&afp)[MH], bool peel) {
         constexpr bool FIRST = decltype(first_tag)::value;
         if (!peel) {
-#if R3_DBG
-            const long long tb0 = R3_T();
-#endif
             wait_a(af);
-#if R3_DBG
-            t_x += R3_T() - tb0;
-#endif
-            if (!(R3_ABL & 2)) load_af(afp, wp2);
+            load_af(afp, wp2);
         }
-        const bool with_x = !(R3_ABL & 1) && (unsigned)(tap - XT0) < (unsigned)XTN;
+        const bool with_x = (unsigned)(tap - XT0) < (unsigned)XTN;
         if (with_x) {
 #pragma unroll
             for (int q = 0; q < UPS; ++q) issue_x((tap - XT0) * UPS + q, xnc, rnc, (int)(xbuf ^ 1u));
         }
-        if (tap == NT - 1 && !(R3_ABL & 4)) {  // every wave's halo units of the next chunk have landed (issued at taps <= 5, waited for at the top of tap 7)
-#if R3_DBG
-            const long long tb1 = R3_T();
-#endif
+        if (tap == NT - 1) {  // every wave's halo units of the next chunk have landed (issued at taps <= 5, waited for at the top of tap 7)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (and this wave's reads of the buffer the chunk after next will be staged into)
             __builtin_amdgcn_s_barrier();
-#if R3_DBG
-            t_bar += R3_T() - tb1;
-#endif
         }
         // next step's tap offset: one pixel right, or to the start of the next row, or (after tap 8) tap 0 of the other input buffer
         unsigned ntapoff = tapoff + (kx == KW - 1 ? rowjump : 16u);
         if (tap == NT - 1) ntapoff = (xbuf ^ 1u) * 4u * PLANE;
-#if R3_SETPRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int b = 0; b < NTW; ++b) {
 #pragma unroll
@@ -266,12 +225,9 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
                 const f32x4 c = FIRST ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[a][b];
                 acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[a]), __builtin_bit_cast(bf16x8, bq[b]), c, 0, 0, 0);
             }
-            if (!(R3_ABL & 16)) bq[b] = lds16(baddr[b] + ntapoff);
+            bq[b] = lds16(baddr[b] + ntapoff);
             __builtin_amdgcn_sched_barrier(0);
         }
-#if R3_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         // ---- advance (scalar)
         tapoff = ntapoff;
         kx = kx == KW - 1 ? 0 : kx + 1;
@@ -308,9 +264,6 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
             step(std::false_type{}, afA, afB, false);
             step(std::false_type{}, afB, afA, false);
         }
-#if R3_DBG
-        const long long te0 = R3_T();
-#endif
         // ---- epilogue of the pass: bias, ReLU, per-channel sums of the stored values, store.  A lane holds 4 consecutive channels of one pixel
         // per accumulator tile; stored directly that is 8-byte pieces of four different instructions per 32 bytes -- and every CU of the chip
         // reaches its epilogue at the same time, so the layer's output is written in bursts at the HBM write rate that partial lines allow.
@@ -334,7 +287,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
             const int pj = (j * WN + wn) * 16;
-            if (pj >= lim || ((R3_ABL & 32) && acc[0][j][0] != 123.f)) continue;  // (wave-uniform)
+            if (pj >= lim) continue;  // (wave-uniform)
             const bool mine = pj + l15 < lim;
 #pragma unroll
             for (int a = 0; a < MH; ++a) {
@@ -357,12 +310,10 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
             for (int h = 0; h < MH / 2; ++h) {
                 const int ci = lane_e + 64 * h, px = ci / CPP, c16 = ci % CPP;
                 const uint4 q = *reinterpret_cast<const uint4*>(stg + px * (CPP * 16) + ((c16 ^ (px & (CPP - 1))) << 4));
-#if R3_NT_OUT
+                // non-temporal: the kernel 3-4 % faster (77.9 -> 75.1, 145 -> 139 us), CRNN step 4.92 -> 4.88 ms in A/B runs (the same in
+                // k_conv3x3_tile: no further change; in k_gemm_x3p, whose output the persistent GRU reads next: slower)
                 typedef unsigned u4v __attribute__((ext_vector_type(4)));
                 if (pj + px < lim) __builtin_nontemporal_store((u4v){q.x, q.y, q.z, q.w}, reinterpret_cast<u4v*>(obase + (long)(pj + px) * ldo * 2 + c16 * 16));
-#else
-                if (pj + px < lim) *reinterpret_cast<uint4*>(obase + (long)(pj + px) * ldo * 2 + c16 * 16) = q;
-#endif
             }
         }
         if (gstat) {
@@ -377,21 +328,9 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_rows(const bf16* __restrict_
                     }
                 }
         }
-#if R3_DBG
-        t_epi += R3_T() - te0;
-#endif
         xpc = xnx;
         r0c = rnx;
     }
-#if R3_DBG
-    if (blockIdx.x == 0 && lane == 0) {
-        g_r3dbg[wave][0] = R3_T() - t_start;
-        g_r3dbg[wave][1] = t_pro;
-        g_r3dbg[wave][2] = t_x;
-        g_r3dbg[wave][3] = t_bar;
-        g_r3dbg[wave][4] = t_epi;
-    }
-#endif
     wait_vm<0>();  // (the wrapped-around weight loads of the last steps: no LDS-DMA may be in flight when the workgroup's LDS is released)
     if (gstat) {
         __syncthreads();
@@ -466,13 +405,12 @@ int r3_launch(const R3Plan& pl, const void* x, int ldx, const void* wpk, void* o
 }  // namespace
 
 bool conv3x3_rows_supported(int ldx, int ldo, int Cin, int M, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw, int dtype) {
-    const int on = env_int("OCRS_CONV_ROWS", 1);  // 2: every shape the kernel can run (tests / measurements)
-    // measured (tools/experiments/r4_conv_time.py, B = 256): ahead of k_conv3x3_c128 / k_conv_igemm by 10-30 % where a row is not a whole number
+    // measured (round 4, B = 256): ahead of k_conv3x3_c128 / k_conv_igemm by 10-30 % where a row is not a whole number
     // of 16-pixel tiles (100, 37, ...) or short (<= 64); behind at 128 / 192 pixels per row (568 / 425 vs 729 / 696 TF/s) -- those stay there
-    if (on == 1 && KW == 3 && !(Wi % 16 != 0 || Wi <= 64)) return false;
+    if (KW == 3 && !(Wi % 16 != 0 || Wi <= 64)) return false;
     const bool k3 = KH == 3 && KW == 3 && padh == 1 && padw == 1 && Ho == Hi && Wo == Wi;
     const bool k2 = KH == 2 && KW == 2 && padh == padw && (padh == 0 || padh == 1) && Ho == Hi + 2 * padh - 1 && Wo == Wi + 2 * padw - 1 && M == 128;
-    return on && dtype == 1 && (M == 128 || M == 64) && Cin % 64 == 0 && (k3 || k2) && ldx % 8 == 0 && ldo % 8 == 0 && (long)Hi * Wi * ldx < (1L << 30) &&
+    return dtype == 1 && (M == 128 || M == 64) && Cin % 64 == 0 && (k3 || k2) && ldx % 8 == 0 && ldo % 8 == 0 && (long)Hi * Wi * ldx < (1L << 30) &&
            r3_plan(M, Ho, Wo, KW).var >= 0;
 }
 
@@ -492,7 +430,3 @@ int conv3x3_rows_launch(const void* x, int ldx, const void* wpk, void* out, int 
 #undef R3_GO
     return OCRS_ERR_ARG;
 }
-
-#if R3_DBG
-extern "C" int ocrs_conv_rows_dbg(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_r3dbg), sizeof(long long) * 64) == hipSuccess ? 0 : 2; }
-#endif

@@ -15,9 +15,6 @@
 // 8 waves = 8 pixel groups (WM = 1): a wave holds MH x NTW accumulator tiles (4 x 4 or 2 x 4).
 #include "det_common.h"
 
-#ifndef R4_ABL
-#define R4_ABL 0
-#endif
 namespace {
 __device__ uint4 g4_zero64[4];  // 64 zero bytes: source of the padding lanes' DMA
 
@@ -145,7 +142,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_tile(const bf16* __restrict_
 #pragma unroll
         for (int a = 0; a < MH; ++a) af[a] = lds16(wstep + (unsigned)a * 1024u);
         // halo units of the next chunk at taps 0..4 (the buffer they overwrite was last read before the previous tap-8 / end-of-pass barrier)
-        const bool with_x = !(R4_ABL & 1) && tap < 5 && (cc + 1 < ncc || has_nx);
+        const bool with_x = tap < 5 && (cc + 1 < ncc || has_nx);
         if (with_x) issue_x(tap, xnc, rnc, cnc, (int)(xbuf ^ 1u));
         constexpr bool last_step = false;  // (moving the pass's last barrier + refill behind the epilogue was measured: 135 -> 162 us)
         if (tap == 8) {  // every wave's halo units of the next chunk have landed; nobody reads the buffer the chunk after next is staged into
@@ -318,8 +315,7 @@ int r4_launch(const R4Plan& pl, const void* x, int ldx, const void* wpk, void* o
 }  // namespace
 
 bool conv3x3_tile_supported(int ldx, int ldo, int Cin, int M, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw, int dtype) {
-    const int on = env_int("OCRS_CONV_TILE", 1);
-    return on && dtype == 1 && (M == 64 || M == 32) && (Cin == 32 || Cin == 64) && Cin * M <= 64 * 32 && KH == 3 && KW == 3 && padh == 1 && padw == 1 && Ho == Hi &&
+    return dtype == 1 && (M == 64 || M == 32) && (Cin == 32 || Cin == 64) && Cin * M <= 64 * 32 && KH == 3 && KW == 3 && padh == 1 && padw == 1 && Ho == Hi &&
            Wo == Wi && ldx % 8 == 0 && ldo % 8 == 0 && (long)Hi * Wi * ldx < (1L << 30) && r4_plan(M, Cin, Hi, Wi).R > 0;
 }
 

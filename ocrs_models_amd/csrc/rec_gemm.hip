@@ -3,9 +3,8 @@
 // autocast), computed as  a b ~ ah bh + ah bl + al bh  exactly like k_gemm_x3 (rec_conv.hip): same products, same accumulation order, the
 // results are bit-identical.
 //
-// Why a second kernel: k_gemm_x3 is latency-bound, not matrix-, LDS- or VALU-bound.  Floor builds of round 4 (tools/experiments/
-// r4_gemm_time.py): weights pre-split and out of LDS -> no change; no split arithmetic -> -8 %; a third of the MFMAs AND no stores AND the
-// row operand L2-resident -> still 112 of 201 us (K = 512, M = 1536): a 128 x 128 x 32 chunk costs ~3500 cycles whatever is in it, because
+// Why a second kernel: k_gemm_x3 is latency-bound, not matrix-, LDS- or VALU-bound.  Floor builds of round 4: weights pre-split and out of
+// LDS -> no change; no split arithmetic -> -8 %; a third of the MFMAs AND no stores AND the row operand L2-resident -> still 112 of 201 us (K = 512, M = 1536): a 128 x 128 x 32 chunk costs ~3500 cycles whatever is in it, because
 // the chunk's loads are issued one chunk (0.3 us of matrix work) ahead and consumed behind a barrier, with two workgroups per CU to hide it.
 //
 // Here (third form; the first two are in DESIGN.md's round-4 section): one 768-thread workgroup per CU, persistent over (row block, column
@@ -34,16 +33,7 @@
 #include "det_common.h"
 #include <type_traits>
 
-#ifndef G_NPROD
-#define G_NPROD 4  // producer waves (all LDS-DMA of the workgroup): one wave issues a 1 KB DMA instruction every ~90 cycles, a chunk needs 24 - 48
-#endif
-#ifndef G_DBG
-#define G_DBG 0  // 1: per-phase cycle counters of every wave of workgroup 0 (measurement builds; read with ocrs_gemm_x3p_dbg)
-#endif
-#if G_DBG
-__device__ long long g_gdbg[8][8];
-#define G_T() __builtin_readcyclecounter()
-#endif
+constexpr int G_NPROD = 4;  // producer waves (all LDS-DMA of the workgroup): one wave issues a 1 KB DMA instruction every ~90 cycles, a chunk needs 24 - 48
 namespace {
 // LDS-DMA of 16 bytes per lane from (wave-uniform base + per-lane byte offset): lane i's bytes land at LDS byte lds_dst + 16 i
 __device__ __forceinline__ void g_dma16(const void* sbase, unsigned voff, unsigned lds_dst) {
@@ -127,21 +117,7 @@ __global__ __launch_bounds__(512 + 64 * G_NPROD) void k_gemm_x3p(const float* __
         } else {
             g_wait_vm<0>();
         }
-#if G_DBG
-        long long pb = 0, pi = 0, pwt = 0;
-#endif
         for (int g = 0; g < G; ++g) {
-#if G_DBG
-            const long long q0 = G_T();
-            g_barrier();
-            const long long q1 = G_T();
-            if (g + 2 < G) issue();
-            const long long q2 = G_T();
-            g_wait_vm<0>();
-            pb += q1 - q0; pi += q2 - q1; pwt += G_T() - q2;
-            if (g == G - 1 && blockIdx.x == 0 && lane == 0 && wave == 8) { g_gdbg[0][6] = pb; g_gdbg[1][6] = pi; g_gdbg[2][6] = pwt; }
-            continue;
-#endif
             g_barrier();  // chunk g has landed (waited for below / above); the consumers are done with chunk g - 1: its stage takes chunk g + 2
             if (g + 2 < G) {
                 issue();
@@ -165,19 +141,9 @@ __global__ __launch_bounds__(512 + 64 * G_NPROD) void k_gemm_x3p(const float* __
 #pragma unroll
         for (int j = 0; j < NTW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     int cst = 0;
-#if G_DBG
-    long long d_bar = 0, d_epi = 0;
-    const long long d_t0 = G_T();
-#endif
     for (int ti = 0; ti < ntile; ++ti) {
         for (int kc = 0; kc < nkc; ++kc) {
-#if G_DBG
-            const long long t0 = G_T();
-#endif
             g_barrier();
-#if G_DBG
-            d_bar += G_T() - t0;
-#endif
             const char* sb = smem + cst * STAGE;
             cst = cst == NS - 1 ? 0 : cst + 1;
             bf16x8 wh[4], wl[4];
@@ -208,9 +174,6 @@ __global__ __launch_bounds__(512 + 64 * G_NPROD) void k_gemm_x3p(const float* __
             }
         }
         // ---- tile done: + bias, 16 bytes per lane (4 consecutive output columns of one row); nothing here waits for the stores
-#if G_DBG
-        const long long e0 = G_T();
-#endif
         int rb, cb;
         tile_of(ti, rb, cb);
         const long p0 = (long)rb * BP + wn * NTW * 16 + n16;
@@ -227,20 +190,7 @@ __global__ __launch_bounds__(512 + 64 * G_NPROD) void k_gemm_x3p(const float* __
                 acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
-#if G_DBG
-        d_epi += G_T() - e0;
-#endif
     }
-#if G_DBG
-    if (blockIdx.x == 0 && lane == 0) {
-        g_gdbg[wave][0] = G_T() - d_t0;
-        g_gdbg[wave][1] = 0;
-        g_gdbg[wave][2] = d_bar;
-        g_gdbg[wave][3] = 0;
-        g_gdbg[wave][4] = d_epi;
-        g_gdbg[wave][5] = G;
-    }
-#endif
 }
 
 // true when ocrs_gemm_x3p can take the shape (the caller falls back to ocrs_gemm_x3 otherwise)
@@ -265,9 +215,8 @@ int ocrs_gemm_x3p_tiles(const float* X, int ldx, int K, const void* wpk, const f
     const int ncb = M / 128;
     // 256-row tiles unless that leaves CUs without a tile (M = 128: one column block)
     OCRS_CHECK_ARG(ntw_arg == 0 || ntw_arg == 2 || ntw_arg == 4);
-    static const int force = env_int("OCRS_GEMM_X3P_NTW", 0);
     const long t4 = ((P + 255) / 256) * ncb;
-    const int ntw = ntw_arg ? ntw_arg : (force == 2 || force == 4) ? force : (t4 >= 2 * kNumCU ? 4 : 2);
+    const int ntw = ntw_arg ? ntw_arg : (t4 >= 2 * kNumCU ? 4 : 2);
     if (ntw == 4) {
         const int nrb = (int)((P + 255) / 256);
         const size_t lds = 3 * (256 * 128 + 16384) + (size_t)M * 4;
@@ -290,10 +239,5 @@ int ocrs_gemm_x3p_tiles(const float* X, int ldx, int K, const void* wpk, const f
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-
-
-#if G_DBG
-int ocrs_gemm_x3p_dbg(long long* host64) { return hipMemcpyFromSymbol(host64, HIP_SYMBOL(g_gdbg), sizeof(long long) * 64) == hipSuccess ? 0 : 2; }
-#endif
 
 }  // extern "C"

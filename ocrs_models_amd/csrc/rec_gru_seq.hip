@@ -27,18 +27,6 @@
 #include "common.h"
 float* rec_defer_partials(int nb, int n, float* out);  // rec_conv.hip (deferred, fixed-order second stage: det_common.h)
 
-#ifndef OCRS_GRU_FAST_ACT
-#define OCRS_GRU_FAST_ACT 1  // throughput mode: hardware exp2 / rcp in the gate activations (0: libm, as the exact-fp32 mode always uses)
-#endif
-#ifndef OCRS_GRU_NT_OUT
-#define OCRS_GRU_NT_OUT 1  // forward recurrence: non-temporal stores for out / saved
-#endif
-#ifndef OCRS_GRU_WAIT_SLEEP
-#define OCRS_GRU_WAIT_SLEEP 1  // s_sleep between two polls of a group's arrival counter (x 64 clocks)
-#endif
-#ifndef OCRS_GRU_POLL_SLEEP
-#define OCRS_GRU_POLL_SLEEP 2  // ... between two polls of the tagged exchange words
-#endif
 namespace {
 constexpr int SH = 256, S3 = 768;  // hidden size, 3 gates
 constexpr int SNB = 32;            // batch columns per group
@@ -147,7 +135,7 @@ __device__ __forceinline__ bool seq_wait(unsigned* cnt, unsigned need, unsigned*
                 return false;
             }
         }
-        __builtin_amdgcn_s_sleep(OCRS_GRU_WAIT_SLEEP);
+        __builtin_amdgcn_s_sleep(1);  // (x 64 clocks between two polls of a group's arrival counter)
     }
 }
 }  // namespace
@@ -215,26 +203,18 @@ __device__ __forceinline__ bool xpoll(float* xws, int group, int par, int kc0, i
                 return false;
             }
         }
-        __builtin_amdgcn_s_sleep(OCRS_GRU_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(2);  // (between two polls of the tagged exchange words)
     }
 }
 // The forward's bulk outputs of a step (out, saved: 265 MB per launch) as NON-TEMPORAL stores: plain stores stream them through the L2 the
 // exchange workspace lives in -- 2.50 -> 2.00 us per step.  (Measured and not used: the same for the backward's dgi / dgh stores (4.14 -> 4.17-4.29),
 // non-temporal loads of gi (2.01 -> 2.55) and of the backward's operands (no change).)
 __device__ __forceinline__ void nt_store(float* p, float v) {
-#if OCRS_GRU_NT_OUT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void nt_store2(float* p, float a, float b) {
     typedef float f2v __attribute__((ext_vector_type(2)));
-#if OCRS_GRU_NT_OUT
     __builtin_nontemporal_store((f2v){a, b}, reinterpret_cast<f2v*>(p));
-#else
-    *reinterpret_cast<float2*>(p) = make_float2(a, b);
-#endif
 }
 __device__ __forceinline__ void st_xw(bool fast, float* p, unsigned a, unsigned b) { st_x(fast, p, __uint_as_float(a), __uint_as_float(b)); }
 // the same split without a tag (counter hand-offs: the backward kernel): hi = bf16(v), lo = bf16(v - hi), exactly what split8 computes --
@@ -341,14 +321,8 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
         store_prev(s);
         if (s + 1 < T) load_gi(d == 0 ? s + 1 : T - 2 - s, gn_r, gn_z, gn_n);
     };
-    constexpr bool FASTACT = !EXACT && OCRS_GRU_FAST_ACT != 0;
+    constexpr bool FASTACT = !EXACT;  // throughput mode: hardware exp2 / rcp in the gate activations (the exact-fp32 mode uses libm)
 
-#ifdef OCRS_GRU_SEQ_PROF
-    unsigned long long pt[6] = {0, 0, 0, 0, 0, 0}, pc = __builtin_readcyclecounter();
-#define PROF_MARK(i) { const unsigned long long now = __builtin_readcyclecounter(); pt[i] += now - pc; pc = now; }
-#else
-#define PROF_MARK(i)
-#endif
     for (int s = 0; s < T; ++s) {
         const int t = d == 0 ? s : T - 1 - s;
         float gh[3] = {0.f, 0.f, 0.f};
@@ -361,7 +335,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
             if constexpr (EXACT) {
                 if (tid == 0) s_ok = seq_wait(cnt, 16u * (unsigned)s, err) ? 1 : 0;
                 __syncthreads();
-                PROF_MARK(0)
                 if (!s_ok) return;  // (uniform)
                 float hb[2][8];
 #pragma unroll
@@ -375,7 +348,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
             } else {
                 unsigned w[2][8];
                 if (!xpoll<8, 2>(xws, group, (s - 1) & 1, 2 * kk, wnt, lane, (unsigned)((((s - 1) >> 1) & 1) ^ 1), err, w)) s_fail = 1;
-                PROF_MARK(0)
                 after_wait(s);
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -395,7 +367,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) red[rb][kk][g][wnt][kq * 4 + r][l15] = acc[g][r];
             __syncthreads();
-            PROF_MARK(2)
             if constexpr (!EXACT) {
                 if (s_fail) return;  // (uniform: written before the barrier)
             }
@@ -413,7 +384,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
         const float hv = bv ? (1.f - zv) * nv + zv * hp : 0.f;
         hp = hv;
         const float hv1 = __shfl_down(hv, 1);  // unit j + 1 of the same column (adjacent lane)
-        PROF_MARK(3)
         if (s + 1 < T) {
             if constexpr (EXACT) {
                 // publish h_t first (the only store the peers wait for): exchange store, drain, barrier, one lane signals
@@ -427,7 +397,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
                 if ((jl & 1) == 0) st_xw(fast, xslot<8>(xws, group, s & 1, xkc, xnt, xq, xlane), w0, w1);
             }
         }
-        PROF_MARK(4)
         p_rv = rv; p_zv = zv; p_nv = nv; p_hn = hn; p_hv = hv; p_hv1 = hv1;
         if constexpr (EXACT) {  // counter hand-off: its publish drains vmcnt(0) -- nothing may be pending in front of it, so no deferral
             store_prev(s + 1);
@@ -435,15 +404,8 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_fwd(const float* __restrict_
         } else {
             gi_r = gn_r; gi_z = gn_z; gi_n = gn_n;
         }
-        PROF_MARK(5)
     }
     if constexpr (!EXACT) after_wait(T);  // (the last step's out / saved)
-#ifdef OCRS_GRU_SEQ_PROF
-    if (tid == 0 && jt == 0) {
-        cnt[1] = fast ? 1u : 0u;
-        for (int i = 0; i < 6; ++i) cnt[2 + i] = (unsigned)(pt[i] / (unsigned long long)T);
-    }
-#endif
 }
 
 // BPTT.  dout [T][N][512], saved / out from the forward, whh [2][768][256] master; dgi, dgh [T][N][1536] (gradients w.r.t. gi and gh).
@@ -512,16 +474,12 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_bwd(const float* __restrict_
     };
     load_ep(d == 0 ? T - 1 : 0);
 
-#ifdef OCRS_GRU_SEQ_PROF
-    unsigned long long pt[6] = {0, 0, 0, 0, 0, 0}, pc = __builtin_readcyclecounter();
-#endif
     for (int s = 0; s < T; ++s) {
         const int t = d == 0 ? T - 1 - s : s;
         float dh = e_dout;
         if (s > 0) {
             if (tid == 0) s_ok = seq_wait(cnt, 16u * (unsigned)s, err) ? 1 : 0;
             __syncthreads();
-            PROF_MARK(0)
             if (!s_ok) return;
             f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -546,9 +504,7 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_bwd(const float* __restrict_
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) red[kk][wnt][kq * 4 + r][l15] = acc[r];
-            PROF_MARK(1)
             __syncthreads();
-            PROF_MARK(2)
             const float* rp = &red[0][bl >> 4][jl][bl & 15];
             constexpr int WS = 2 * 16 * 17;
             dh += carry + ((rp[0] + rp[WS]) + (rp[2 * WS] + rp[3 * WS]));
@@ -564,7 +520,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_bwd(const float* __restrict_
         sb_nr += dnr;
         carry = dh * e_z;
         const float dr1 = __shfl_down(dr, 1), dz1 = __shfl_down(dz, 1), dnr1 = __shfl_down(dnr, 1);
-        PROF_MARK(3)
         if (s + 1 < T) {
             if constexpr (EXACT) {
                 if ((jl & 1) == 0) {
@@ -585,7 +540,6 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_bwd(const float* __restrict_
             __syncthreads();
             if (tid == 0) seq_signal(fast, cnt);
         }
-        PROF_MARK(4)
         if (bv) {
             float* gi_ = dgi + ((long)t * N + b) * (2 * S3) + d * S3 + j;
             gi_[0] = dr;
@@ -599,14 +553,7 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_bwd(const float* __restrict_
             }
         }
         if (s + 1 < T) load_ep(d == 0 ? T - 2 - s : s + 1);
-        PROF_MARK(5)
     }
-#ifdef OCRS_GRU_SEQ_PROF
-    if (tid == 0 && jt == 0) {
-        cnt[1] = fast ? 1u : 0u;
-        for (int i = 0; i < 6; ++i) cnt[2 + i] = (unsigned)(pt[i] / (unsigned long long)T);
-    }
-#endif
     // bias gradients (nullable): db_ih = column sums of dgi, db_hh = column sums of dgh over (t, n) -- the two 159-MB re-reads of dgi / dgh by
     // k_col_sum4 (0.17 ms per CRNN step) are not needed.  Lanes -> the wave's four batch columns (lanes 16 apart), waves through LDS in a fixed
     // order, then one fp32 atomic per (group, unit, gate) -- 8 groups per direction at N = 256 (like k_col_sum4's per-block atomics).
@@ -644,7 +591,11 @@ __global__ __launch_bounds__(512, 2) void k_gru_seq_bwd(const float* __restrict_
 
 static int seq_groups(int N) { return 2 * ((N + SNB - 1) / SNB); }
 static int seq_grid(int N) { return 8 * ((seq_groups(N) + 7) / 8) * 16; }  // padded to whole rounds of the 8 XCDs
-static int seq_try_fast() { return env_int("OCRS_GRU_SEQ_FAST", 1); }  // (read per call: the tests compare both paths in one process)
+// OCRS_GRU_SEQ_FAST=0 keeps every group on the agent-scope exchange (a test hook: read per call, so that one process can compare both paths)
+static int seq_try_fast() {
+    const char* v = getenv("OCRS_GRU_SEQ_FAST");
+    return v ? atoi(v) : 1;
+}
 
 template <class K>
 static bool seq_fits(K kernel, int nblocks) {
@@ -659,8 +610,7 @@ extern "C" {
 
 // 1 if the persistent recurrence can run for N batch columns on the current device (all 32 * ceil(N / 32) workgroups co-resident)
 long ocrs_gru_seq_supported(int N) {
-    static const int on = env_int("OCRS_GRU_SEQ", 1);
-    if (!on || N <= 0) return 0;
+    if (N <= 0) return 0;
     static int cap = -1;  // resident workgroups the device holds of the most demanding of the four kernels
     if (cap < 0) {
         cap = 0;
@@ -672,9 +622,8 @@ long ocrs_gru_seq_supported(int N) {
     // Head-room: the launch only deadlocks-until-timeout if some workgroup cannot become resident while its peers spin.  Other streams'
     // kernels may hold workgroup slots at that moment -- the DDP bucketer's RCCL all-reduce (<= 32 channels = workgroups by default, 64 with
     // NCCL_MAX_NCHANNELS raised) starts right before the backward recurrence -- so the grid must fit with that many slots to spare
-    // (OCRS_GRU_SEQ_HEADROOM, default 64).  N = 256 needs 256 of the 512 slots an MI355X offers these kernels.
-    static const int headroom = env_int("OCRS_GRU_SEQ_HEADROOM", 64);
-    return seq_grid(N) + headroom <= cap;
+    // (64).  N = 256 needs 256 of the 512 slots an MI355X offers these kernels.
+    return seq_grid(N) + 64 <= cap;
 }
 long ocrs_gru_seq_sync_words(int N) { return (long)seq_groups(N) * SYNC_STRIDE; }
 // floats of the exchange workspace of one launch (the backward needs 3x the forward: size for the backward, both passes take it)

@@ -6,7 +6,6 @@
 from __future__ import annotations
 
 import contextlib
-import os
 
 import torch
 
@@ -123,7 +122,7 @@ def balanced_cross_entropy_loss(pred: torch.Tensor, target: torch.Tensor) -> tor
 MAX_CTC_STATES = 4096  # csrc/rec_seq.hip: up to 16 states per thread x 256 threads (labels of up to 2047 symbols)
 
 
-_CTC_AB = os.environ.get("OCRS_CTC_AB", "1") != "0"  # alpha and beta recursions in one launch + a parallel gradient kernel (round 4)
+_CTC_AB = True  # alpha and beta recursions in one launch + a parallel gradient kernel (round 4); the tests turn it off to compare the forms
 
 
 class _CTC(torch.autograd.Function):
@@ -138,16 +137,7 @@ class _CTC(torch.autograd.Function):
         dev = lp.device
         nll = torch.empty(N, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        ctx.fused = False
         ctx.ab = False
-        if not h16 and L.ctc_fused_lds_bytes(T, C, Smax) > 0:
-            # fused wave-level form (csrc/rec_seq.hip k_ctc_fused_w): loss AND the gradient for an upstream gradient of 1 in one launch
-            need_grad = ctx.needs_input_grad[0]  # (False under an outer no_grad(): requires_grad alone would compute the gradient needlessly)
-            gpre = torch.empty_like(lp) if need_grad else None
-            L.ctc_fused(ptr(lp), ptr(tg), ptr(in_len), ptr(tg_len), ptr(nll), ptr(loss), ptr(gpre), T, N, C, Lpad, Smax)
-            ctx.fused = True
-            ctx.save_for_backward(gpre)
-            return loss
         if h16:
             alpha = torch.empty(N, T, Smax, dtype=torch.float16, device=dev)
             rowmax = torch.empty(N, T, dtype=torch.float32, device=dev)
@@ -169,12 +159,6 @@ class _CTC(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        if ctx.fused:
-            (gpre,) = ctx.saved_tensors
-            g = gout.contiguous().float().reshape(1)
-            out = torch.empty_like(gpre)  # (a fresh tensor: a second backward over a retained graph must see the unscaled saved gradient -- ADVICE r04)
-            lib().scale_by_dev(ptr(gpre), ptr(g), ptr(out), gpre.numel())
-            return out, None, None, None, None, None
         lp, tg, in_len, tg_len, alpha, nll, rowmax = ctx.saved_tensors
         T, N, C = lp.shape
         grad = torch.empty_like(lp)

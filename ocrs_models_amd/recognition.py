@@ -43,12 +43,12 @@ class _RecRun:
         self.dev = x.device
         self.dtype = dtype
         self.dt = _DT[self.dtype]
-        self.x3 = os.environ.get("OCRS_GRU_X3", "1") != "0"  # split-bf16 GEMMs for the fp32 GRU weight gradients in throughput mode
-        self.x3p = self.x3 and os.environ.get("OCRS_GEMM_X3P", "1") != "0"  # ... the projections on the pipelined kernel (rec_gemm.hip, round 4)
+        # split-bf16 GEMMs for the fp32 GRU weight gradients in throughput mode, the projections on the pipelined kernel (rec_gemm.hip)
+        self.x3 = os.environ.get("OCRS_GRU_X3", "1") != "0"
         # recurrence as one persistent launch per layer and pass (csrc/rec_gru_seq.hip) when all its workgroups can be resident; its matrix
         # products follow the projection GEMMs' arithmetic: exact fp32 MFMA in parity mode, split-bf16 x3 in throughput mode
         self.gru_seq = bool(self.L.gru_seq_supported(x.shape[0])) and not _GRU_SEQ_OFF.get(x.device, False)
-        self.gru_exact = 0 if (self.dt == 1 and self.x3 and os.environ.get("OCRS_GRU_REC_X3", "1") != "0") else 1
+        self.gru_exact = 0 if self.dt == 1 and self.x3 else 1
         self.x = x
         self.N, _, self.H, self.W = x.shape
         self.ncls = self.P["output.0.weight"].shape[0]
@@ -99,7 +99,7 @@ class _RecRun:
         stays in place (same scheme as models.py::_Run.prepack)."""
         P = self.P
         cache = getattr(self.mod, "_pack_cache", None)
-        key = (self.dt, self.train, self.x3p, tuple(p.data_ptr() for p in P.values()))
+        key = (self.dt, self.train, self.x3, tuple(p.data_ptr() for p in P.values()))
         if cache is None or cache[0] != key:
             rows = []  # (src tensor, dtype code, K, M, K2, s1, s2, sm, element offset)
             for name in self._CONVS:
@@ -113,7 +113,7 @@ class _RecRun:
                 rows.append((P["output.0.weight"], 0, 512, C, 512, 0, 1, 512, 0))
                 if self.train:
                     rows.append((P["output.0.weight"], 0, C, 512, C, 0, 512, 1, 0))
-            elif self.x3p:
+            else:
                 # throughput mode, pipelined split-bf16 GEMM (csrc/rec_gemm.hip): the GRU input-projection weights pre-split into hi / lo bf16
                 # fragment planes (pack mode 2), forward A[m][k] = W_ih[m][k] and -- training -- input-gradient A[m][k] = W_ih[k][m] layouts;
                 # the output layer's input gradient likewise (its forward has a ragged M = n_classes and stays on k_gemm_x3)
@@ -170,7 +170,7 @@ class _RecRun:
     def gemm_x3(self, x, ldx, K, w, ldw, km, bias, M, ldo, rows, kw=0):
         """Throughput-mode fp32 GEMM as split-bf16 (see csrc/rec_conv.hip::k_gemm_x3): W straight from the master layout."""
         out = self.empty(rows, ldo, dtype=torch.float32)
-        if self.x3p and M % 128 == 0:
+        if M % 128 == 0:
             # pre-split weights of this step's prepack (mode 2): A[m][k] = W[m][k] (km = 0: s2 = 1, sm = ldw) or W[k][m] (km = 1: s2 = ldw, sm = 1)
             Kw = kw or K
             wpk = self.packs.get((w.data_ptr(), 1, Kw, M, 0, ldw if km else 1, 1 if km else ldw, 2))
@@ -364,7 +364,7 @@ class _RecRun:
         # the first layer's weight gradient, the GRU bias sums) write per-block partials into the library's workspace and queue a fixed-order column
         # sum; ONE launch at the end of the backward runs them all -- the step's gradients are bit-reproducible.  Not with a gradient bucketer (a
         # stage's gradients must be complete when it is reported).
-        deferring = bucketer is None and os.environ.get("OCRS_BWD_DEFER", "1") != "0"
+        deferring = bucketer is None
         if deferring:
             L.bwd_defer_begin(None, 0)
 
@@ -417,12 +417,12 @@ class _RecRun:
                 for d in (0, 1):
                     self.wgrad(dgh.data_ptr() + 4 * d * 768, 1536, 768, gl["out"].data_ptr() + 4 * d * 256, 512, 256, G["gru.weight_hh" + sfx[d]], 1,
                                T, N, T, N, 1 if d == 0 else -1, 0, 1, 1, 0)
-            if self._side is not None and _REC_OVERLAP_GRU and layer == 1 and _REC_OVERLAP_GRU1 and bucketer is None:
+            if self._side is not None and layer == 1 and bucketer is None:
                 # layer 1's weight gradients must not run under layer 0's persistent recurrence (its hand-offs suffer from streaming neighbours:
                 # measured slower in round 2): they are queued on the side stream BEHIND that recurrence, together with layer 0's
                 deferred_l1 = gru_wgrads
                 self._keep.extend((dgi, dgh, gl["x"], gl["out"]))
-            elif layer == 0 and self._side is not None and _REC_OVERLAP_GRU:
+            elif layer == 0 and self._side is not None:
                 # layer 0's weight gradients next to the conv backward that follows
                 self._side.wait_stream(main)
                 with torch.cuda.stream(self._side):
@@ -549,9 +549,9 @@ class _RecFn(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
-_REC_OVERLAP = os.environ.get("OCRS_REC_OVERLAP", "1") != "0"  # conv weight gradients of the backward on a side stream
-_REC_OVERLAP_GRU = os.environ.get("OCRS_REC_OVERLAP_GRU", "1") != "0"  # ... and the GRU layer-0 weight gradients
-_REC_OVERLAP_GRU1 = os.environ.get("OCRS_REC_OVERLAP_GRU1", "1") != "0"  # ... and layer 1's, queued behind layer 0's recurrence (single-GPU runs)
+# the conv and GRU weight gradients of the backward on a side stream (False: everything on the caller's stream -- bench.py's per-launch
+# roofline, tools/prof_crnn.py)
+_REC_OVERLAP = True
 _REC_SIDE = {}
 
 

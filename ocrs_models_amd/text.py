@@ -10,8 +10,6 @@ from __future__ import annotations
 
 import string
 
-import os
-
 import torch
 
 from ._lib import lib, ptr
@@ -66,7 +64,7 @@ class _Decode:
         return [row[:n] for row, n in zip(labels_h, lens_h)]
 
 
-_DECODE_SIDE = os.environ.get("OCRS_DECODE_SIDE", "1") != "0"
+_DECODE_SIDE = True  # greedy decode on a side stream (tools/prof_crnn.py turns it off for single-stream traces)
 _DECODE_STREAMS = {}
 
 
