@@ -367,6 +367,33 @@ int ocrs_collate_pad(const void* packed, const long long* offs, const int* width
 int ocrs_resize_aa(const float* in, float* ws, float* out, int planes, int h, int w, int oh, int ow, hipStream_t st);
 long ocrs_resize_aa_ws_floats(int planes, int h, int ow);
 
+/* ------------------------------------------------------------------ training augmentations ---- */
+/* The reference's torchvision augmentations (csrc/augment.hip), restated from torchvision's tensor code path for the fixed arguments the
+ * training scripts use; parameters are drawn on the host by ocrs_models_amd/augment.py.  params: [B][24] 32-bit words per sample, 16-byte
+ * aligned: int kind (0 identity, 1 ColorJitter, 2 nearest affine, 3 perspective, 4 shift (crop / pad), 5 bilinear affine (rotation)),
+ * int flags (bit 0: brightness before contrast), int h, w (source), ih, iw (intermediate, after the augmentation), dy, dx (shift: source
+ * row / column of intermediate pixel 0), ow (lines: resized width), 7 unused ints, then 8 fp32: jitter {b, c, (float)(1 - c)}; affine
+ * {theta row 0 / (w/2), theta row 1 / (h/2), base-grid x and y offsets}; perspective {coeffs 0-2 / (w/2), 3-5 / (h/2), coeffs 6, 7}.
+ * The records must describe the packed sources: no kernel reads outside [offs, offs + h * w) of a sample.  Per image h, w <= 65535 and
+ * h * w < 2^31 (checked through max_h / max_w).  Contrast means are reduced in a fixed order without atomics: bit-reproducible. */
+/* prepare_transform(mask_size, augment) (ocrs_models/train_detection.py:266-290) + default collate: RandomApply(RandomChoice([ColorJitter,
+ * RandomAffine, RandomPerspective, RandomCrop(600, pad_if_needed)]), p=0.5) then Resize(mask_size, antialias=False), on the stack
+ * [image, mask].  Sample b = uint8 image img_u8 + offs[b] and mask + offs[b] (mask_kind 0: uint8 0/1, 1: fp32), (h, w) row-major;
+ * transform_image fused into the load.  img_out (B,1,OH,OW) fp32 / bf16 (dtype 0 / 1), mask_out (B,1,OH,OW) fp32; all 16-byte aligned.
+ * ws: ocrs_augment_det_ws_floats(B) floats.  Three launches whatever B. */
+long ocrs_augment_det_ws_floats(int B);
+int ocrs_augment_det(const void* img_u8, const void* mask, const long long* offs, const int* params, float* ws, void* img_out, float* mask_out,
+                     int B, int max_h, int max_w, int OH, int OW, int mask_kind, int dtype, hipStream_t st);
+/* The recognition sample path (ocrs_models/datasets/hiertext.py:271-294 with text_recognition_data_augmentations(),
+ * datasets/__init__.py:4-30) + collate_samples' image part (train_rec.py:285-299): background masking by the optional uint8 0/1 line masks,
+ * RandomApply(RandomChoice([ColorJitter, RandomRotation(5, expand, bilinear, fill -0.5), Pad(5, fill -0.5)]), p=0.5), clamp(-0.5, 0.5)
+ * (clamp != 0), antialiased resize to (OH, ow) and right-padding with 0.0 into out (B,1,OH,Wpad) fp32 / bf16.  offs [B][3] = {source element
+ * offset of crop and mask, intermediate offset, horizontal-pass offset}; crops kind 0 uint8 (transform fused), 1 fp32.  ws:
+ * ocrs_augment_lines_ws_floats(B, inter_floats = sum ih * iw, sum ih * ow) floats.  Five launches whatever B. */
+long ocrs_augment_lines_ws_floats(int B, long inter_floats, long hpass_floats);
+int ocrs_augment_lines(const void* crops, const void* masks, const long long* offs, const int* params, float* ws, long inter_floats, void* out, int B,
+                       int max_ih, int max_iw, int OH, int Wpad, int kind, int clamp, int dtype, hipStream_t st);
+
 /* ------------------------------------------------------------------ validation metrics ------- */
 /* Word-level metrics of the detection test() loop (ocrs_models/train_detection.py:177-184) on the device, restating the host contract
  * ocrs_models_amd/postprocess.py (reference postprocess.py:11-36 extract_cc_quads, :102-187 box_match_metrics); csrc/postprocess.hip.

@@ -95,3 +95,6 @@ def collate_samples(samples: list[dict], device, dtype: torch.dtype = torch.floa
         widths_d = iw.to(torch.int32).to(device, non_blocking=True)
         lib().collate_pad(ptr(packed_d), ptr(offs_d), ptr(widths_d), ptr(image), n, h, wmax, 0 if torch.uint8 in kinds else 1, _DT[dtype])
     return {"image": image, "text_seq": text, "text_len": tl, "image_width": iw}
+
+
+from .augment import AugParams, collate_lines, detection_batch, sample_detection_params, sample_line_params  # noqa: E402,F401
