@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Train-step throughput of the detection hot path on MI355X (BASELINE.json configs[1]):
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 without a launcher: spawns the N ranks itself, self_launch())
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without a launcher: spawns the N ranks itself, self_launch())
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 step = forward + balanced BCE + zero_grad + backward (+ RCCL gradient all-reduce, overlapped) + Adam on a batch of
 synthetic greyscale tiles, B=32 x 1x1024x1024 per GPU (weak scaling), bf16 activations / fp32 accumulate+params,
 random-init weights (seed 1234 as train_detection.py:337).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps (writes --dump-outputs) and prints the line: the contract fields, `roofline` (from the timed
+steps themselves; `traffic` from the committed PMC profile) and `ddp` under a launcher.  Every leg that takes runs of its own -- the live PMC
+passes, fp32_exact, reference_style_step, config1_hip, the 1-rank RCCL probe, crnn, cpu_baseline -- runs only with --full (each still
+switched off by its --no-* option there).
 
 Objects in the line besides the contract fields (all byte / flop models are SURVEY.md 8(d)'s, restated in DESIGN.md 5):
   roofline     -- the dominant PASS of the step (the DepthwiseConv-block backward: every launch belonging to one block's backward),
@@ -14,7 +19,7 @@ Objects in the line besides the contract fields (all byte / flop models are SURV
                   with 8(d)'s byte model: a block backward reads saved input, saved output and grad-out once and writes grad-in once
                   = 2 (Cin + Cout) elements per pixel.  Also: whole_step_frac (3 * sizeof * sum(in+out) of the whole net / step time /
                   8 TB/s), traffic + traffic_ratio (HBM bytes from the committed PMC passes / algorithmic bytes), and `passes`
-                  (forward-block and ConvTranspose passes, event-timed in the last warm-up step).
+                  (forward-block and ConvTranspose passes, event-timed in the last warm-up step).  --full: traffic from two live PMC passes.
   fp32_exact   -- the same step in the fp32 parity mode (a few steps).
   crnn         -- line-crops/s of the CRNN recognition train step (configs[2], at the legal crop height 64) with its own roofline
                   (conv MFMA TF/s vs the 2.5 PF dense bf16 peak; GRU us per time step vs the 1.45 us kernel-boundary floor) and the
@@ -194,7 +199,7 @@ def pmc_live(args):
         return None, "rocprofv3 not on this box"
     nsteps = 2
     child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--batch", str(args.batch), "--size", str(args.size), "--dtype", args.dtype,
-             "--no-crnn", "--no-cpu-baseline", "--no-roofline", "--no-fp32", "--no-ref-style", "--no-ddp-probe", "--no-config1", "--no-pmc"]
+             "--no-roofline"]  # (a plain run: detection only)
     acc = {}
     try:
         with tempfile.TemporaryDirectory(dir="/tmp") as d:
@@ -286,7 +291,7 @@ def _median_steps(fn, warm, timed):
 def cpu_baseline():
     """oracle/ train steps (stock ATen CPU operators, what the reference dispatches to) on the host cores, SURVEY 8(d) protocol: same
     synthetic distributions and seeds as the GPU run, reduced batches, median of >= 5 timed steps after 2 warm-ups (the 1024^2 detection
-    case: 3 after 1 -- one step is ~8 s and the default bench must stay within minutes)."""
+    case: 3 after 1 -- one step is ~8 s and the --full bench must stay within minutes)."""
     import numpy as np
 
     from oracle import aten_step as A
@@ -634,6 +639,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="tiles per GPU")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true", help="also run every leg besides the timed detection steps (live PMC passes, fp32 parity "
+                    "mode, reference-style step, config-1 step, 1-rank RCCL probe, CRNN, CPU baseline); off: the headline figure only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-crnn", action="store_true")
@@ -818,7 +825,7 @@ def main():
             return {"ms_per_step": round(ms_tot / nsteps, 3), "alg_GB_per_step": round(b_tot / nsteps / 1e9, 3), "achieved_GBps": round(ach, 1),
                     "frac": round(ach / HBM_PEAK_GBS, 4), "launches_per_step": nlaunch // nsteps, "units_per_step": nblocks // nsteps}
 
-        rows, src = (None, "--no-pmc") if args.no_pmc else pmc_live(args)
+        rows, src = pmc_live(args) if args.full and not args.no_pmc else (None, "--no-pmc" if args.no_pmc else "they run with --full")
         live_note = src
         if rows is None:  # fall back to the committed profile of an earlier run (and say so)
             rows, src = pmc_profile()
@@ -854,7 +861,7 @@ def main():
             out["roofline"]["passes"] = {p: pass_stats(warm, p, 1) for p in PASSES if pass_stats(warm, p, 1)}
     if distributed and ddp_info:
         out["ddp"] = dict(ddp_info)
-    if rank == 0 and world == 1 and not args.no_fp32 and args.dtype == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_fp32 and args.dtype == "bf16":
         k = max(5, args.steps // 2)
         dt32, _, _, _ = run_det("fp32", 2, k, False)
         alg32 = 3 * 4 * det_alg_elems_per_image(S, S) * B  # SURVEY 8(d)'s whole-step byte model at 4 bytes per element
@@ -862,14 +869,14 @@ def main():
                              "alg_GB_per_step": round(alg32 / 1e9, 2), "whole_step_frac": round(alg32 / (dt32 / k) / 1e9 / HBM_PEAK_GBS, 4),
                              "note": "parity mode = the reference's own arithmetic (train_detection.py:92-97, no autocast): fp32 storage, exact-fp32 MFMA; "
                                      "levels 0-1 on the row-streaming kernels of csrc/det_rs32.hip (round 6)"}
-    if rank == 0 and world == 1 and not args.no_ref_style:
+    if args.full and rank == 0 and world == 1 and not args.no_ref_style:
         # the step exactly as the reference's loop runs it (train_detection.py:87-98): uint8 H2D copy + device transform_image + loss.item()
         k = max(5, args.steps // 2)
         dtr, _, _, _ = run_det(args.dtype, 2, k, False, ref_style=True)
         out["reference_style_step"] = {"value": round(B * k / dtr, 2), "unit": "images/s", "ms_per_step": round(dtr / k * 1e3, 3), "steps": k,
                                        "h2d_in_step": True, "loss_item_per_step": True,
                                        "note": "pinned uint8 tile + mask batch copied H2D every step, transform_image on the device, loss.item() every step"}
-    if rank == 0 and world == 1 and not args.no_config1:
+    if args.full and rank == 0 and world == 1 and not args.no_config1:
         # BASELINE configs[0] sized step ON THE HIP PATH (B = 2 x 512^2; the CPU figure for the same step is cpu_baseline.det_config1_B2_512):
         # eager (one ctypes call per launch: host-bound) vs graph.GraphedTrainStep (hipGraph replay: one host call per step)
         out["config1_hip"] = {}
@@ -915,7 +922,7 @@ def main():
             del m1, o1, m2, o2, gstep
             torch.cuda.empty_cache()
         out["config1_hip"]["workload"] = "detection train step, 2x1x512x512 (BASELINE configs[0]), seed 1234; eager = one C-ABI call per launch from Python, hipgraph = graph.GraphedTrainStep replay"
-    if rank == 0 and world == 1 and not distributed and not args.no_ddp_probe:
+    if args.full and rank == 0 and world == 1 and not distributed and not args.no_ddp_probe:
         # the data-parallel machinery on this single GPU: a 1-rank RCCL group with OCRS_DDP_FORCE=1 -- every bucket's all-reduce is really
         # issued and waited for, so `exposed_allreduce_ms_per_step` is the cost the overlap does not hide at N = 1 (launch + wait latency)
         try:
@@ -939,9 +946,9 @@ def main():
             os.environ.pop("OCRS_DDP_FORCE", None)
     del img, mask
     torch.cuda.empty_cache()
-    if not args.no_crnn:
+    if args.full and not args.no_crnn:
         out["crnn"] = bench_crnn(args, world, rank, dev, dist, distributed)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -8,4 +8,4 @@ rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace_crnn -- python 
 python tools/trace_step.py gpurun_out/trace_crnn k_conv0_fwd > gpurun_out/crnn_step_trace.txt 2>&1
 find gpurun_out/trace_crnn -name "*kernel_trace.csv" -delete
 tail -3 gpurun_out/trace_crnn.log; tail -2 gpurun_out/crnn_step_trace.txt
-python bench.py --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['crnn']['value'], d['crnn']['ms_per_step'])"
+python bench.py --full --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['crnn']['value'], d['crnn']['ms_per_step'])"
