@@ -13,6 +13,7 @@ There is no CPU path: tensors must be on an MI355X.
 from __future__ import annotations
 
 import math
+from types import MappingProxyType
 
 import torch
 from torch import nn
@@ -74,7 +75,20 @@ class _Act:
 
 
 class _BlockRec:
+    """What a block's backward needs from its forward.  fsum (the first block only): the forward-only sums of its fused weight gradient."""
+
     __slots__ = ("prefix", "a", "b", "z", "tr", "saved", "Cin", "Cout", "H", "W", "fsum")
+
+    def __init__(self, prefix, a, b, z, tr, saved, Cin, Cout, H, W, fsum=None):
+        self.prefix, self.a, self.b, self.z, self.tr, self.saved = prefix, a, b, z, tr, saved
+        self.Cin, self.Cout, self.H, self.W, self.fsum = Cin, Cout, H, W, fsum
+
+
+def _srcs(a, b):
+    """(xa, xb, Ca, Cb, tra, trb) arguments of a block kernel: its input a, or the concatenation of a and b"""
+    if b is None:
+        return ptr(a.t), None, a.C, 0, ptr(a.tr), None
+    return ptr(a.t), ptr(b.t), a.C, b.C, ptr(a.tr), ptr(b.tr)
 
 
 _identity_cache: dict = {}
@@ -95,43 +109,42 @@ def _identity_tr(C, device):
 class _DetRun:
     """One forward (and later backward) pass of the detection network on the current stream."""
 
-    capture = None  # (test tap, see __init__)
     # deep-level ConvTranspose weight gradients on a side stream (they overlap the latency-bound kernels that follow); GraphedTrainStep turns it
     # off around its warm-up and capture (a fork / join the graph does not need)
     overlap = True
-    # round-5 rank-one ends of the network, each compared bit for bit against the path it replaced
+    # routing switches, all on; tests turn them off (on a run, or on the class) to compare each path with the one it replaced -- the off paths
+    # are also the ones eval mode and unsupported shapes take:
+    #   use_mm: the matrix-core block kernels (csrc/det_mm.hip, bf16 levels 0-2);  use_rs32: the fp32 row-streaming kernels (csrc/det_rs32.hip)
+    #   fuse_bn_bwd: BatchNorm-backward sums produced by the consumers' backward pass instead of a bn_bwd_reduce pass
+    #   fold_fwd_fin: BatchNorm statistics finalised inside the forward launch
+    # and the round-5 rank-one ends of the network, each compared bit for bit against the stored path
     # (tests/test_edge_cases_gpu.py::test_rank_one_ends_of_the_network_are_bit_identical_to_the_stored_paths):
     #   c1_u: the first block also writes its 2-byte-per-pixel u plane (read by in_conv.seq.1's forward and backward instead of z)
     #   c1_noz: ... and does not store its 8-channel output at all when every consumer takes the u plane
     #   c1_fuse: the first block's weight gradient from sums accumulated by in_conv.seq.1's backward (no dL/dx~ store, no k_c1_bwd2 pass)
     #   head_gl: out_conv's backward hands the last block gl (4 B / pixel) instead of its 8-channel gradient
-    _switches = {"c1_u": True, "c1_noz": True, "c1_fuse": True, "head_gl": True}
+    use_mm = use_rs32 = fuse_bn_bwd = fold_fwd_fin = True
+    c1_u = c1_noz = c1_fuse = head_gl = True
+    # per-pass state, declared here with its value between passes (immutable defaults: a run the op tests assemble field by field reads them too):
+    packs = MappingProxyType({})  # this step's weight-fragment packs (prepack); empty outside a full forward
+    _zpool, _zoff = None, 0  # the fp64 accumulator pool (zeros64)
+    _flat, _folds, _defer_folds = None, (), False  # the flat gradient buffer of a backward and its deferred fp64 folds (fold64)
+    _keep_ws, _deferring = None, False  # inside backward(): the workspaces the deferral window still reads (_hold)
+    _head_gl = _c1acc = None  # the backward's hand-overs out_conv -> last block (gl) and in_conv.seq.1 -> first block (c1acc)
 
-    def __init__(self, mod, x, names, params, train):
+    def __init__(self, P, Bf, dev, dtype, N, train=True, mod=None, x=None):
+        """P / Bf: parameters / buffers by state-dict name (P in the module's parameter order); mod / x: the module and the input image of a
+        whole-network pass (forward / backward need them; the op tests drive single stages without)."""
         self.L = lib()
-        self.mod = mod
-        self.P = dict(zip(names, params))
-        self.names = names
-        self.Bf = dict(mod.named_buffers())
-        self.train = train
-        self.dev = x.device
-        self.dtype = mod._act_dtype()
-        self.dt = _DT[self.dtype]
-        self.N = x.shape[0]
+        self.P, self.Bf, self.names = P, Bf, list(P)
+        self.dev, self.dtype, self.dt, self.N, self.train = dev, dtype, _DT[dtype], N, train
+        self.mod, self.x = mod, x
         self.recs = {}
         self.fused = {}  # block prefix -> fp64 [2][C] BatchNorm-backward sums accumulated by its consumers' dw_bwd
-        # routing switches, all on; tests/test_det_ops_gpu.py turns them off on a run to compare the paths: the matrix-core block kernels
-        # (csrc/det_mm.hip, bf16 levels 0-2), the fp32 row-streaming kernels (csrc/det_rs32.hip), BatchNorm-backward sums produced by the
-        # consumers' backward pass instead of a bn_bwd_reduce pass, BatchNorm statistics finalised inside the forward launch
-        self.use_mm = self.use_rs32 = self.fuse_bn_bwd = self.fold_fwd_fin = True
-        sw = _DetRun._switches
-        self.c1_u, self.c1_noz, self.c1_fuse, self.head_gl = sw["c1_u"], sw["c1_noz"], sw["c1_fuse"], sw["head_gl"]
         self.pooled_by_block = None
-        self.x = x
         # test tap (tests/test_det_bf16_layerwise_gpu.py): when the module carries a dict ``_capture`` every backward stage records the gradient
         # tensors it consumed / produced there, and the run itself (saved activations) is kept alive in it; None in production
         self.capture = getattr(mod, "_capture", None)
-        self._keep_ws, self._deferring = [], False
         if self.capture is not None:
             self.capture["run"] = self
 
@@ -139,17 +152,27 @@ class _DetRun:
     def empty(self, *shape, dtype=None):
         return torch.empty(shape, dtype=dtype or self.dtype, device=self.dev)
 
+    def fits32(self, H, W, C):
+        """an fp32 [N, H, W, C] tensor is addressable with 32-bit buffer offsets (the row-streaming kernels' limit)"""
+        return self.N * H * W * C * 4 < 2 ** 32
+
+    def bn_fin(self, prefix, C):
+        """-> (tr, saved, the argument tail from gamma on of a training-mode finalisation of BatchNorm `prefix` into them)"""
+        P, Bf = self.P, self.Bf
+        tr, saved = self.empty(3, C, dtype=torch.float32), self.empty(2, C, dtype=torch.float32)
+        return tr, saved, (ptr(P[f"{prefix}.weight"]), ptr(P[f"{prefix}.bias"]), 1e-5, 0.1, ptr(tr), ptr(saved), ptr(Bf[f"{prefix}.running_mean"]),
+                           ptr(Bf[f"{prefix}.running_var"]), ptr(Bf[f"{prefix}.num_batches_tracked"]), 0.0)
+
     def _hold(self, ws):
-        keep = getattr(self, "_keep_ws", None)  # (absent when a block backward is driven directly, outside backward(): nothing is deferred then)
-        if keep is not None:
-            keep.append(ws)
+        if self._keep_ws is not None:  # (released at the end of backward(), after the deferred reductions that read ws; outside it nothing is deferred)
+            self._keep_ws.append(ws)
 
     def zeros64(self, n):
         """n zeroed float64 values carved from one per-step pool (one fill launch instead of ~50 small memsets)."""
-        pool = getattr(self, "_zpool", None)
+        pool = self._zpool
         n8 = (n + 7) // 8 * 8
         if pool is None or self._zoff + n8 > pool.numel():
-            if pool is not None and getattr(self, "_folds", None) and self.overlap:
+            if pool is not None and self._folds and self.overlap:
                 # pool overflow in the middle of a backward (latent with the default net: ~6.6 k of the 8192 doubles): a queued fold may name a
                 # ConvTranspose bias accumulator that convt_bwd_parts(..., 2) is still writing on the side stream -- join it before folding
                 torch.cuda.current_stream().wait_stream(_side_stream(self.dev))
@@ -164,8 +187,7 @@ class _DetRun:
         """dst (a view into this backward's flat fp32 gradient buffer) += src64 (fp64 accumulators carved by zeros64).  Single-GPU runs collect
         these ~10 tiny adds of a step and run them as ONE launch at the end of the backward (ocrs_fold64_multi); with a gradient bucketer
         (DDP: stages are reported as they complete) or outside a backward the add runs at once."""
-        flat = getattr(self, "_flat", None)
-        if flat is None or self._defer_folds is False or src64._base is not self._zpool:
+        if self._flat is None or not self._defer_folds or src64._base is not self._zpool:
             dst.view(-1).add_(src64)
             return
         self._folds.append((dst.storage_offset(), src64.storage_offset(), src64.numel()))
@@ -173,7 +195,7 @@ class _DetRun:
     _FOLD_TABLES = {}
 
     def fold_flush(self):
-        folds = getattr(self, "_folds", None)
+        folds = self._folds
         if not folds:
             return
         key = (self.dev, tuple(folds))
@@ -187,7 +209,7 @@ class _DetRun:
 
     def pack(self, src, mode, K, M, K2, s1, s2, sm):
         """MFMA weight fragments of one layer: from this step's multi-pack buffer (prepack) or, outside a full forward, packed here."""
-        hit = getattr(self, "packs", {}).get((src.data_ptr(), mode, K, M, s2, sm))
+        hit = self.packs.get((src.data_ptr(), mode, K, M, s2, sm))
         if hit is not None:
             return hit
         nbytes = self.L.pack_frags_bytes(K, M, self.dt)
@@ -230,14 +252,11 @@ class _DetRun:
     def bn_tr(self, prefix, gstat, count, C, nparts=0):
         """gstat: fp64 [2][C] accumulated sums, or (nparts > 0) fp32 per-block partials [nparts][C][2] of the matrix-core forward"""
         P, Bf = self.P, self.Bf
-        tr = self.empty(3, C, dtype=torch.float32)
-        saved = self.empty(2, C, dtype=torch.float32)
+        tr, saved, fin = self.bn_fin(prefix, C)
         if self.train and nparts:
-            self.L.bn_finalize_parts(ptr(gstat), nparts, count, C, ptr(P[f"{prefix}.weight"]), ptr(P[f"{prefix}.bias"]), 1e-5, 0.1, ptr(tr), ptr(saved),
-                                     ptr(Bf[f"{prefix}.running_mean"]), ptr(Bf[f"{prefix}.running_var"]), ptr(Bf[f"{prefix}.num_batches_tracked"]), 0.0)
+            self.L.bn_finalize_parts(ptr(gstat), nparts, count, C, *fin)
         elif self.train:
-            self.L.bn_finalize(ptr(gstat), count, C, ptr(P[f"{prefix}.weight"]), ptr(P[f"{prefix}.bias"]), 1e-5, 0.1, ptr(tr), ptr(saved),
-                               ptr(Bf[f"{prefix}.running_mean"]), ptr(Bf[f"{prefix}.running_var"]), ptr(Bf[f"{prefix}.num_batches_tracked"]), 0.0)
+            self.L.bn_finalize(ptr(gstat), count, C, *fin)
         else:
             rstd = torch.rsqrt(Bf[f"{prefix}.running_var"] + 1e-5)
             tr[0] = P[f"{prefix}.weight"].detach() * rstd
@@ -245,83 +264,92 @@ class _DetRun:
             tr[2] = 0.0
         return tr, saved
 
+    # -- routing: the kernel family of a DepthwiseConv block's forward / backward ------------------
+    def fwd_route(self, Ca, Cb, Cout, H, W):
+        """"mm": the matrix-core kernels (csrc/det_mm.hip, bf16 levels 0-2), "rs32": the fp32 row-streaming kernels (csrc/det_rs32.hip, wide
+        levels), "tile": the generic tiled kernels (deep levels, and whatever the other two do not take)"""
+        if self.use_mm and self.L.mm_fwd_supported(Ca, Cb, Cout, self.dt):
+            return "mm"
+        if self.use_rs32 and self.L.rs32_fwd_supported(Ca, Cb, Cout, self.dt) and self.fits32(H, W, max(Ca + Cb, Cout)):
+            return "rs32"
+        return "tile"
+
+    def bwd_route(self, r, pooled, need_gx):
+        """the backward of block record r: "c1" (the first block), else as fwd_route"""
+        if r.Cin == 1:
+            return "c1"
+        L, C, H, W = self.L, r.Cout, r.H, r.W
+        Ca, Cb = r.a.C, (r.b.C if r.b is not None else 0)
+        if self.use_mm and need_gx and H >= 2 and W >= 2 and L.mm_bwd_supported(Ca, Cb, C, self.dt):
+            return "mm"
+        if (self.use_rs32 and need_gx and L.rs32_bwd_supported(Ca, Cb, C, 1 if pooled else 0, self.dt) and self.fits32(H, W, max(r.Cin, C))
+                and (not pooled or (H >= 2 and W >= 2))):
+            return "rs32"
+        return "tile"
+
     # -- forward ---------------------------------------------------------------------------------
     def block(self, prefix, a, b, Cout, pool=False):
         """-> the block's output activation (raw z + load transform); with pool=True also ``self.pooled_by_block``: the 2x2 max-pooled
         (pre-BatchNorm) output written by the same kernel, or None when that configuration has no fused pooling"""
         L, P, N = self.L, self.P, self.N
         H, W = a.H, a.W
-        Cin = a.C + (b.C if b is not None else 0)
+        Cb = b.C if b is not None else 0
+        Cin = a.C + Cb
         wdw, wpw = P[f"{prefix}.seq.0.weight"], P[f"{prefix}.seq.1.weight"]
         z = self.empty(N, H, W, Cout)
-        Cb = b.C if b is not None else 0
-        bnp, Bf = f"{prefix}.seq.2", self.Bf
+        bnp = f"{prefix}.seq.2"
         # (training: the BatchNorm statistics are finalised by the last workgroup of the forward launch, bit-identical to the separate finalisation)
-        if self.use_mm and L.mm_fwd_supported(a.C, Cb, Cout, self.dt):
+        fin = self.train and self.fold_fwd_fin
+        pooled = gamma = None
+        route = self.fwd_route(a.C, Cb, Cout, H, W)
+        if route == "mm":
             # depthwise + pointwise as ONE implicit GEMM on the matrix cores; batch statistics as deterministic per-block partials
-            pooled = gamma = None
             if pool:  # max-pool written by the same kernel instead of a separate pass over the full-size z
-                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
-            self.pooled_by_block = pooled
+                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{bnp}.weight"]
             nparts = L.mm_fwd_nparts(a.C, Cb, Cout, N, H, W)
             parts = self.empty(nparts * 2 * Cout, dtype=torch.float32)
-            if self.train and self.fold_fwd_fin and a.u is not None and b is None and pooled is None and Cout in (8, 16):
+            if fin and a.u is not None and b is None and pooled is None and Cout in (8, 16):
                 # the block behind the first block: its input is rebuilt from the first block's u plane (2 instead of 16 bytes per pixel)
-                tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-                L.mm_fwd_fin_xu(ptr(a.u), ptr(a.wexp), ptr(a.tr), ptr(wdw), ptr(wpw), ptr(z), ptr(parts), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]),
-                                ptr(P[f"{bnp}.bias"]), 1e-5, 0.1, ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]),
-                                ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0, Cout, N, H, W, self.dt)
-            elif self.train and self.fold_fwd_fin:
-                tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-                L.mm_fwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
-                             ptr(z), ptr(parts), ptr(gamma), ptr(pooled), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]), ptr(P[f"{bnp}.bias"]),
-                             1e-5, 0.1, ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]),
-                             ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0, Cout, N, H, W, self.dt)
+                tr, saved, fin_args = self.bn_fin(bnp, Cout)
+                L.mm_fwd_fin_xu(ptr(a.u), ptr(a.wexp), ptr(a.tr), ptr(wdw), ptr(wpw), ptr(z), ptr(parts), ptr(self.zeros64(1)), N * H * W, *fin_args,
+                                Cout, N, H, W, self.dt)
+            elif fin:
+                tr, saved, fin_args = self.bn_fin(bnp, Cout)
+                L.mm_fwd_fin(*_srcs(a, b), ptr(wdw), ptr(wpw), ptr(z), ptr(parts), ptr(gamma), ptr(pooled), ptr(self.zeros64(1)), N * H * W, *fin_args,
+                             Cout, N, H, W, self.dt)
             else:
-                L.mm_fwd(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
-                         ptr(z), ptr(parts), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
+                L.mm_fwd(*_srcs(a, b), ptr(wdw), ptr(wpw), ptr(z), ptr(parts), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
                 tr, saved = self.bn_tr(bnp, parts, N * H * W, Cout, nparts=nparts)
-        elif self.use_rs32 and L.rs32_fwd_supported(a.C, Cb, Cout, self.dt) and N * H * W * max(Cin, Cout) * 4 < 2 ** 32:  # (32-bit buffer offsets)
+        elif route == "rs32":
             # fp32 (parity mode), wide levels: register-resident row-streaming waves (csrc/det_rs32.hip) -- no LDS tile, exact-fp32 matrix cores
-            pooled = gamma = None
             if pool:
-                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
-            self.pooled_by_block = pooled
+                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{bnp}.weight"]
             gstat = self.zeros64(2 * Cout)
-            common = (ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw), ptr(z),
-                      ptr(gstat), ptr(gamma), ptr(pooled))
-            if self.train and self.fold_fwd_fin:
-                tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-                L.rs32_fwd(*common, ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]), ptr(P[f"{bnp}.bias"]), 1e-5, 0.1, ptr(tr), ptr(saved),
-                           ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]), ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0, Cout, N, H, W)
+            common = (*_srcs(a, b), ptr(wdw), ptr(wpw), ptr(z), ptr(gstat), ptr(gamma), ptr(pooled))
+            if fin:
+                tr, saved, fin_args = self.bn_fin(bnp, Cout)
+                L.rs32_fwd(*common, ptr(self.zeros64(1)), N * H * W, *fin_args, Cout, N, H, W)
             else:
                 L.rs32_fwd(*common, None, 0, None, None, 0.0, 0.0, None, None, None, None, None, 0.0, Cout, N, H, W)
                 tr, saved = self.bn_tr(bnp, gstat, N * H * W, Cout)
         else:
             wpk = self.pack(wpw, 0, Cin, Cout, Cin, 0, 1, Cin)
             gstat = self.zeros64(2 * Cout)
-            pooled = gamma = None
             if pool and L.dwpw_fwd_pool_supported(Cin, Cout):
-                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{prefix}.seq.2.weight"]
-            self.pooled_by_block = pooled
-            if self.train and self.fold_fwd_fin and pooled is None and L.dwpw_fwd_fin_supported(Cin, Cout, self.dt):  # deep levels (ocrs_bn_finalize's arithmetic)
-                tr, saved = self.empty(3, Cout, dtype=torch.float32), self.empty(2, Cout, dtype=torch.float32)
-                L.dwpw_fwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None,
-                               ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(self.zeros64(1)), N * H * W, ptr(P[f"{bnp}.weight"]), ptr(P[f"{bnp}.bias"]), 1e-5, 0.1,
-                               ptr(tr), ptr(saved), ptr(Bf[f"{bnp}.running_mean"]), ptr(Bf[f"{bnp}.running_var"]), ptr(Bf[f"{bnp}.num_batches_tracked"]), 0.0,
-                               Cout, N, H, W, self.dt)
+                pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{bnp}.weight"]
+            if fin and pooled is None and L.dwpw_fwd_fin_supported(Cin, Cout, self.dt):  # deep levels (ocrs_bn_finalize's arithmetic)
+                tr, saved, fin_args = self.bn_fin(bnp, Cout)
+                L.dwpw_fwd_fin(*_srcs(a, b), ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(self.zeros64(1)), N * H * W, *fin_args, Cout, N, H, W, self.dt)
             else:
-                L.dwpw_fwd(ptr(a.t), ptr(b.t) if b is not None else None, a.C, Cb, ptr(a.tr),
-                           ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
+                L.dwpw_fwd(*_srcs(a, b), ptr(wdw), ptr(wpk), ptr(z), ptr(gstat), ptr(gamma), ptr(pooled), Cout, N, H, W, self.dt)
                 tr, saved = self.bn_tr(bnp, gstat, N * H * W, Cout)
-        r = _BlockRec()
-        r.fsum = None
-        r.prefix, r.a, r.b, r.z, r.tr, r.saved, r.Cin, r.Cout, r.H, r.W = prefix, a, b, z, tr, saved, Cin, Cout, H, W
-        self.recs[prefix] = r
+        self.pooled_by_block = pooled
+        self.recs[prefix] = _BlockRec(prefix, a, b, z, tr, saved, Cin, Cout, H, W)
         return _Act(z, tr, Cout, H, W, src=prefix)
 
     def block_c1(self, prefix, img, H, W):
         L, P, N = self.L, self.P, self.N
+        wdw, wpw = P[f"{prefix}.seq.0.weight"], P[f"{prefix}.seq.1.weight"]
         z = self.empty(N, H, W, 8)
         gstat = self.zeros64(16)
         uplane = fsum = None
@@ -336,19 +364,15 @@ class _DetRun:
             # block's weight-gradient sums instead of storing its input gradient (ocrs_mm_bwd_fin_xu_c1), this launch adds the forward-only sums
             fsum = self.zeros64(20) if (z is None and self.c1_fuse) else None
             if fsum is not None:
-                L.dwpw_c1_fwd_us(ptr(img), ptr(P[f"{prefix}.seq.0.weight"]), ptr(P[f"{prefix}.seq.1.weight"]), ptr(z), ptr(uplane), ptr(gstat), ptr(fsum), N, H, W,
-                                 self.dt)
+                L.dwpw_c1_fwd_us(ptr(img), ptr(wdw), ptr(wpw), ptr(z), ptr(uplane), ptr(gstat), ptr(fsum), N, H, W, self.dt)
             else:
-                L.dwpw_c1_fwd_u(ptr(img), ptr(P[f"{prefix}.seq.0.weight"]), ptr(P[f"{prefix}.seq.1.weight"]), ptr(z), ptr(uplane), ptr(gstat), N, H, W, self.dt)
+                L.dwpw_c1_fwd_u(ptr(img), ptr(wdw), ptr(wpw), ptr(z), ptr(uplane), ptr(gstat), N, H, W, self.dt)
         else:
-            L.dwpw_c1_fwd(ptr(img), ptr(P[f"{prefix}.seq.0.weight"]), ptr(P[f"{prefix}.seq.1.weight"]), ptr(z), ptr(gstat), N, H, W, self.dt)
+            L.dwpw_c1_fwd(ptr(img), ptr(wdw), ptr(wpw), ptr(z), ptr(gstat), N, H, W, self.dt)
         tr, saved = self.bn_tr(f"{prefix}.seq.2", gstat, N * H * W, 8)
-        r = _BlockRec()
-        r.prefix, r.a, r.b, r.z, r.tr, r.saved, r.Cin, r.Cout, r.H, r.W = prefix, None, None, z, tr, saved, 1, 8, H, W
-        self.recs[prefix] = r
+        self.recs[prefix] = _BlockRec(prefix, None, None, z, tr, saved, 1, 8, H, W, fsum)
         out = _Act(z, tr, 8, H, W, src=prefix)
-        out.u, out.wexp = uplane, P[f"{prefix}.seq.1.weight"]
-        r.fsum = fsum if uplane is not None else None
+        out.u, out.wexp = uplane, wpw
         return out
 
     def double(self, prefix, a, b, Cout, pool=False):
@@ -386,8 +410,8 @@ class _DetRun:
             wpk = self.pack(P[f"up.{i}.up.weight"], 1, 4 * Cup, 4 * Cout, Cup, 0, 0, 0)
             t = self.empty(N, skip.H, skip.W, Cout)
             up.other_use = True
-            if (self.use_rs32 and L.rs32_convt_fwd_supported(Cup, Cout, self.dt)  # fp32, wide levels: row-streaming over the input grid (csrc/det_rs32.hip)
-                    and N * skip.H * skip.W * Cout * 4 < 2 ** 32):
+            # fp32, wide levels: row-streaming over the input grid (csrc/det_rs32.hip)
+            if self.use_rs32 and L.rs32_convt_fwd_supported(Cup, Cout, self.dt) and self.fits32(skip.H, skip.W, Cout):
                 L.rs32_convt_fwd(ptr(up.t), ptr(up.tr), ptr(P[f"up.{i}.up.weight"]), ptr(P[f"up.{i}.up.bias"]), ptr(t), Cup, Cout, N, up.H, up.W, skip.H, skip.W)
             else:
                 L.convt_fwd(ptr(up.t), ptr(up.tr), ptr(wpk), ptr(P[f"up.{i}.up.bias"]), ptr(t), Cup, Cout, N, up.H, up.W, skip.H, skip.W, self.dt)
@@ -397,10 +421,7 @@ class _DetRun:
         pred = self.empty(N, 1, H, W, dtype=torch.float32)
         up.other_use = True
         L.head_fwd(ptr(up.t), ptr(up.tr), ptr(P["out_conv.0.weight"]), ptr(P["out_conv.0.bias"]), ptr(pred), N * H * W, self.dt)
-        self.head_in = up
-        self.pred = pred
-        self.skips = skips
-        self.HW = (H, W)
+        self.head_in, self.pred, self.skips, self.HW = up, pred, skips, (H, W)
         return pred
 
     # -- backward --------------------------------------------------------------------------------
@@ -418,29 +439,22 @@ class _DetRun:
         if gsum is None:
             gsum = self.zeros64(2 * C)
             L.bn_bwd_reduce(ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(r.saved), ptr(gsum), C, N, H, W, self.dt)
-        gam, dgam, dbet = P[f"{prefix}.seq.2.weight"], self.G[f"{prefix}.seq.2.weight"], self.G[f"{prefix}.seq.2.bias"]
-        a, b = r.a, r.b
-        # block backward on the matrix cores (csrc/det_mm.hip): bf16, levels 0-2
-        use_mm = (r.Cin != 1 and self.use_mm and need_gx and H >= 2 and W >= 2
-                  and L.mm_bwd_supported(a.C, b.C if b is not None else 0, C, self.dt))
-        coef = None
-        # BatchNorm-backward finalisation: derived from gsum in the prologue of the matrix-core kernel, inside ocrs_pw_bwd_fin on the generic
-        # path (which needs coef as scratch); its own launch only for the first block
-        if not use_mm:
+        route = self.bwd_route(r, pooled, need_gx)
+        gam, wdw, wpw = P[f"{prefix}.seq.2.weight"], P[f"{prefix}.seq.0.weight"], P[f"{prefix}.seq.1.weight"]
+        dWdw, dWpw, dgamma, dbeta = (self.G[f"{prefix}.seq.{k}"] for k in ("0.weight", "1.weight", "2.weight", "2.bias"))
+        # BatchNorm-backward finalisation: derived from gsum in the prologue of the matrix-core / row-streaming kernels, inside ocrs_pw_bwd_fin on the
+        # tiled path (which needs coef as scratch); its own launch only for the first block
+        if route == "c1":
             coef = self.empty(3, C, dtype=torch.float32)
-            if r.Cin == 1:
-                L.bn_bwd_finalize(ptr(gsum), N * H * W, C, ptr(gam), ptr(r.saved), ptr(coef), ptr(dgam), ptr(dbet))
-        wdw, wpw = P[f"{prefix}.seq.0.weight"], P[f"{prefix}.seq.1.weight"]
-        if r.Cin == 1:
+            L.bn_bwd_finalize(ptr(gsum), N * H * W, C, ptr(gam), ptr(r.saved), ptr(coef), ptr(dgamma), ptr(dbeta))
             acc = self.zeros64(17)  # fp64 accumulators (order-independent), folded into the fp32 gradients below
-            c1acc = getattr(self, "_c1acc", None)
-            if c1acc is not None:  # the sums are already there (ocrs_mm_bwd_fin_xu_c1): no pass over the image and the gradient
-                self._c1acc = None
+            if self._c1acc is not None:  # the sums are already there (ocrs_mm_bwd_fin_xu_c1): no pass over the image and the gradient
+                c1acc, self._c1acc = self._c1acc, None
                 L.c1_bwd_fin(ptr(c1acc), ptr(r.fsum), ptr(coef), ptr(wpw), ptr(acc))
             else:
                 L.dwpw_c1_bwd(ptr(self.x), ptr(wdw), ptr(wpw), ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(acc), N, H, W, self.dt)
-            self.fold64(self.G[f"{prefix}.seq.1.weight"], acc[:8])
-            self.fold64(self.G[f"{prefix}.seq.0.weight"], acc[8:17])
+            self.fold64(dWpw, acc[:8])
+            self.fold64(dWdw, acc[8:17])
             return None, None
         a, b = r.a, r.b
         Ca, Cb = a.C, (b.C if b is not None else 0)
@@ -453,79 +467,61 @@ class _DetRun:
             if act.src not in self.fused:
                 self.fused[act.src] = self.zeros64(2 * act.C)
             return self.recs[act.src].saved, self.fused[act.src]
-        if use_mm:
-            # dz, dgrad of both convs, both weight gradients and the producers' BatchNorm-backward sums from ONE staged copy of (g, z, x)
+        if route in ("mm", "rs32"):
+            # mm (bf16): dz, dgrad of both convs, both weight gradients and the producers' BatchNorm-backward sums from ONE staged copy of (g, z, x);
+            # rs32 (fp32 parity mode): the whole block backward as ONE row-streaming pass -- dz coefficients derived in the prologue, `du` never
+            # stored, both weight gradients and the producers' BatchNorm-backward sums from the same registers
             gxa = self.empty(N, H, W, Ca)
             gxb = self.empty(N, H, W, Cb) if b is not None else None
             sva, gsa = stat_target(a)
             svb, gsb = stat_target(b)
-            ws = self.empty(L.mm_bwd_ws_floats(Ca, Cb, C, N, H, W), dtype=torch.float32)
+            ws = self.empty((L.mm_bwd_ws_floats if route == "mm" else L.rs32_bwd_ws_floats)(Ca, Cb, C, N, H, W), dtype=torch.float32)
             self._hold(ws)  # (its reduction may be queued until the end of the backward)
-            gl = getattr(self, "_head_gl", None)
-            if gl is not None and g1 is gl:  # the block in front of out_conv: its output gradient is formed from gl inside the launch
+            if self._head_gl is not None and g1 is self._head_gl:
+                # the block in front of out_conv: its output gradient is formed from gl (4 B / pixel) inside the launch
+                head = (ptr(a.t), Ca, ptr(a.tr), ptr(wdw), ptr(wpw), ptr(g1), ptr(P["out_conv.0.weight"]), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam),
+                        ptr(r.saved), ptr(dgamma), ptr(dbeta), ptr(gxa), ptr(dWpw), ptr(dWdw), ptr(ws), ptr(sva), ptr(gsa), C, N, H, W)
                 self._head_gl = None
-                L.mm_bwd_fin_head(ptr(a.t), Ca, ptr(a.tr), ptr(wdw), ptr(wpw), ptr(gl), ptr(P["out_conv.0.weight"]), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam),
-                                  ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]),
-                                  ptr(ws), ptr(sva), ptr(gsa), C, N, H, W, self.dt)
+                if route == "mm":
+                    L.mm_bwd_fin_head(*head, self.dt)
+                else:
+                    L.rs32_bwd_head(*head)
                 return gxa, gxb
-            if (a.u is not None and b is None and not pooled and L.mm_bwd_head_supported(Ca, 0, C, N, H, W, self.dt)):
+            if route == "rs32":
+                L.rs32_bwd(*_srcs(a, b), ptr(wdw), ptr(wpw), ptr(g1), ptr(g2), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgamma),
+                           ptr(dbeta), ptr(gxa), ptr(gxb), ptr(dWpw), ptr(dWdw), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb), 1 if pooled else 0,
+                           C, N, H, W)
+                return gxa, gxb
+            if a.u is not None and b is None and not pooled and L.mm_bwd_head_supported(Ca, 0, C, N, H, W, self.dt):
                 # the block behind the first block: its input is rebuilt from the first block's u plane (2 instead of 16 bytes per pixel)
                 r1 = self.recs.get(a.src) if a.src is not None else None
-                if r1 is not None and getattr(r1, "fsum", None) is not None and C == 8 and sva is not None and self.capture is None:
+                if r1 is not None and r1.fsum is not None and C == 8 and sva is not None and self.capture is None:
                     # ... and its input gradient is not stored at all: the first block's weight-gradient sums are accumulated here
                     c1acc = self.zeros64(8 * 32)
-                    L.mm_bwd_fin_xu_c1(ptr(a.u), ptr(a.wexp), ptr(a.tr), ptr(wdw), ptr(wpw), ptr(g1), ptr(g2), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved),
-                                       ptr(dgam), ptr(dbet), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva),
-                                       ptr(gsa), ptr(self.x), ptr(c1acc), C, N, H, W, self.dt)
+                    L.mm_bwd_fin_xu_c1(ptr(a.u), ptr(a.wexp), ptr(a.tr), ptr(wdw), ptr(wpw), ptr(g1), ptr(g2), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam),
+                                       ptr(r.saved), ptr(dgamma), ptr(dbeta), ptr(dWpw), ptr(dWdw), ptr(ws), ptr(sva), ptr(gsa), ptr(self.x), ptr(c1acc),
+                                       C, N, H, W, self.dt)
                     self._c1acc = c1acc
                     return None, None
                 L.mm_bwd_fin_xu(ptr(a.u), ptr(a.wexp), ptr(a.tr), ptr(wdw), ptr(wpw), ptr(g1), ptr(g2), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved),
-                                ptr(dgam), ptr(dbet), ptr(gxa), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws),
-                                ptr(sva), ptr(gsa), C, N, H, W, self.dt)
+                                ptr(dgamma), ptr(dbeta), ptr(gxa), ptr(dWpw), ptr(dWdw), ptr(ws), ptr(sva), ptr(gsa), C, N, H, W, self.dt)
                 return gxa, gxb
-            L.mm_bwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw),
-                         ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(gxb),
-                         ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb),
-                         C, N, H, W, self.dt)
+            L.mm_bwd_fin(*_srcs(a, b), ptr(wdw), ptr(wpw), ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgamma),
+                         ptr(dbeta), ptr(gxa), ptr(gxb), ptr(dWpw), ptr(dWdw), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb), C, N, H, W, self.dt)
             return gxa, gxb
-        if (self.use_rs32 and need_gx and L.rs32_bwd_supported(Ca, Cb, C, 1 if pooled else 0, self.dt) and N * H * W * max(r.Cin, C) * 4 < 2 ** 32
-                and (not pooled or (H >= 2 and W >= 2))):
-            # fp32 (parity mode), wide levels: the whole block backward as ONE row-streaming pass (csrc/det_rs32.hip) -- dz coefficients derived in the
-            # prologue, `du` never stored, both weight gradients and the producers' BatchNorm-backward sums from the same registers
-            gxa = self.empty(N, H, W, Ca)
-            gxb = self.empty(N, H, W, Cb) if b is not None else None
-            sva, gsa = stat_target(a)
-            svb, gsb = stat_target(b)
-            ws = self.empty(L.rs32_bwd_ws_floats(Ca, Cb, C, N, H, W), dtype=torch.float32)
-            self._hold(ws)  # (its reduction may be queued until the end of the backward)
-            gl = getattr(self, "_head_gl", None)
-            if gl is not None and g1 is gl:  # the block in front of out_conv: its output gradient is formed from gl (4 B / pixel) inside the launch
-                self._head_gl = None
-                L.rs32_bwd_head(ptr(a.t), Ca, ptr(a.tr), ptr(wdw), ptr(wpw), ptr(gl), ptr(P["out_conv.0.weight"]), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam),
-                                ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws),
-                                ptr(sva), ptr(gsa), C, N, H, W)
-                return gxa, gxb
-            L.rs32_bwd(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(wpw), ptr(g1),
-                       ptr(g2), ptr(r.z), ptr(r.tr), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(gxa), ptr(gxb),
-                       ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb),
-                       1 if pooled else 0, C, N, H, W)
-            return gxa, gxb
-        if getattr(self, "_head_gl", None) is not None and g1 is self._head_gl:
-            raise RuntimeError("internal: out_conv handed this block gl instead of its gradient, but the block did not route to a kernel that takes it")
+        coef = self.empty(3, C, dtype=torch.float32)
         du = self.empty(N, H, W, r.Cin)
         ws = self.empty(L.pw_bwd_ws_floats(r.Cin, C, N, H, W), dtype=torch.float32)
         self._hold(ws)  # (its reduction may be queued until the end of the backward)
-        L.pw_bwd_fin(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(g1),
-                     ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgam), ptr(dbet), ptr(wpk_d), ptr(du),
-                     ptr(self.G[f"{prefix}.seq.1.weight"]), ptr(ws), C, N, H, W, self.dt)
+        L.pw_bwd_fin(*_srcs(a, b), ptr(wdw), ptr(g1), ptr(g2), pooled, ptr(r.z), ptr(r.tr), ptr(coef), ptr(gsum), ptr(gam), ptr(r.saved), ptr(dgamma),
+                     ptr(dbeta), ptr(wpk_d), ptr(du), ptr(dWpw), ptr(ws), C, N, H, W, self.dt)
         gxa = self.empty(N, H, W, Ca) if need_gx else None
         gxb = self.empty(N, H, W, Cb) if (need_gx and b is not None) else None
         ws = self.empty(L.dw_bwd_ws_floats(r.Cin, N, H, W), dtype=torch.float32)
         self._hold(ws)  # (its reduction may be queued until the end of the backward)
         sva, gsa = stat_target(a)
         svb, gsb = stat_target(b)
-        L.dw_bwd(ptr(a.t), ptr(b.t) if b is not None else None, Ca, Cb, ptr(a.tr), ptr(b.tr) if b is not None else None, ptr(wdw), ptr(du),
-                 ptr(gxa), ptr(gxb), ptr(self.G[f"{prefix}.seq.0.weight"]), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb), N, H, W, self.dt)
+        L.dw_bwd(*_srcs(a, b), ptr(wdw), ptr(du), ptr(gxa), ptr(gxb), ptr(dWdw), ptr(ws), ptr(sva), ptr(gsa), ptr(svb), ptr(gsb), N, H, W, self.dt)
         return gxa, gxb
 
     def backward(self, gpred):
@@ -536,7 +532,7 @@ class _DetRun:
             if self._deferring:  # (an exception on the way: leave the library's deferral mode)
                 self._deferring = False
                 self.L.bwd_defer_flush()
-            self._keep_ws = []
+            self._keep_ws = None
 
     def _backward(self, gpred):
         L, P, N, w = self.L, self.P, self.N, DEPTH_SCALE
@@ -599,13 +595,13 @@ class _DetRun:
             self.fused[up.src] = gs_head
         acc = self.zeros64(9)
         # out_conv's backward hands the last block either its 8-channel gradient g (16 B per pixel) or -- when that block's backward can form
-        # g = round(gl * w[c]) itself (ocrs_mm_bwd_fin_head: the row-streaming kernel) -- only gl = dL/dlogit (4 B per pixel)
-        r_up = self.recs.get(up.src) if up.src is not None else None
-        head_gl = (self.head_gl and self.capture is None and gs_head is not None and r_up is not None and r_up.b is None and self.use_mm
-                   and L.mm_bwd_head_supported(r_up.a.C, 0, r_up.Cout, N, H, W, self.dt))
-        if not head_gl and self.dt == 0:  # fp32 (round 6): the same hand-over on the row-streaming backward (ocrs_rs32_bwd_head; exactly _block_bwd's routing test)
-            head_gl = bool(self.head_gl and self.capture is None and gs_head is not None and r_up is not None and r_up.b is None and self.use_rs32
-                           and L.rs32_bwd_head_supported(r_up.a.C, 0, r_up.Cout, self.dt) and N * H * W * 8 * 4 < 2 ** 32)
+        # g = round(gl * w[c]) itself (ocrs_mm_bwd_fin_head, fp32: ocrs_rs32_bwd_head) -- only gl = dL/dlogit (4 B per pixel)
+        r_up = self.recs[up.src] if gs_head is not None else None  # (gs_head: up is the raw output of the last block)
+        head_gl = False
+        if self.head_gl and self.capture is None and r_up is not None and r_up.b is None:
+            route = self.bwd_route(r_up, 0, True)  # (as block_bwd routes it below)
+            head_gl = bool((route == "mm" and L.mm_bwd_head_supported(r_up.a.C, 0, r_up.Cout, N, H, W, self.dt))
+                           or (route == "rs32" and L.rs32_bwd_head_supported(r_up.a.C, 0, r_up.Cout, self.dt)))
         if deferred is not None and not (head_gl and (N * H * W) % 4 == 0 and deferred[0].data_ptr() == self.pred.data_ptr()):
             gpred, deferred = _losses.materialize_deferred(deferred), None
         if deferred is not None:
@@ -644,7 +640,7 @@ class _DetRun:
             sv = gs_up = None
             # fp32, wide levels (round 6): the input gradient on the row-streaming kernel (csrc/det_rs32.hip) -- from the MASTER weight, and it also produces
             # the producer block's BatchNorm-backward sums (no ocrs_bn_bwd_reduce pass); the weight / bias half stays ocrs_convt_bwd_parts(.., 2)
-            rs_ctd = (self.use_rs32 and L.rs32_convt_dgrad_supported(Cup, Cout, self.dt) and N * ta.H * ta.W * Cout * 4 < 2 ** 32
+            rs_ctd = (self.use_rs32 and L.rs32_convt_dgrad_supported(Cup, Cout, self.dt) and self.fits32(ta.H, ta.W, Cout)
                       and L.convt_bwd_splittable(Cup, Cout, self.dt))
             if self.fuse_bn_bwd and up_in.src is not None and (rs_ctd or L.convt_bwd_stats_supported(Cup, Cout, self.dt)):
                 # the ConvTranspose is this block's only consumer and stages its z anyway: it also produces the block's BatchNorm-backward sums
@@ -746,8 +742,7 @@ def _check_versions(ctx):
 
 class _DetFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mod, names, *params):
-        run = _DetRun(mod, x, names, [p.detach() for p in params], mod.training)
+    def forward(ctx, run, *params):
         pred = run.forward()
         ctx.run = run
         ctx.params = params
@@ -761,7 +756,7 @@ class _DetFn(torch.autograd.Function):
         # free the saved activations now (like autograd without retain_graph) -- this also breaks the reference cycle
         # pred -> grad_fn -> ctx -> run -> pred, which would otherwise keep ~15 GB per step alive until the cyclic GC runs
         ctx.run = None
-        return (None, None, None, *grads)
+        return (None, *grads)
 
 
 class DetectionModel(nn.Module):
@@ -800,7 +795,8 @@ class DetectionModel(nn.Module):
         for p in params:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("parameters must be contiguous fp32")
+        run = _DetRun(dict(zip(names, (p.detach() for p in params))), dict(self.named_buffers()), x.device, self._act_dtype(), x.shape[0],
+                      self.training, mod=self, x=x)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _DetFn.apply(x, self, names, *params)
-        run = _DetRun(self, x, names, [p.detach() for p in params], self.training)
+            return _DetFn.apply(run, *params)
         return run.forward()

@@ -32,14 +32,10 @@ def cpu(t):
 
 
 def make_run(dev, dtype, N, P, Bf):
-    from ocrs_models_amd._lib import lib
-    from ocrs_models_amd.models import _DT, _DetRun
+    from ocrs_models_amd.models import _DetRun
 
-    r = _DetRun.__new__(_DetRun)
-    r.L, r.P, r.Bf, r.names, r.train, r.dev, r.dtype, r.dt, r.N, r.recs = lib(), P, Bf, list(P), True, dev, dtype, _DT[dtype], N, {}
-    r.fused, r.fuse_bn_bwd, r.fuse_pool, r.pooled_by_block = {}, True, True, None
-    r.use_mm, r.fold_fin, r.overlap, r.fold_fwd_fin, r.c1_u, r.head_gl, r.c1_noz, r.capture = True, True, False, True, True, True, False, None
-    r.use_rs32 = True
+    r = _DetRun(P, Bf, dev, dtype, N)
+    r.c1_noz, r.overlap = False, False
     return r
 
 

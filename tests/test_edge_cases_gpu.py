@@ -211,7 +211,7 @@ def test_rank_one_ends_of_the_network_are_bit_identical_to_the_stored_paths(dev,
             # (c1_noz: the first block does not store its 8-channel output at all -- in_conv.seq.1's forward reads the u plane too;
             #  c1_fuse, the last variant: the first block's weight gradient from sums accumulated by in_conv.seq.1's backward -- see below)
             for k, v in (("c1_u", c1u), ("c1_noz", noz), ("head_gl", hgl), ("c1_fuse", fuse)):
-                monkeypatch.setitem(_DetRun._switches, k, bool(v))
+                monkeypatch.setattr(_DetRun, k, bool(v))
             m.load_state_dict(sd)
             m.zero_grad()
             pred = m(x)

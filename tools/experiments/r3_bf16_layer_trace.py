@@ -20,7 +20,7 @@ m.train()
 names = [n for n, _ in m.named_parameters()]
 params = [p.detach() for _, p in m.named_parameters()]
 with torch.no_grad():
-    run = _DetRun(m, x.to(dev), names, params, True)
+    run = _DetRun(dict(zip(names, params)), dict(m.named_buffers()), dev, torch.bfloat16, B, mod=m, x=x.to(dev))
     pred = run.forward()
 torch.cuda.synchronize()
 def cmp(name, a_nhwc, b_nchw):
