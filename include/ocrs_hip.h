@@ -422,6 +422,59 @@ long ocrs_mask_metrics_ws_bytes(int B, int H, int W);
 int ocrs_mask_metrics(const void* pred, int pred_kind, const void* target, int target_kind, float threshold, int B, int H, int W, double* out, void* ws,
                       hipStream_t st);
 
+/* ------------------------------------------------------------------ layout model -------------- */
+/* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
+ * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.
+ * Dropout (the four sites of nn.TransformerEncoderLayer, torch/nn/modules/transformer.py as instantiated at models.py:385-388): p = 0 skips it;
+ * otherwise element i of a site's tensor is kept iff word (i & 3) of Philox-4x32-10(counter = (i >> 2, site), key = seed) >= p * 2^32, and kept
+ * values are scaled by 1 / (1 - p).  `site` = 4 * layer + {0 attention probabilities, 1 after out_proj, 2 after the ReLU, 3 after linear2}.
+ * Masks are regenerated by the backward entry points from the same (p, seed, site); ocrs_layout_dropout_mask writes one out (1 = kept). */
+int ocrs_layout_dropout_mask(unsigned char* mask, long n, float p, long seed, int site, hipStream_t st);
+/* SinPositionalEncoding(256) (models.py:271-337): boxes [rows][4] -> out [rows][256]; rates [32] = 1 / 10000^(j / 32) as the reference's fp32
+ * expression yields them.  Coordinates are rounded half to even; they must be >= 0 and < 2^24. */
+int ocrs_layout_embed(const float* boxes, const float* rates, float* out, long rows, hipStream_t st);
+/* Self-attention of nn.TransformerEncoderLayer(256, 4) with batch_first=False (models.py:385-388, 400): qkv [S][W][768] = the in-projection's
+ * output (q | k | v, 4 heads of 64), the SEQUENCE axis is the leading one (the pages of the batch), W the independent batch axis; out [S][W][256]
+ * = dropout(softmax(q k^T / 8)) v per (w, head), the layout out_proj reads.  Exact-fp32 MFMA.  1 <= S <= 128 (ocrs_layout_attn_supported).
+ * The dropout element index is ((w * 4 + head) * S + query) * S + key.
+ * _bwd: dout [S][W][256] -> dqkv [S][W][768] (every element written), probabilities and masks recomputed. */
+long ocrs_layout_attn_supported(int S); /* 1 / 0 */
+int ocrs_layout_attn_fwd(const float* qkv, float* out, int S, int W, float p, long seed, int site, hipStream_t st);
+int ocrs_layout_attn_bwd(const float* qkv, const float* dout, float* dqkv, int S, int W, float p, long seed, int site, hipStream_t st);
+/* y = LayerNorm(x + dropout(a)) over rows of 256 (norm1 / norm2 with dropout1 / dropout2 of the post-norm encoder layer, models.py:385-388);
+ * stat (nullable) [rows][2] = mean | rstd for the backward. */
+int ocrs_layout_ln_fwd(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stat, long rows, float eps, float p, long seed,
+                       int site, hipStream_t st);
+/* Its backward: dy = dy1 (+ dy2, nullable: the two gradient paths into a layer output are summed on load); ds [rows][256] = dL/d(x + dropout(a))
+ * (the residual branch's gradient; with p = 0 also the gradient of a); da (p > 0) = the gradient of a.  dgamma / dbeta [256] are WRITTEN as
+ * fixed-order sums of per-workgroup partials in ws (ocrs_layout_ln_bwd_ws_floats(rows) floats). */
+long ocrs_layout_ln_bwd_ws_floats(long rows);
+int ocrs_layout_ln_bwd(const float* dy1, const float* dy2, const float* x, const float* a, const float* stat, const float* gamma, float* ds, float* da,
+                       float* dgamma, float* dbeta, float* ws, long rows, float p, long seed, int site, hipStream_t st);
+/* dropout(relu(.)) on the feed-forward hidden [n] in place (models.py:385-388: activation + dropout of the encoder layer); relu = 0 when the
+ * producing GEMM already applied it.  _bwd: out = g / (1 - p) where the stored h > 0, else 0 (out may alias g). */
+int ocrs_layout_relu_drop_fwd(float* h, long n, int relu, float p, long seed, int site, hipStream_t st);
+int ocrs_layout_relu_drop_bwd(const float* g, const float* h, float* out, long n, float p, hipStream_t st);
+/* Bias gradients of the Linear layers (autograd of models.py:388, 390): out[c] = sum over rows of a[row][c], c < Cout <= C (C % 4 == 0 columns
+ * are read), WRITTEN as a fixed-order sum of per-workgroup partials in ws (ocrs_layout_col_sum_ws_floats(C, rows) floats). */
+long ocrs_layout_col_sum_ws_floats(int C, long rows);
+int ocrs_layout_col_sum(const float* a, int ld, int C, int Cout, float* out, float* ws, long rows, hipStream_t st);
+/* classify's padded output [rows][ld] -> [rows][2], through the sigmoid when probs != 0 (models.py:401-406); and the reverse for its gradient:
+ * g [rows][2] -> dlog [rows][ld] with zero padding columns. */
+int ocrs_layout_head_out(const float* logits, int ld, float* out, long rows, int probs, hipStream_t st);
+int ocrs_layout_head_grad_in(const float* g, float* dlog, int ld, long rows, hipStream_t st);
+/* weighted_loss() = BCEWithLogitsLoss(pos_weight) with mean reduction over rows * 2 elements (train_layout.py:94-97, 128, 166) in one launch:
+ * loss [1]; dlogits (nullable) [rows][2] = d loss / d pred; counts (nullable) [6] int64 = per class {true positives, predicted positives,
+ * target positives} of LayoutAccuracyStats.update (train_layout.py:46-58), a prediction being positive when sigmoid(pred) >= 0.5 in fp32
+ * (train_layout.py:131), or pred >= 0.5 when pred_is_prob != 0 (test(), train_layout.py:164-167, which also feeds the probabilities to the
+ * logits loss).  ws: ocrs_layout_loss_ws_bytes() bytes whose first word is zero on entry (and left zero). */
+long ocrs_layout_loss_ws_bytes(void);
+int ocrs_layout_loss(const float* pred, const float* target, float pos_weight, int pred_is_prob, float* loss, float* dlogits, long long* counts, void* ws,
+                     long rows, hipStream_t st);
+/* precision_recall of both classes (train_layout.py:24-35, 55-63: int64 counts divided as fp32, 0 / 0 = NaN) added to the running sums on the
+ * device: sums [5] fp64 = line-start precision | recall | line-end precision | recall | number of updates. */
+int ocrs_layout_stats_update(const long long* counts, double* sums, hipStream_t st);
+
 /* ------------------------------------------------------------------ optimiser ---------------- */
 /* table [nt][5] int64 {param, grad, exp_avg, exp_avg_sq, numel}; chunks [nchunks][2] int32 {tensor, chunk of ocrs_opt_chunk()}. */
 int ocrs_opt_chunk(void);

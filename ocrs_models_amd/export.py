@@ -2,7 +2,7 @@
 
 The reference exports its models with ``torch.onnx.export(model, ...)`` (ocrs_models/train_detection.py:391-406,
 ocrs_models/train_rec.py:396-409) so that downstream tooling can convert them; a model whose ``forward`` launches HIP kernels
-through a C ABI cannot be traced.  ``AtenGraph(model)`` wraps a ``DetectionModel`` / ``RecognitionModel`` of this package (sharing
+through a C ABI cannot be traced.  ``AtenGraph(model)`` wraps a ``DetectionModel`` / ``RecognitionModel`` / ``LayoutModel`` of this package (sharing
 its parameter and buffer tensors, nothing is copied) in an ``nn.Module`` whose ``forward`` is written with stock
 ``torch.nn.functional`` operators only: it runs on any device, traces, and exports.  It is NOT the product path (no kernel of
 this package is involved) and it is inference / export only.
@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .models import DEPTH_SCALE, DetectionModel
+from .layout import LayoutModel
 from .recognition import RecognitionModel
 
 
@@ -58,13 +59,20 @@ def recognition_forward(m: RecognitionModel, x: torch.Tensor) -> torch.Tensor:
     return m.output(x)
 
 
+def layout_forward(m: LayoutModel, x: torch.Tensor) -> torch.Tensor:
+    """models.py:392-406: the reference architecture itself -- m.embed is written with stock operators, m.encode is the stock
+    nn.TransformerEncoder that holds the parameters, m.classify a stock nn.Linear."""
+    y = m.classify(m.encode(m.embed(x)))
+    return y.sigmoid() if m.return_probs else y
+
+
 class AtenGraph(nn.Module):
     """``forward(x)`` of the wrapped model with stock ATen operators only (shares parameters and buffers with it)."""
 
     def __init__(self, model: nn.Module):
         super().__init__()
-        if not isinstance(model, (DetectionModel, RecognitionModel)):
-            raise TypeError("AtenGraph wraps ocrs_models_amd.DetectionModel / RecognitionModel")
+        if not isinstance(model, (DetectionModel, RecognitionModel, LayoutModel)):
+            raise TypeError("AtenGraph wraps ocrs_models_amd.DetectionModel / RecognitionModel / LayoutModel")
         self.model = model
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -72,6 +80,8 @@ class AtenGraph(nn.Module):
             raise RuntimeError("the ATen graph is the export / inference fallback: call .eval() first (training runs on the HIP path)")
         if isinstance(self.model, DetectionModel):
             return detection_forward(self.model, x)
+        if isinstance(self.model, LayoutModel):
+            return layout_forward(self.model, x)
         return recognition_forward(self.model, x)
 
     def state_dict(self, *a, **k):
@@ -86,6 +96,9 @@ def export_onnx(model: nn.Module, path: str, sample: torch.Tensor):
     graph = AtenGraph(model).eval()
     if isinstance(model, DetectionModel):
         names = dict(input_names=["image"], output_names=["mask"], dynamic_axes={"image": {0: "batch"}, "mask": {0: "batch"}})
+    elif isinstance(model, LayoutModel):  # train_layout.py:257-268
+        names = dict(input_names=["word_boxes"], output_names=["preds"], dynamic_axes={"word_boxes": {0: "batch", 1: "box"}, "preds": {0: "box"}},
+                     opset_version=16)
     else:
         names = dict(input_names=["line_image"], output_names=["chars"],
                      dynamic_axes={"line_image": {0: "batch", 3: "seq"}, "chars": {0: "out_seq"}})

@@ -26,6 +26,12 @@ class GraphedTrainStep:
     def __init__(self, model, optimizer, loss_fn, example_input: torch.Tensor, example_target: torch.Tensor, warmup: int = 3):
         if not getattr(optimizer, "capturable", False):
             raise RuntimeError("GraphedTrainStep needs ocrs_models_amd.optim.Adam(..., capturable=True)")
+        from .layout import LayoutModel
+
+        if isinstance(model, LayoutModel) and model.training and model.dropout_p > 0:
+            # (the dropout seed is a host scalar drawn per forward: a replay would repeat the captured step's masks)
+            raise RuntimeError("GraphedTrainStep cannot replay a training-mode LayoutModel with dropout on: every replay would repeat the same "
+                               "dropout masks; set model.dropout_p = 0 or run the step eagerly")
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
         self.x = example_input.clone()
         self.t = example_target.clone()

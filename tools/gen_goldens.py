@@ -207,16 +207,110 @@ def gen_op_kats(out, meta):
     out["pool/x"] = x.detach().numpy(); out["pool/y"] = y.detach().numpy(); out["pool/dx"] = x.grad.numpy()
 
 
+def gen_layout(R, out, states, meta):
+    """The reference's LayoutModel (models.py:340-406) and train_layout.py pieces on the name-keyed fill of tests/layout_ref.py, every dropout
+    probability set to 0 (the reference's RNG stream cannot be matched): forward, weighted_loss, backward, one and three Adam(lr=3e-4) steps,
+    LayoutAccuracyStats, test()'s loss-on-probabilities value; fp32, fp64 (the embedding stays fp32: its output is cast) and bf16 autocast."""
+    import ocrs_models.train_layout as tlay
+
+    import tests.golden_util as gu
+    from tests import layout_ref as lref
+
+    def put(out, prefix, tensor):  # (this group keeps only tensors of <= 512 elements in full: 74 tensors x 3 cases x 5 sets)
+        full_max, gu.FULL_MAX = gu.FULL_MAX, 512
+        try:
+            for k, v in summarize(tensor).items():
+                out[f"{prefix}|{k}"] = v
+        finally:
+            gu.FULL_MAX = full_max
+
+    def build(seed):
+        m = R.models.LayoutModel(return_probs=False, pos_embedding="sin")
+        m.load_state_dict(lref.fill_params(seed))
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.Dropout):
+                mod.p = 0.0
+            if isinstance(mod, torch.nn.MultiheadAttention):
+                mod.dropout = 0.0
+        return m.train()
+
+    for name, case in lref.CASES.items():
+        boxes, target = lref.make_inputs(case["N"], case["W"], case["seed"])
+        for tag in ("f32", "f64", "bf16") if name == "lay1" else ("f32", "f64"):  # (the autocast distance is recorded at (16, 50))
+            m = build(case["seed"])
+            loss_fn = tlay.weighted_loss()
+            if tag == "f64":
+                m, loss_fn = m.double(), loss_fn.double()
+            opt = torch.optim.Adam(m.parameters(), lr=3e-4)
+            for step in range(3 if tag == "f32" else 1):
+                if tag == "f64":
+                    pred = m.classify(m.encode(m.embed(boxes).double()))
+                    loss = loss_fn(pred, target.double())
+                else:
+                    with torch.autocast("cpu", dtype=torch.bfloat16, enabled=(tag == "bf16")):
+                        pred = m(boxes)
+                    pred = pred.float()
+                    loss = loss_fn(pred, target)
+                opt.zero_grad()
+                loss.backward()
+                if step == 0:
+                    put(out, f"{name}/{tag}/pred", pred.detach())
+                    out[f"{name}/{tag}/loss"] = np.asarray(loss.item())
+                    for k, p in m.named_parameters():
+                        put(out, f"{name}/{tag}/grad/{k}", p.grad.float() if tag == "bf16" else p.grad)
+                    if tag == "f32":
+                        put(out, f"{name}/f32/embed", m.embed(boxes))
+                        stats = tlay.LayoutAccuracyStats()
+                        prob = torch.clamp(pred.detach().sigmoid(), 0.0, 1.0)
+                        stats.update(prob, target)
+                        meta[f"{name}/stats"] = stats.stats_dict()
+                        meta[f"{name}/summary"] = stats.summary()
+                        out[f"{name}/f32/test_loss"] = np.asarray(loss_fn(pred.detach().sigmoid(), target).item())
+                    if tag == "f64":
+                        out[f"{name}/f64/test_loss"] = np.asarray(loss_fn(pred.detach().sigmoid(), target.double()).item())
+                opt.step()
+                if tag == "f32" and step in (0, 2):
+                    for k, v in m.state_dict().items():
+                        put(states, f"{name}/f32/state{step + 1}/{k}", v)
+        meta[name] = dict(case)
+    m = R.models.LayoutModel()
+    meta["state_keys"] = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    meta["n_params"] = sum(p.numel() for p in m.parameters())
+    meta["lr_scale_for_epoch"] = [[e, tlay.lr_scale_for_epoch(e)] for e in (0, 1, 10, 49, 50, 51, 200)]
+    meta["f1_score"] = [[p, r, tlay.f1_score(p, r)] for p, r in ((0.5, 0.5), (0.25, 0.75), (1.0, 0.1), (0.9, 0.8))]
+    none = torch.zeros(2, 3, 2)
+    st = tlay.LayoutAccuracyStats()
+    st.update(none, none)
+    meta["stats_no_positives_are_nan"] = [v != v for v in st.stats_dict().values()]
+
+
+def main_layout(args, R):
+    """regenerate tests/golden/layout.npz (predictions, losses, gradients), layout_state.npz (parameters after the Adam steps; a file of its
+    own keeps each below 1 MiB) and layout_meta.json only (the other goldens are not rewritten)"""
+    lay, states, meta = {}, {}, OrderedDict()
+    meta["torch"] = torch.__version__
+    gen_layout(R, lay, states, meta)
+    np.savez_compressed(os.path.join(args.out, "layout.npz"), **lay)
+    np.savez_compressed(os.path.join(args.out, "layout_state.npz"), **states)
+    with open(os.path.join(args.out, "layout_meta.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    for fn in ("layout.npz", "layout_state.npz", "layout_meta.json"):
+        print(fn, os.path.getsize(os.path.join(args.out, fn)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
+    ap.add_argument("--only", choices=["layout"], help="regenerate only the named group of goldens")
     args = ap.parse_args()
     from ref_import import import_reference
 
     R = import_reference(args.reference)
     torch.set_num_threads(8)
     os.makedirs(args.out, exist_ok=True)
+    if args.only == "layout":
+        return main_layout(args, R)
     meta = OrderedDict()
     meta["torch"] = torch.__version__
     det, rec, ops, det512 = {}, {}, {}, {}
@@ -233,6 +327,7 @@ def main():
         json.dump(meta, f, indent=1, ensure_ascii=False)
     for fn in ("det.npz", "rec.npz", "ops.npz", "det512.npz", "meta.json"):
         print(fn, os.path.getsize(os.path.join(args.out, fn)))
+    main_layout(args, R)
 
 
 if __name__ == "__main__":
