@@ -357,6 +357,22 @@ int ocrs_ctc_bwd_h16(const float* lp, const int* targets, const long long* in_le
                      const float* nll, const float* gout, float* grad, int T, int N, int C, int Lpad, int Smax, hipStream_t st);
 /* preds.argmax(-1) + ctc_greedy_decode_text's collapse (train_rec.py:52; datasets/util.py:147-177). */
 int ocrs_ctc_greedy_decode(const float* lp, const long long* in_len, int* amax, int* labels, int* lens, int T, int N, int C, hipStream_t st);
+/* levenshtein() of RecognitionAccuracyStats.update (train_rec.py:29-68), unit costs, one row pair per sample: a [N][pa], b [N][pb] int32 label
+ * rows, a_len / b_len [N] (clamped to [0, pitch]; entries beyond the length are ignored) -> dist [N] int32.  codes: optional int32[ncodes]
+ * class-to-character table (the host compares the characters of decode_text / ctc_greedy_decode_text, datasets/util.py:132-177, and an
+ * alphabet with a repeated character makes two ids equal): labels inside the table are compared through it, others as themselves; null
+ * (ncodes 0) = identity.  ws: ocrs_edit_distance_ws_bytes(N, pa) bytes.  One launch, no length limit, exact. */
+long ocrs_edit_distance_ws_bytes(int N, int pa);
+int ocrs_edit_distance(const int* a, const long long* a_len, int pa, const int* b, const long long* b_len, int pb, const int* codes, int ncodes,
+                       void* ws, int* dist, int N, hipStream_t st);
+/* RecognitionAccuracyStats.update (train_rec.py:29-68; decode_text / ctc_greedy_decode_text, datasets/util.py:132-177) entirely on the device:
+ * arg-max + collapse exactly as ocrs_ctc_greedy_decode, targets [N][Lpitch] compacted like decode_text (every entry <= 0 of the whole padded
+ * row dropped, tgt_len plays no part), edit distance, then state[0] += sum(dist) (char_errors), state[1] += sum(tgt_len) as given
+ * (total_chars).  state: int64[2], accumulated with integer atomics; dist [N] optional (null: not written); codes: optional int32[C] as above.
+ * ws: ocrs_ctc_cer_ws_bytes(T, N, Lpitch) bytes (0 = shape not supported).  Two launches, no copy, no synchronisation, no allocation. */
+long ocrs_ctc_cer_ws_bytes(int T, int N, int Lpitch);
+int ocrs_ctc_cer_update(const float* lp, const long long* in_len, const int* targets, const long long* tgt_len, const int* codes, void* ws,
+                        long long* state, int* dist, int T, int N, int C, int Lpitch, hipStream_t st);
 
 /* ------------------------------------------------------------------ input pipeline ----------- */
 /* transform_image (ocrs_models/datasets/util.py:27-35): out[i] = float(img_u8[i]) / 255 - 0.5; both pointers 16-byte aligned. */

@@ -4,6 +4,8 @@
 * ``round_up``, ``ctc_input_and_target_compatible``, ``collate_samples``           (train_rec.py:220-304)
 * ``RecognitionAccuracyStats``                                                     (train_rec.py:20-82) -- arg-max and the CTC collapse run
   on the GPU (``ocrs_ctc_greedy_decode``), only the already-collapsed label rows come back for the Levenshtein distance.
+* ``DeviceRecognitionAccuracyStats``, ``edit_distance_device``                       the same stats with nothing left on the host
+  (``ocrs_ctc_cer_update`` / ``ocrs_edit_distance``, csrc/rec_cer.hip): edit distances and both sums on the GPU, one host sync per read.
 * ``transform_image``                                                              (datasets/util.py:27-35)
 """
 from __future__ import annotations
@@ -152,6 +154,133 @@ class RecognitionAccuracyStats:
 
     def stats_dict(self) -> dict:
         return {"char_error_rate": self.char_error_rate()}
+
+
+def _lengths_to_device(dev, *lengths):
+    """per-sample lengths (lists or tensors) -> int64 device tensors; host ones go over together in ONE pinned non-blocking copy"""
+    ts = [torch.as_tensor(v, dtype=torch.int64).reshape(-1) for v in lengths]
+    host = [i for i, t in enumerate(ts) if not t.is_cuda]
+    if host:
+        up = torch.cat([ts[i] for i in host]).pin_memory().to(dev, non_blocking=True)
+        o = 0
+        for i in host:
+            n = ts[i].numel()
+            ts[i], o = up[o:o + n], o + n
+    return [t.to(dev).contiguous() for t in ts]
+
+
+def _labels_to_device(dev, x):
+    """(N, L) label rows -> contiguous int32 on the device (a host tensor: one pinned non-blocking copy)"""
+    x = torch.as_tensor(x)
+    if x.dim() != 2:
+        raise RuntimeError("label rows must be (N, L)")
+    if not x.is_cuda:
+        x = x.to(torch.int32).contiguous().pin_memory().to(dev, non_blocking=True)
+    return x.to(dev, torch.int32).contiguous()
+
+
+def alphabet_codes(alphabet):
+    """class id -> id of the first class with the same character (0 = blank stays 0): the table the device kernels compare through.  None
+    when all characters are distinct (identity)."""
+    first, codes = {}, [0]
+    for i, ch in enumerate(alphabet):
+        codes.append(first.setdefault(ch, i + 1))
+    return codes if len(first) < len(codes) - 1 else None
+
+
+def edit_distance_device(a, a_len, b, b_len, codes=None) -> torch.Tensor:
+    """Levenshtein distance (unit costs, exactly ``levenshtein``) of N pairs of label rows on the GPU: ``a`` (N, pa) and ``b`` (N, pb) int32
+    device tensors, the first ``a_len[i]`` / ``b_len[i]`` entries of row i count.  ``codes``: optional int32 device table, labels inside it
+    are compared through it (two ids with the same code are equal).  Returns int32 (N,) on the device; nothing is synchronised."""
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and isinstance(b, torch.Tensor) and b.is_cuda):
+        raise RuntimeError("ocrs_models_amd edit distances run on MI355X only (no CPU path)")
+    dev = a.device
+    a, b = _labels_to_device(dev, a), _labels_to_device(dev, b)
+    N, pa, pb = a.shape[0], a.shape[1], b.shape[1]
+    al, bl = _lengths_to_device(dev, a_len, b_len)
+    if b.shape[0] != N or al.numel() != N or bl.numel() != N:
+        raise RuntimeError(f"a, b and their lengths must have the same batch size {N}")
+    dist = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:
+        return dist
+    if codes is not None:
+        codes = codes.to(dev, torch.int32).contiguous()
+    ws = torch.empty(lib().edit_distance_ws_bytes(N, pa), dtype=torch.uint8, device=dev)
+    lib().edit_distance(ptr(a), ptr(al), pa, ptr(b), ptr(bl), pb, ptr(codes), 0 if codes is None else codes.numel(), ptr(ws), ptr(dist), N)
+    return dist
+
+
+class DeviceRecognitionAccuracyStats:
+    """``RecognitionAccuracyStats`` with nothing left on the host: arg-max, CTC collapse, target compaction, edit distances and both sums
+    run in ``ocrs_ctc_cer_update`` (two launches, no copy back, no synchronisation; capturable in a graph).  The counters live in ``state``,
+    one int64[2] device tensor (char_errors, total_chars) that a data-parallel caller can all-reduce; reading ``char_errors``,
+    ``total_chars``, ``char_error_rate()`` or ``stats_dict()`` is the one host synchronisation.
+
+    Both quirks of the host class are kept: every zero of the whole padded target row is dropped (``decode_text``) whatever
+    ``target_lengths`` says, and ``total_chars`` adds the lengths as given."""
+
+    device_resident = True  # train_rec.train_step hands such stats the uploaded targets and the length tensors
+
+    def __init__(self, alphabet=DEFAULT_ALPHABET):
+        self.alphabet = list(alphabet)
+        self._codes_host = alphabet_codes(self.alphabet)
+        self._codes = None
+        self.state = None   # created on the device of the first update
+        self.last_dist = None  # int32 (N,) edit distances of the latest update (device)
+
+    def update(self, targets, target_lengths, preds, pred_lengths):
+        """targets [batch, seq] (host or device); preds [seq, batch, class] log-probs on the GPU; lengths per sample (lists or tensors)."""
+        self.update_async(targets, target_lengths, preds, pred_lengths)
+
+    def update_async(self, targets, target_lengths, preds, pred_lengths):
+        """Queue the whole update on the current stream; the returned finisher has nothing left to do."""
+        if not (isinstance(preds, torch.Tensor) and preds.is_cuda):
+            raise RuntimeError("ocrs_models_amd accuracy stats run on MI355X only (no CPU path)")
+        assert len(target_lengths) == targets.size(0) and len(pred_lengths) == preds.size(1)
+        lp = preds.contiguous().float()
+        T, N, C = lp.shape
+        dev = lp.device
+        if C != len(self.alphabet) + 1:
+            raise RuntimeError(f"log-probs have {C} classes, the alphabet has {len(self.alphabet)} characters + blank")
+        if self.state is None:
+            self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+            if self._codes_host is not None:
+                self._codes = torch.tensor(self._codes_host, dtype=torch.int32).to(dev)
+        if N == 0:
+            return _nothing
+        tg = _labels_to_device(dev, targets)
+        il, tl = _lengths_to_device(dev, pred_lengths, target_lengths)
+        Lp = tg.shape[1]
+        nbytes = lib().ctc_cer_ws_bytes(T, N, Lp)
+        if nbytes <= 0:
+            raise RuntimeError(f"unsupported shape for the device accuracy stats: T={T}, N={N}, target pitch {Lp}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        dist = torch.empty(N, dtype=torch.int32, device=dev)
+        lib().ctc_cer_update(ptr(lp), ptr(il), ptr(tg), ptr(tl), ptr(self._codes), ptr(ws), ptr(self.state), ptr(dist), T, N, C, Lp)
+        self.last_dist = dist
+        return _nothing
+
+    def _read(self):
+        return (0, 0) if self.state is None else tuple(self.state.tolist())
+
+    @property
+    def char_errors(self) -> int:
+        return self._read()[0]
+
+    @property
+    def total_chars(self) -> int:
+        return self._read()[1]
+
+    def char_error_rate(self) -> float:
+        errors, total = self._read()
+        return errors / total
+
+    def stats_dict(self) -> dict:
+        return {"char_error_rate": self.char_error_rate()}
+
+
+def _nothing():
+    return None
 
 
 def round_up(val: int, unit: int) -> int:

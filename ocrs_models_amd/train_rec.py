@@ -10,7 +10,18 @@ import torch
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401  (shared with train_detection, train_rec.py:9)
 from .losses import CTCLoss
 from .optim import Adam, clip_grad_norm_
-from .text import RecognitionAccuracyStats
+from .text import DeviceRecognitionAccuracyStats, RecognitionAccuracyStats
+
+NAN_LOSS_MESSAGE = "Training produced invalid loss. Check input and target lengths are compatible with CTC loss"
+
+
+def make_stats(stats: str = "host"):
+    """"host": RecognitionAccuracyStats (edit distances in Python); "device": DeviceRecognitionAccuracyStats (everything on the GPU)."""
+    if stats == "host":
+        return RecognitionAccuracyStats()
+    if stats == "device":
+        return DeviceRecognitionAccuracyStats()
+    raise ValueError(f'stats must be "host" or "device", not {stats!r}')
 
 
 def make_optimizer(model, lr: float = 1e-3) -> Adam:
@@ -36,10 +47,12 @@ def train_step(model, optimizer, batch: dict, device, stats: RecognitionAccuracy
         pred_seq = model(img)
         batch_loss = loss_fn(pred_seq, text_seq, input_lengths, target_lengths)
     finish_stats = None
-    if stats is not None:  # device part now, host part (edit distances) after the backward pass has been queued
+    if getattr(stats, "device_resident", False):  # the whole update is queued here, on the targets already uploaded for the loss
+        finish_stats = stats.update_async(text_seq, target_lengths, pred_seq.detach(), input_lengths)
+    elif stats is not None:  # device part now, host part (edit distances) after the backward pass has been queued
         finish_stats = stats.update_async(batch["text_seq"], target_lengths.tolist(), pred_seq.detach(), input_lengths.tolist())
     if check_nan and math.isnan(batch_loss.item()):
-        raise Exception("Training produced invalid loss. Check input and target lengths are compatible with CTC loss")
+        raise Exception(NAN_LOSS_MESSAGE)
     batch_loss.backward()
     grad_norm = clip_grad_norm_(model.parameters(), max_norm=max_norm)
     optimizer.step()
@@ -48,14 +61,33 @@ def train_step(model, optimizer, batch: dict, device, stats: RecognitionAccuracy
     return batch_loss.detach(), grad_norm
 
 
-def train(epoch: int, device, dataloader, model, optimizer):
-    """Epoch loop with the reference's signature and return value (train_rec.py:85-160)."""
+def train(epoch: int, device, dataloader, model, optimizer, stats: str = "host"):
+    """Epoch loop with the reference's signature and return value (train_rec.py:85-160).
+
+    ``stats="device"`` (extension; the default is the reference's behaviour): the accuracy stats are a DeviceRecognitionAccuracyStats and the
+    per-step ``isnan(loss.item())`` becomes a device-side count of non-finite losses that is read, with the two means, in ONE host
+    synchronisation at the end of the epoch; the reference's exception is raised then.
+    """
     model.train()
-    stats = RecognitionAccuracyStats()
+    on_device = stats == "device"
+    stats = make_stats(stats)
     loss_fn = CTCLoss()
     mean_loss = torch.zeros((), device=device)
     total_norm = torch.zeros((), device=device)
     n = 0
+    if on_device:
+        bad = torch.zeros((), device=device)
+        for batch in dataloader:
+            loss, gn = train_step(model, optimizer, batch, device, stats, loss_fn, check_nan=False)
+            mean_loss += loss
+            total_norm += gn
+            bad += (~torch.isfinite(loss)).float()
+            n += 1
+        loss_sum, norm_sum, nbad = torch.stack([mean_loss, total_norm, bad]).tolist()  # the epoch's one host synchronisation
+        if nbad > 0:
+            raise Exception(NAN_LOSS_MESSAGE)
+        print(f"Mean grad norm {norm_sum / max(n, 1)}")
+        return loss_sum / max(n, 1), stats
     for batch in dataloader:
         loss, gn = train_step(model, optimizer, batch, device, stats, loss_fn)
         mean_loss += loss
@@ -65,8 +97,10 @@ def train(epoch: int, device, dataloader, model, optimizer):
     return float(mean_loss.item()) / max(n, 1), stats
 
 
-def test(device, dataloader, model, preview: int = 10):
+def test(device, dataloader, model, preview: int = 10, stats: str = "host"):
     """Validation loop with the reference's signature and return value (mean loss, RecognitionAccuracyStats) (train_rec.py:163-217).
+    ``stats="device"`` (extension): DeviceRecognitionAccuracyStats on the uploaded targets; with ``preview=0`` the mean loss read at the end is
+    the epoch's only host synchronisation.
 
     Like the reference's, it runs outside autocast (fp32 kernels) and in eval mode; the first batch's first ``preview`` predictions are
     printed next to their targets.
@@ -74,7 +108,8 @@ def test(device, dataloader, model, preview: int = 10):
     from .text import DEFAULT_ALPHABET, ctc_greedy_decode_text, decode_text
 
     model.eval()
-    stats = RecognitionAccuracyStats()
+    on_device = stats == "device"
+    stats = make_stats(stats)
     loss_fn = CTCLoss()
     mean_loss = torch.zeros((), device=device)
     n = 0
@@ -85,7 +120,10 @@ def test(device, dataloader, model, preview: int = 10):
             text_seq = batch["text_seq"].to(device, non_blocking=True)
             target_lengths = batch["text_len"]
             pred_seq = model(img)
-            stats.update(batch["text_seq"], target_lengths.tolist(), pred_seq, input_lengths.tolist())
+            if on_device:
+                stats.update(text_seq, target_lengths, pred_seq, input_lengths)
+            else:
+                stats.update(batch["text_seq"], target_lengths.tolist(), pred_seq, input_lengths.tolist())
             if batch_idx == 0 and preview:
                 amax = pred_seq[:, : min(preview, pred_seq.shape[1]), :].argmax(-1).T.cpu()
                 for i in range(amax.shape[0]):
