@@ -438,6 +438,35 @@ long ocrs_mask_metrics_ws_bytes(int B, int H, int W);
 int ocrs_mask_metrics(const void* pred, int pred_kind, const void* target, int target_kind, float threshold, int B, int H, int W, double* out, void* ws,
                       hipStream_t st);
 
+/* ------------------------------------------------------------------ page inference ------------ */
+/* From a page to recognition batches (csrc/ocr_infer.hip; Python: ocrs_models_amd/inference.py, which states the geometry rules).  Quads are
+ * [..][4][2] fp32 (x, y) in pixel-centre coordinates, 16-byte aligned.  Nothing here synchronises: counts are device-side with a capacity.
+ *
+ * binarize_mask + resize(.., InterpolationMode.NEAREST) (ocrs_models/eval_detection.py:54-57) in one launch: prob (B,1,h,w) fp32 ->
+ * out (B,1,H,W) uint8, 1 where prob > threshold; source index min(int(floorf(dst * ((float)in / out))), in - 1) per axis (F.interpolate). */
+int ocrs_binarize_resize_nearest(const float* prob, unsigned char* out, int B, int h, int w, int H, int W, float threshold, hipStream_t st);
+/* expand_quads (ocrs_models/postprocess.py:39-76; eval_detection.py:67): quads / out [B][cap][4][2]; counts (nullable) [B] int, rows past
+ * counts[b] are not written.  Every edge of the rectangle moves outward by dist (centre + axes c0->c1, c1->c2, half-extents + dist; corner k
+ * stays corner k); four equal corners are copied; a zero-area ring becomes the rectangle around its segment. */
+int ocrs_expand_quads(const float* quads, float* out, const int* counts, int B, long cap, float dist, hipStream_t st);
+/* Crop geometry of n = min(*count, cap) quads (count nullable: n = cap), the line-crop step of ocrs_models/datasets/hiertext.py:271-294 applied to
+ * word rectangles: plan [cap][8] int = {h, w, ow = line_output_width(h, w, output_height), packed element offset (crops start 16-byte aligned),
+ * horizontal-pass element offset (sum of h * ow), first sampler tile, position in (output width, index) order, the quad at this position};
+ * totals [805] int64 = {n, packed elements, horizontal-pass elements, sampler tiles, histogram of ow over 0..800}.  One workgroup. */
+int ocrs_crop_plan(const float* quads, const int* count, long cap, int output_height, int* plan, long long* totals, hipStream_t st);
+/* The crops themselves (hiertext.py:271-283 crops axis-aligned boxes on the host; here rotated rectangles): page (H, W) uint8, transform_image
+ * (datasets/util.py:27-35) fused, bilinear, border padding -> packed fp32, crop i (h_i, w_i) row-major at its plan offset.  max_tiles >= totals[3]
+ * sizes the launch, packed_floats >= totals[1] bounds the writes. */
+int ocrs_rectify_crops(const unsigned char* page, int H, int W, const float* quads, const int* plan, const long long* totals, long max_tiles, float* packed,
+                       long packed_floats, hipStream_t st);
+/* resize(line_img, [output_height, ow], antialias=True) (hiertext.py:288-294) of every packed crop + collate_samples' right padding with 0.0
+ * (train_rec.py:285-299): the crop at position r of the plan's order goes to row r % max_batch of chunk r / max_batch; chunks [nchunks][2] int64 =
+ * {element offset in out, Wpad}; pad columns are written too.  Same passes and weights as ocrs_resize_aa: bit-identical to it per crop.
+ * ws: ocrs_resize_aa_packed_ws_floats(totals[2]) floats. */
+long ocrs_resize_aa_packed_ws_floats(long hpass_floats);
+int ocrs_resize_aa_packed(const float* packed, const int* plan, const int* count, long cap, const long long* chunks, int nchunks, int max_batch, float* ws,
+                          long ws_floats, float* out, long out_floats, int output_height, hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

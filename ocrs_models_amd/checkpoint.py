@@ -28,3 +28,10 @@ def load_checkpoint(filename: str, model: nn.Module, optimizer: Optimizer, devic
     model.load_state_dict(checkpoint["model_state"])
     optimizer.load_state_dict(checkpoint["optimizer_state"])
     return checkpoint
+
+
+def load_model_state(filename: str, model: nn.Module, device: torch.device):
+    """The model half of ``load_checkpoint``, for evaluation (ocrs_models/eval_detection.py:29-30 loads ``model_state`` alone)."""
+    checkpoint = torch.load(filename, map_location=device)
+    model.load_state_dict(checkpoint["model_state"])
+    return checkpoint

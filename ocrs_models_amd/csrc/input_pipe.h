@@ -30,5 +30,12 @@ __device__ __forceinline__ float aa_w(const AaSpan& s, int j) {
     const float w = fmaxf(0.0f, 1.0f - fabsf(((float)(j + s.lo) - s.center + 0.5f) * s.inv));
     return s.total != 0.0f ? w / s.total : w;
 }
+// one output element of a pass: the span's weights against cnt inputs `stride` elements apart, src at the span's first input.  Every
+// antialiased resize (ocrs_resize_aa, ocrs_resize_aa_packed) sums through this one loop, which is what makes their results the same bits.
+__device__ __forceinline__ float aa_dot(const AaSpan& s, const float* __restrict__ src, size_t stride) {
+    float acc = 0.0f;
+    for (int j = 0; j < s.cnt; ++j) acc += aa_w(s, j) * src[(size_t)j * stride];
+    return acc;
+}
 
 }  // namespace

@@ -68,10 +68,7 @@ __global__ __launch_bounds__(256) void k_resize_aa_h(const float* __restrict__ i
     if (ox >= ow) return;
     const size_t rowi = ((size_t)blockIdx.z * h + blockIdx.y);
     const AaSpan s = aa_span(ox, w, scale);
-    const float* src = in + rowi * w + s.lo;
-    float acc = 0.0f;
-    for (int j = 0; j < s.cnt; ++j) acc += aa_w(s, j) * src[j];
-    out[rowi * ow + ox] = acc;
+    out[rowi * ow + ox] = aa_dot(s, in + rowi * w + s.lo, 1);
 }
 // in [planes][h][ow] -> out [planes][oh][ow]
 __global__ __launch_bounds__(256) void k_resize_aa_v(const float* __restrict__ in, float* __restrict__ out, int h, int oh, int ow, float scale) {
@@ -79,10 +76,7 @@ __global__ __launch_bounds__(256) void k_resize_aa_v(const float* __restrict__ i
     if (ox >= ow) return;
     const int oy = blockIdx.y;
     const AaSpan s = aa_span(oy, h, scale);  // uniform over the block: scalar registers
-    const float* src = in + ((size_t)blockIdx.z * h + s.lo) * ow + ox;
-    float acc = 0.0f;
-    for (int j = 0; j < s.cnt; ++j) acc += aa_w(s, j) * src[(size_t)j * ow];
-    out[((size_t)blockIdx.z * oh + oy) * ow + ox] = acc;
+    out[((size_t)blockIdx.z * oh + oy) * ow + ox] = aa_dot(s, in + ((size_t)blockIdx.z * h + s.lo) * ow + ox, ow);
 }
 
 }  // namespace

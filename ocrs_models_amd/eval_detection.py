@@ -1,0 +1,87 @@
+"""The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
+
+    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT]
+
+loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
+model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
+on the page).  With ``--rec-model`` the words are recognised too (``inference.ocr_page``'s stages) and printed, one JSON object per line.
+The image is read and the pictures are written with PIL on the host; that is not a hot path.
+"""
+from __future__ import annotations
+
+import json
+import sys
+import time
+from argparse import ArgumentParser
+
+import numpy as np
+import torch
+from PIL import Image, ImageDraw
+
+from . import inference
+from .checkpoint import load_model_state
+from .models import DetectionModel
+from .recognition import RecognitionModel
+from .text import DEFAULT_ALPHABET
+
+
+def _to_pil(img: torch.Tensor) -> Image.Image:
+    """float (H,W) in [0,1] -> 8-bit greyscale, as torchvision's to_pil_image does (mul(255), truncate)"""
+    return Image.fromarray(img.detach().mul(255).to(torch.uint8).cpu().numpy())
+
+
+def draw_quads(img_u8: np.ndarray, quads) -> Image.Image:
+    """postprocess.py:190-211: the quads' outlines in red, two pixels wide, on an RGB copy of the page"""
+    out = Image.fromarray(img_u8).convert("RGB")
+    draw = ImageDraw.Draw(out)
+    for quad in quads:
+        verts = [(float(x), float(y)) for x, y in quad]
+        for i, start in enumerate(verts):
+            draw.line((start, verts[(i + 1) % len(verts)]), fill="red", width=2)
+    return out
+
+
+def main(argv=None):
+    parser = ArgumentParser()
+    parser.add_argument("model")
+    parser.add_argument("image")
+    parser.add_argument("out_basename")
+    parser.add_argument("--rec-model", help="recognition checkpoint: also recognise the words and print them as JSON lines")
+    args = parser.parse_args(argv)
+
+    device = torch.device("cuda:0")
+    model = DetectionModel().to(device)
+    load_model_state(args.model, model, device)
+    model.eval()
+
+    page_h = np.asarray(Image.open(args.image).convert("L"), dtype=np.uint8)
+    page = torch.from_numpy(page_h.copy())[None].to(device)
+
+    img = inference.resize(inference.transform_image(page), inference.MASK_SIZE)
+    _to_pil((img[0] + 0.5).clamp(0, 1)).save(f"{args.out_basename}-input.png")
+
+    torch.cuda.synchronize()
+    start = time.time()
+    det = inference.detect_words(model, page)
+    torch.cuda.synchronize()
+    print(f"Predicted text in {time.time() - start:.2f}s", file=sys.stderr)
+
+    text_regions = page[0].float() / 255.0 * det["text_mask"].float()
+    _to_pil(text_regions).save(f"{args.out_basename}-text-regions.png")
+    _to_pil(det["probs"]).save(f"{args.out_basename}-text-probs.png")
+    quads = det["quads"].tolist()
+    draw_quads(page_h, quads).save(f"{args.out_basename}-text-words.png")
+
+    if args.rec_model and det["n"]:
+        rec = RecognitionModel(DEFAULT_ALPHABET).to(device)
+        load_model_state(args.rec_model, rec, device)
+        rec.eval()
+        plan = inference.crop_plan(det["quads"])
+        packed = inference.rectify_crops(page, det["quads"], plan)
+        texts = inference.recognize_crops(rec, inference.crops_to_batches(packed, plan))
+        for quad, text in zip(quads, texts):
+            print(json.dumps({"quad": quad, "text": text}))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,255 @@
+"""Page OCR on the GPU: from a page image to word quads, rectified word crops and recognised text.
+
+The detection half is the reference's evaluation script (ocrs_models/eval_detection.py:19-69): resize the page to ``MASK_SIZE``, eval
+forward, binarise, nearest-resize the mask back to the page, ``extract_cc_quads``, ``expand_quads(dist=SHRINK_DISTANCE)``.  The
+recognition half prepares every word rectangle the way the reference prepares line crops (datasets/hiertext.py:271-294: crop,
+``transform_image``, antialiased resize to 64 rows, width by aspect ratio) and pads them into batches as ``collate_samples`` does
+(train_rec.py:285-299), then runs the recogniser's eval forward and the greedy CTC decode of ``train_rec.test``.
+
+Every function takes and returns device tensors and has no CPU path; the pixel work is in csrc/ocr_infer.hip (C ABI section "page
+inference" of include/ocrs_hip.h).
+
+Host synchronisations per page (``ocr_page``), and there are no others:
+
+1. the component count (``extract_cc_quads_device`` reads N to slice the quads);
+2. the crop plan's totals (``CropPlan.host``: they size the packed crop buffer, the resize workspace and the batches);
+3. the decoded labels (every chunk's forward and decode are queued first, then the label copies are waited for).
+
+Geometry rules (restated for the tests in tests/ocr_ref.py).  Quad coordinates are pixel-centre indices: coordinate k is the centre of
+pixel k, as ``extract_cc_quads`` produces them.
+
+* Expansion.  For a rectangle with corners c0..c3: the centre (mean of the corners) and the unit axes along c0->c1 and c1->c2; ``dist`` is
+  added to each half-extent; corner k of the output corresponds to corner k of the input.  For any non-degenerate rectangle this is
+  shapely's mitred ``parallel_offset`` followed by ``minimum_rotated_rectangle`` (postprocess.py:39-65).  A zero-length ring (all four
+  corners equal) is returned unchanged, as in the reference.  A zero-area ring of non-zero length -- what the hull code returns as
+  ``[a, b, b, a]`` -- becomes the rectangle around the segment, ``2 * dist`` thick and ``dist`` longer at each end (the missing axis is the
+  normal of the other one; a quad whose first two sides are both empty is returned unchanged).  shapely is not installed where this is
+  built, so the vertex ORDER of the result and this degenerate case are UNPINNED in the sense of postprocess.py's docstring.
+* Crop frame.  The width axis u is the longer of the sides c0->c1 and c1->c2; on a tie the side with the larger |x| component (the first
+  one if that ties too).  The sign of u is chosen so that u.x > 0, or u.x == 0 and u.y > 0 (a point gets u = (1, 0)).  v = (-u.y, u.x) points
+  down the page and is never mirrored.  The origin is the corner with the smallest projections on u and v (the smallest sum of the two).
+  ``w_i = max(1, round(long))``, ``h_i = max(1, round(short))`` (round half to even).  Sample (y, x) sits at
+  ``origin + (x + 0.5) / w_i * long * u + (y + 0.5) / h_i * short * v``; sampling is bilinear on the ``transform_image`` values of the page,
+  with coordinates clamped to the page (border padding).  All of this is fp32 arithmetic.
+* Output width.  ``line_output_width(h_i, w_i, output_height)``, unchanged.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import torch
+
+from ._lib import lib, ptr
+from .input_pipeline import _need_cuda, resize, transform_image
+from .text import DEFAULT_ALPHABET, decode_text, greedy_decode_batch_async, round_up
+
+MASK_SIZE = (800, 600)   # train_detection.py's mask_size: the size the detection model is trained and evaluated at
+SHRINK_DISTANCE = 3.0    # datasets/util.py: how far text polygons are shrunk when training masks are made
+_OW_BINS = 801           # line_output_width() is in [10, 800]
+
+
+def binarize_resize(prob: torch.Tensor, size, threshold: float = 0.5) -> torch.Tensor:
+    """(B,1,h,w) or (h,w) fp32 probabilities -> uint8 0/1 mask (B,1,H,W) or (H,W): ``binarize_mask`` followed by
+    ``resize(.., size, InterpolationMode.NEAREST)`` (eval_detection.py:54-57) in one launch."""
+    _need_cuda(prob, "binarize_resize")
+    if prob.dtype != torch.float32 or not (prob.dim() == 2 or (prob.dim() == 4 and prob.shape[1] == 1)):
+        raise RuntimeError("binarize_resize: expected (B,1,h,w) or (h,w) float32 probabilities")
+    H, W = int(size[0]), int(size[1])
+    h, w = prob.shape[-2:]
+    B = prob.shape[0] if prob.dim() == 4 else 1
+    src = prob.contiguous()
+    out = torch.empty((B, 1, H, W) if prob.dim() == 4 else (H, W), dtype=torch.uint8, device=prob.device)
+    lib().binarize_resize_nearest(ptr(src), ptr(out), B, h, w, H, W, float(threshold))
+    return out
+
+
+def expand_quads(quads: torch.Tensor, dist: float, counts: torch.Tensor | None = None) -> torch.Tensor:
+    """``expand_quads`` (postprocess.py:68-76) on the device: (N,4,2) or (B,cap,4,2) fp32 -> the same shape, every rectangle's edges moved
+    outward by ``dist``.  ``counts`` (B,) int32 on the device: rows past ``counts[b]`` are returned as they came."""
+    _need_cuda(quads, "expand_quads")
+    if quads.dtype != torch.float32 or quads.dim() not in (3, 4) or tuple(quads.shape[-2:]) != (4, 2):
+        raise RuntimeError("expand_quads: expected (N,4,2) or (B,cap,4,2) float32 quads")
+    q = quads.contiguous()
+    B, cap = (1, q.shape[0]) if q.dim() == 3 else (q.shape[0], q.shape[1])
+    if counts is None:
+        out = torch.empty_like(q)
+    else:
+        _need_cuda(counts, "expand_quads")
+        if counts.dtype != torch.int32 or counts.numel() != B:
+            raise RuntimeError("expand_quads: counts must be int32 with one entry per batch row")
+        counts = counts.contiguous()
+        out = q.clone()
+    lib().expand_quads(ptr(q), ptr(out), ptr(counts), B, cap, float(dist))
+    return out
+
+
+def detect_words(model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE) -> dict:
+    """eval_detection.py:32-67 for one (1,H,W) uint8 page on the device -> ``probs`` (h,w), ``text_mask`` (H,W) uint8, ``quads`` (N,4,2) in
+    page coordinates and ``n``.  The model must be in eval mode.  One host synchronisation (the component count)."""
+    from .postprocess import extract_cc_quads_device
+
+    _need_cuda(page_u8, "detect_words")
+    if page_u8.dtype != torch.uint8 or page_u8.dim() != 3 or page_u8.shape[0] != 1:
+        raise RuntimeError("detect_words: expected a (1,H,W) uint8 page")
+    if model.training:
+        raise RuntimeError("detect_words: the model must be in eval mode (model.eval())")
+    H, W = page_u8.shape[-2:]
+    img = resize(transform_image(page_u8), size)
+    with torch.inference_mode():
+        probs = model(img.unsqueeze(0))[0, 0]
+    text_mask = binarize_resize(probs, (H, W), threshold)
+    quads = expand_quads(extract_cc_quads_device(text_mask), expand)
+    return {"probs": probs, "text_mask": text_mask, "quads": quads, "n": quads.shape[0]}
+
+
+@dataclass
+class CropPlan:
+    """Per-quad crop geometry on the device.  ``table`` (N,8) int32: h, w, output width, packed element offset, horizontal-pass element
+    offset, first sampler tile, position in (output width, index) order, the quad at that position.  ``totals`` (805,) int64: N, packed
+    elements, horizontal-pass elements, sampler tiles, then the histogram of output widths 0..800."""
+    table: torch.Tensor
+    totals: torch.Tensor
+    output_height: int
+    _host: list | None = field(default=None, repr=False)
+    _host_table: torch.Tensor | None = field(default=None, repr=False)
+
+    def host(self) -> list:
+        """``totals`` on the host: the one synchronisation between the plan and the crops (cached).  The table comes along in the same
+        wait, so the order (``host_perm``) costs no second one."""
+        if self._host is None:
+            tot = torch.empty(self.totals.shape, dtype=torch.int64, pin_memory=True)
+            tab = torch.empty(self.table.shape, dtype=torch.int32, pin_memory=True)
+            tot.copy_(self.totals, non_blocking=True)
+            tab.copy_(self.table, non_blocking=True)
+            torch.cuda.current_stream(self.totals.device).synchronize()
+            self._host, self._host_table = tot.tolist(), tab
+            if max(self._host[1:4]) >= 2 ** 31:
+                raise RuntimeError("crop_plan: the crops of this page do not fit 32-bit offsets")
+        return self._host
+
+    def host_perm(self) -> list[int]:
+        """Position of quad i in output-width order as a host list (from the copy ``host()`` made): ``sorted_results[perm[i]]`` is quad i's"""
+        self.host()
+        return self._host_table[:, 6].tolist()
+
+
+def crop_plan(quads: torch.Tensor, output_height: int = 64) -> CropPlan:
+    """Geometry of the crop of every quad (N,4,2) by the module's crop-frame rule, offsets into the packed buffers and the order by output
+    width.  One kernel, no synchronisation."""
+    _need_cuda(quads, "crop_plan")
+    if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
+        raise RuntimeError("crop_plan: expected (N,4,2) float32 quads")
+    q = quads.contiguous()
+    n = q.shape[0]
+    table = torch.empty(n, 8, dtype=torch.int32, device=q.device)
+    totals = torch.empty(4 + _OW_BINS, dtype=torch.int64, device=q.device)
+    lib().crop_plan(ptr(q), None, n, int(output_height), ptr(table), ptr(totals))
+    return CropPlan(table, totals, int(output_height))
+
+
+def rectify_crops(page_u8: torch.Tensor, quads: torch.Tensor, plan: CropPlan) -> torch.Tensor:
+    """Cut every rotated rectangle out of the (1,H,W) / (H,W) uint8 page into one packed fp32 buffer: crop i is (h_i, w_i) row-major at
+    ``plan.table[i, 3]``.  ``transform_image`` fused, bilinear, one launch for all crops."""
+    _need_cuda(page_u8, "rectify_crops")
+    _need_cuda(quads, "rectify_crops")
+    if page_u8.dtype != torch.uint8 or not (page_u8.dim() == 2 or (page_u8.dim() == 3 and page_u8.shape[0] == 1)):
+        raise RuntimeError("rectify_crops: expected a (1,H,W) or (H,W) uint8 page")
+    if quads.dtype != torch.float32 or quads.dim() != 3 or quads.shape[0] != plan.table.shape[0]:
+        raise RuntimeError("rectify_crops: quads must be the (N,4,2) float32 quads the plan was made from")
+    H, W = page_u8.shape[-2:]
+    _, packed_floats, _, tiles = plan.host()[:4]
+    page, q = page_u8.contiguous(), quads.contiguous()
+    packed = torch.empty(packed_floats, dtype=torch.float32, device=q.device)
+    lib().rectify_crops(ptr(page), H, W, ptr(q), ptr(plan.table), ptr(plan.totals), tiles, ptr(packed), packed_floats)
+    return packed
+
+
+def plan_chunks(hist, max_batch: int, width_unit: int) -> list[tuple[int, int, int]]:
+    """Host side of the batching rule: from the histogram of output widths, the chunks of the width-sorted crops as
+    (first position, crop count, Wpad = round_up(widest crop of the chunk, width_unit))."""
+    chunks, pos, total = [], 0, sum(hist)
+    edges = []  # cumulative counts per width, ascending
+    run = 0
+    for wd, c in enumerate(hist):
+        if c:
+            run += c
+            edges.append((run, wd))
+    k = 0
+    while pos < total:
+        cnt = min(max_batch, total - pos)
+        while edges[k][0] < pos + cnt:
+            k += 1
+        chunks.append((pos, cnt, round_up(edges[k][1], width_unit)))
+        pos += cnt
+    return chunks
+
+
+def crops_to_batches(packed: torch.Tensor, plan: CropPlan, max_batch: int = 256, width_unit: int = 64):
+    """Antialiased resize of every packed crop to ``output_height`` rows and ``line_output_width(h_i, w_i)`` columns, written straight into
+    right-padded (n,1,output_height,Wpad) batches (pad value 0.0, as ``collate_samples`` pads).  Crops are ordered by output width (ties by
+    quad index), a chunk holds at most ``max_batch`` crops and ``Wpad = round_up(widest crop of the chunk, width_unit)`` with ``text.round_up``,
+    the reference's, which gives an exact multiple a whole unit more (train_rec.py:220-225).
+
+    Returns ``(batches, image_widths, perm)``: the batch tensors, the (n,) int64 device widths of their crops, and the permutation back to
+    quad order as a host list (``plan.host_perm()``: ``sorted_results[perm[i]]`` belongs to quad i; it came with the totals, no wait of its own)."""
+    _need_cuda(packed, "crops_to_batches")
+    if packed.dtype != torch.float32 or max_batch < 1 or width_unit < 1:
+        raise RuntimeError("crops_to_batches: expected the float32 buffer of rectify_crops, max_batch >= 1 and width_unit >= 1")
+    tot = plan.host()
+    n, packed_floats, hpass = tot[0], tot[1], tot[2]
+    if packed.numel() < packed_floats:
+        raise RuntimeError("crops_to_batches: the packed buffer is smaller than the plan says")
+    OH = plan.output_height
+    dev = packed.device
+    chunks = plan_chunks(tot[4:], max_batch, width_unit)
+    offs, off = [], 0
+    for _, cnt, wpad in chunks:
+        offs += [off, wpad]
+        off += cnt * OH * wpad
+    out = torch.empty(off, dtype=torch.float32, device=dev)
+    batches = [out[o:o + cnt * OH * wpad].view(cnt, 1, OH, wpad) for (_, cnt, wpad), o in zip(chunks, offs[::2])]
+    if n:
+        L = lib()
+        chunks_d = torch.tensor(offs, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        ws_floats = L.resize_aa_packed_ws_floats(hpass)
+        ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+        L.resize_aa_packed(ptr(packed), ptr(plan.table), None, n, ptr(chunks_d), len(chunks), int(max_batch), ptr(ws), ws_floats, ptr(out), off, OH)
+    widths_sorted = plan.table[:, 2][plan.table[:, 7].long()].long() if n else torch.empty(0, dtype=torch.int64, device=dev)
+    image_widths = [widths_sorted[p:p + cnt] for p, cnt, _ in chunks]
+    return batches, image_widths, plan.host_perm()
+
+
+def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET) -> list[str]:
+    """Eval forward of the recogniser per batch with ``input_lengths = image_width // 4`` (as ``train_rec.test``) and the device greedy
+    decode.  ``batches`` is what ``crops_to_batches`` returned: ``(batch tensors, image widths, perm)``.  Returns the strings in quad order.
+    Every chunk's forward and decode are queued before the first label copy is waited for."""
+    batches, image_widths, perm = batches
+    for b in batches:
+        _need_cuda(b, "recognize_crops")
+    if rec_model.training:
+        raise RuntimeError("recognize_crops: the model must be in eval mode (model.eval())")
+    alphabet = list(alphabet)
+    handles = []
+    with torch.inference_mode():
+        for img, iw in zip(batches, image_widths):
+            handles.append(greedy_decode_batch_async(rec_model(img), iw.div(4, rounding_mode="floor")))
+    texts = [decode_text(row, alphabet) for h in handles for row in h.result()]
+    return [texts[p] for p in perm]
+
+
+def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
+             output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET) -> list[dict]:
+    """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
+    A page without components returns ``[]`` without launching the recogniser."""
+    det = detect_words(det_model, page_u8, size, threshold, expand)
+    if det["n"] == 0:
+        return []
+    quads = det["quads"]
+    plan = crop_plan(quads, output_height)
+    packed = rectify_crops(page_u8, quads, plan)
+    batches = crops_to_batches(packed, plan, max_batch, width_unit)
+    # the quads travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of their own)
+    quads_h = torch.empty(quads.shape, dtype=torch.float32, pin_memory=True)
+    quads_h.copy_(quads, non_blocking=True)
+    texts = recognize_crops(rec_model, batches, alphabet)
+    return [{"quad": q, "text": t} for q, t in zip(quads_h.tolist(), texts)]

@@ -18,6 +18,8 @@ The same contract on the GPU (csrc/postprocess.hip, C ABI ``ocrs_cc_quads`` / ``
   sync -- what ``train_detection.test(..., metrics_fn="device")`` uses.
 * ``extract_cc_quads_device(mask)``: the quads of one device mask, on the device (one sync, to read the count).
 * ``box_match_metrics_device(pred_quads, target_quads)``: ``box_match_metrics`` of two device quad sets.
+* ``expand_quads_device(quads, dist)``: ``expand_quads`` (postprocess.py:39-76) of a device quad set (csrc/ocr_infer.hip; the rule, and what
+  of it is UNPINNED without shapely, is in ocrs_models_amd/inference.py's docstring).
 
 Components, their numbering and the hull vertex sequence are identical to the host's (integer work); the calipers, clipping and areas
 repeat the host's fp64 operations in the host's order, so quads agree to rounding and the four counts agree exactly in practice (DESIGN.md
@@ -215,6 +217,14 @@ def extract_cc_quads_device(mask: torch.Tensor, threshold: float = 0.5) -> torch
     quads = torch.empty(L.cc_quads_capacity(H, W), 4, 2, dtype=torch.float32, device=m.device)
     L.cc_quads(ptr(m), kind, float(threshold), 1, H, W, ptr(n), ptr(quads), None, ptr(ws))
     return quads[: int(n.item())]
+
+
+def expand_quads_device(quads: torch.Tensor, dist: float, counts: torch.Tensor | None = None) -> torch.Tensor:
+    """``expand_quads`` on the GPU: (N,4,2) or (B,cap,4,2) fp32 device quads -> the same shape, every edge moved outward by ``dist``
+    (``inference.expand_quads``; no host synchronisation)."""
+    from .inference import expand_quads
+
+    return expand_quads(quads, dist, counts)
 
 
 def label_components_device(masks: torch.Tensor, threshold: float = 0.5) -> tuple[torch.Tensor, torch.Tensor]:
