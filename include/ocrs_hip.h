@@ -519,6 +519,16 @@ int ocrs_layout_loss(const float* pred, const float* target, float pos_weight, i
 /* precision_recall of both classes (train_layout.py:24-35, 55-63: int64 counts divided as fp32, 0 / 0 = NaN) added to the running sums on the
  * device: sums [5] fp64 = line-start precision | recall | line-end precision | recall | number of updates. */
 int ocrs_layout_stats_update(const long long* counts, double* sums, hipStream_t st);
+/* One batch of WebLayout.__getitem__ + F.pad + default_collate (ocrs_models/datasets/web_layout.py:76-186; csrc/layout_data.hip) from the
+ * dataset parsed once into device memory: coords [T][4] fp64 (left, top, right, bottom of every word, pages back to back in paragraph ->
+ * word order), para [T] = the paragraph index of a word within its page, page_off [P + 1] = first word of a page, viewport [P][2] =
+ * int(width), int(height).  pages [N] in 0 .. P-1, jitter [N][2] fp64 (x, y; web_layout.py:92-95) -> boxes [N][W][4], labels [N][W][2] fp32
+ * (line_start, line_end).  Per coordinate c * 1.0 + jitter, then c / viewport - 0.5 if normalize != 0, each a single fp64 operation, rounded
+ * to fp32 once (torch.Tensor(words), web_layout.py:174).  A label is set when the word has no previous / next word in its paragraph or
+ * intervals_overlap (datasets/util.py:197-204) of the two transformed vertical intervals is false; the neighbour of slot W - 1 is word W of
+ * the page (web_layout.py:177-184 truncates after labelling).  Slots past the page's word count are 0.0.  Every element is written. */
+int ocrs_weblayout_batch(const double* coords, const int* para, const long long* page_off, const double* viewport, int P, const int* pages,
+                         const double* jitter, int N, int W, int normalize, float* boxes, float* labels, hipStream_t st);
 
 /* ------------------------------------------------------------------ optimiser ---------------- */
 /* table [nt][5] int64 {param, grad, exp_avg, exp_avg_sq, numel}; chunks [nchunks][2] int32 {tensor, chunk of ocrs_opt_chunk()}. */

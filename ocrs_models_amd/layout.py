@@ -227,14 +227,24 @@ class _LayoutRun:
         L, P, R, N, W, p, seed = self.L, self.P, self.R, self.N, self.W, self.p, self.seed
         # flat gradient buffer in backward-completion order, as the other two models keep it (data-parallel buckets = contiguous ranges)
         flat = torch.zeros(sum(q.numel() for q in P.values()), dtype=torch.float32, device=self.dev)
-        G, off = {}, 0
+        G, off, stage_end = {}, 0, {}
         for stage in _ORDER:
             for k in self.names:
                 if k.startswith(stage) and k not in G:
                     n = P[k].numel()
                     G[k] = flat[off:off + n].view_as(P[k])
                     off += n
+            stage_end[stage] = off
         assert off == flat.numel(), "parameter ordering table is incomplete"
+        bucketer = getattr(self.mod, "_grad_bucketer", None)
+        done = [0]
+
+        def stage_done(stage):
+            # called behind the stage's last gradient launch: every launch writes its own outputs (k_lay_colsum owns its partials, no deferral
+            # window), so the range is final in stream order and a data-parallel bucket may go out
+            if bucketer is not None and stage_end[stage] > done[0]:
+                bucketer.ready(flat, done[0], stage_end[stage])
+            done[0] = max(done[0], stage_end[stage])
         g = g.contiguous().float()
         if self.out is not None:  # return_probs: d sigmoid
             g = g * self.out * (1 - self.out)
@@ -242,6 +252,7 @@ class _LayoutRun:
         L.layout_head_grad_in(ptr(g), ptr(dlog), LDL, R)
         self.wgrad(dlog, LDL, N_CLASSES, self.xf, D_MODEL, G["classify.weight"])
         self.bias_grad(dlog, LDL, N_CLASSES, G["classify.bias"])
+        stage_done("classify.")
         dy1, dy2 = self.linear_dgrad(dlog, LDL, P["classify.weight"]), None
         self.xf = None
         lnws = self.empty(L.layout_ln_bwd_ws_floats(R))
@@ -253,27 +264,35 @@ class _LayoutRun:
             L.layout_ln_bwd(ptr(dy1), ptr(dy2), ptr(A["x1"]), ptr(A["f"]), ptr(A["st2"]), ptr(P[pre + "norm2.weight"]), ptr(ds2),
                             ptr(df) if p > 0 else None, ptr(G[pre + "norm2.weight"]), ptr(G[pre + "norm2.bias"]), ptr(lnws), R, p, seed,
                             site_code(i, SITE_FF))
+            stage_done(pre + "norm2.")
             self.wgrad(df, D_MODEL, D_MODEL, A["h"], D_FF, G[pre + "linear2.weight"])
             self.bias_grad(df, D_MODEL, D_MODEL, G[pre + "linear2.bias"])
+            stage_done(pre + "linear2.")
             dh = self.linear_dgrad(df, D_MODEL, P[pre + "linear2.weight"])
             L.layout_relu_drop_bwd(ptr(dh), ptr(A["h"]), ptr(dh), R * D_FF, p)
             self.wgrad(dh, D_FF, D_FF, A["x1"], D_MODEL, G[pre + "linear1.weight"])
             self.bias_grad(dh, D_FF, D_FF, G[pre + "linear1.bias"])
+            stage_done(pre + "linear1.")
             dx1 = self.linear_dgrad(dh, D_FF, P[pre + "linear1.weight"])
             ds1 = self.empty(R, D_MODEL)
             da = self.empty(R, D_MODEL) if p > 0 else ds1
             L.layout_ln_bwd(ptr(ds2), ptr(dx1), ptr(A["x"]), ptr(A["a"]), ptr(A["st1"]), ptr(P[pre + "norm1.weight"]), ptr(ds1),
                             ptr(da) if p > 0 else None, ptr(G[pre + "norm1.weight"]), ptr(G[pre + "norm1.bias"]), ptr(lnws), R, p, seed,
                             site_code(i, SITE_PROJ))
+            stage_done(pre + "norm1.")
             self.wgrad(da, D_MODEL, D_MODEL, A["att"], D_MODEL, G[pre + "self_attn.out_proj.weight"])
             self.bias_grad(da, D_MODEL, D_MODEL, G[pre + "self_attn.out_proj.bias"])
+            stage_done(pre + "self_attn.out_proj.")
             datt = self.linear_dgrad(da, D_MODEL, P[pre + "self_attn.out_proj.weight"])
             dqkv = self.empty(R, 3 * D_MODEL)
             L.layout_attn_bwd(ptr(A["qkv"]), ptr(datt), ptr(dqkv), N, W, p, seed, site_code(i, SITE_ATTN))
             self.wgrad(dqkv, 3 * D_MODEL, 3 * D_MODEL, A["x"], D_MODEL, G[pre + "self_attn.in_proj_weight"])
             self.bias_grad(dqkv, 3 * D_MODEL, 3 * D_MODEL, G[pre + "self_attn.in_proj_bias"])
+            stage_done(pre + "self_attn.in_proj_")
             if i > 0:  # (the embedding has no parameters and the boxes need no gradient)
                 dy1, dy2 = ds1, self.linear_dgrad(dqkv, 3 * D_MODEL, P[pre + "self_attn.in_proj_weight"])
+        if bucketer is not None:
+            bucketer.finish(flat)
         self.flat = flat
         return [G[k] for k in self.names]
 

@@ -1,13 +1,17 @@
 """Layout training and validation, the bodies of the reference's ``train()`` / ``test()`` loops (ocrs_models/train_layout.py:15-183):
 forward, weighted BCE-with-logits, backward, Adam step, accuracy statistics -- with the loss and the statistics kept on the device (one host
-synchronisation per epoch instead of three per batch).  No dataset reader, command line or experiment tracking here."""
+synchronisation per epoch instead of three per batch), and its ``main()`` (train_layout.py:186-319) on the device-resident dataset of
+``ocrs_models_amd.datasets``: ``python -m ocrs_models_amd.train_layout DATA_DIR``.  No experiment tracking here."""
 from __future__ import annotations
+
+from argparse import ArgumentParser
 
 import torch
 from torch import nn
 
 from ._lib import lib, ptr
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401  (train_layout.py:12)
+from .datasets import DeviceWebLayoutLoader, WebLayout
 from .layout import LayoutModel, loss_workspace  # noqa: F401
 from .optim import Adam
 
@@ -173,3 +177,77 @@ def test(device, dataloader, model) -> tuple[float, LayoutAccuracyStats]:
             total += loss
             n += 1
     return float(total.item()) / n, stats
+
+
+N_WORDS = 500    # train_layout.py:203-205: words used from each page; inputs and targets are padded to this length
+BATCH_SIZE = 64  # train_layout.py:218
+CHECKPOINT_FILE = "text-layout-checkpoint.pt"
+
+
+def main(argv=None):
+    """The reference's training script (train_layout.py:186-319) without wandb: same arguments, constants, print lines and checkpoint file."""
+    parser = ArgumentParser(description="Train text layout model.")
+    parser.add_argument("data_dir")
+    parser.add_argument("--checkpoint", type=str, help="Model checkpoint to load")
+    parser.add_argument("--export", type=str, help="Export model to ONNX format")
+    parser.add_argument("--max-epochs", type=int, help="Maximum number of epochs to train for")
+    parser.add_argument("--validate-only", action="store_true", help="Run validation only")
+    args = parser.parse_args(argv)
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("ocrs_models_amd.train_layout runs on MI355X only (no CPU path)")
+    torch.manual_seed(1234)
+    normalize_coords = False
+    max_jitter = 10  # max random translation of the training pages
+
+    device = torch.device("cuda")
+    model = LayoutModel(return_probs=False, pos_embedding="sin").to(device)
+    optimizer = make_optimizer(model)
+    scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lr_scale_for_epoch)
+    train_dataset = WebLayout(args.data_dir, max_jitter=max_jitter, normalize_coords=normalize_coords, randomize=True, padded_size=N_WORDS,
+                              train=True, device=device)
+    train_dataloader = DeviceWebLayoutLoader(train_dataset, batch_size=BATCH_SIZE, shuffle=True)
+    val_dataset = WebLayout(args.data_dir, normalize_coords=normalize_coords, randomize=False, padded_size=N_WORDS, train=False, device=device)
+    val_dataloader = DeviceWebLayoutLoader(val_dataset, batch_size=BATCH_SIZE, shuffle=True)
+
+    total_params = sum(p.numel() for p in model.parameters() if p.requires_grad)
+    print(f"Model param count {total_params}")
+
+    epoch = 0
+    if args.checkpoint:
+        checkpoint = load_checkpoint(args.checkpoint, model, optimizer, device)
+        epoch = checkpoint["epoch"]
+
+    if args.export:
+        from .export import export_onnx
+
+        dummy_input, dummy_target = next(iter(train_dataloader))
+        export_onnx(model, args.export, dummy_input[0:1])
+        return
+
+    if args.validate_only:
+        val_loss, val_stats = test(device, val_dataloader, model)
+        print(f"Epoch {epoch} val stats: {val_stats.summary()}")
+        return
+
+    best_val_loss = float("inf")
+    while args.max_epochs is None or epoch < args.max_epochs:
+        train_loss, train_stats = train(epoch, device, train_dataloader, model, optimizer)
+        val_loss, val_stats = test(device, val_dataloader, model)
+        lr = optimizer.state_dict()["param_groups"][0]["lr"]
+
+        print(f"Epoch {epoch} train loss {train_loss} val loss {val_loss}")
+        print(f"Epoch {epoch} train stats: {train_stats.summary()}")
+        print(f"Epoch {epoch} val stats: {val_stats.summary()}")
+        print(f"Epoch {epoch} lr {lr}")
+
+        if val_loss < best_val_loss:
+            best_val_loss = val_loss
+            save_checkpoint(CHECKPOINT_FILE, model, optimizer, epoch=epoch)
+
+        scheduler.step()
+        epoch += 1
+
+
+if __name__ == "__main__":
+    main()
