@@ -529,6 +529,23 @@ int ocrs_layout_stats_update(const long long* counts, double* sums, hipStream_t 
  * the page (web_layout.py:177-184 truncates after labelling).  Slots past the page's word count are 0.0.  Every element is written. */
 int ocrs_weblayout_batch(const double* coords, const int* para, const long long* page_off, const double* viewport, int P, const int* pages,
                          const double* jitter, int N, int W, int normalize, float* boxes, float* labels, hipStream_t st);
+/* Recognition training data (csrc/line_data.hip; Python: ocrs_models_amd/datasets.py HierTextRecognition / DeviceLineLoader).
+ * ocrs_line_mask: generate_mask(w, h, [poly], shrink_dist=0.0) of ocrs_models/datasets/util.py:78-110 as called by hiertext.py:262, i.e. PIL's
+ * ImageDraw.polygon(poly, fill="white", outline=None) on a mode "1" image, bit for bit, for n polygons in one launch.  vertices [..][2] int32
+ * (x, y), polygon i = vertex_counts[i] (2 .. 512) vertices from vertex_offs[i], coordinates within +-65535 (the host checks both); sizes [n][2] int32 (h, w) of its canvas; its 0/1 byte mask
+ * (h * w, row-major) is written at out_u8 + out_offs[i].  max_h >= every h (it sizes the grid).  Self-intersecting polygons get whatever the
+ * restated scanline rules give (tests/hiertext_ref.py), and so do polygons that pass twice through one vertex; parity with PIL (12.2.0) is
+ * pinned for simple polygons only (DESIGN.md section 10 says on how many). */
+int ocrs_line_mask(const int* vertices, const long long* vertex_offs, const int* vertex_counts, const int* sizes, const long long* out_offs,
+                   void* out_u8, int n, int max_h, hipStream_t st);
+/* One batch of HierTextRecognition._get_line_image + generate_mask (hiertext.py:256-263) from the line store in device memory: pixels_u8 = the
+ * un-resized grey crops back to back, line l = sizes[l] (h, w) bytes from pixel_offs[l], its polygon as above (vertices relative to the crop's
+ * origin); N lines.  For b < B, line indices[b] (0 .. N-1) is copied to out_crops_u8 + batch_offs[3 * b] and its mask rasterised at
+ * out_masks_u8 + batch_offs[3 * b]: batch_offs is the [B][3] offset table of ocrs_augment_lines, which runs next on these two buffers.
+ * max_h >= the height of every line of the batch. */
+int ocrs_line_batch(const void* pixels_u8, const long long* pixel_offs, const int* sizes, const int* vertices, const long long* vertex_offs,
+                    const int* vertex_counts, int N, const int* indices, int B, int max_h, const long long* batch_offs, void* out_crops_u8,
+                    void* out_masks_u8, hipStream_t st);
 
 /* ------------------------------------------------------------------ optimiser ---------------- */
 /* table [nt][5] int64 {param, grad, exp_avg, exp_avg_sq, numel}; chunks [nchunks][2] int32 {tensor, chunk of ocrs_opt_chunk()}. */

@@ -291,6 +291,45 @@ def detection_batch(images, masks, device, augment: bool, dtype: torch.dtype = t
     return {"image": image, "text_mask": text_mask}
 
 
+def _line_batch_plan(text_seqs, params: list[AugParams], output_height: int, dtype, device):
+    """collate_samples' metadata rules on the resized widths (round_up quirk, bucket over every sample, infeasible-sample drop) ->
+    (empty (n, 1, output_height, wmax) image on ``device``, {"text_seq", "text_len", "image_width"} host tensors, kept positions)."""
+    ows = [line_output_width(p.out_size[0], p.out_size[1], output_height) for p in params]
+    wmax = round_up(max(ows), 256)
+    lmax = round_up(max(t.shape[0] for t in text_seqs), 64)
+    keep = [k for k, t in enumerate(text_seqs) if ctc_input_and_target_compatible(ows[k] // 4, t)]
+    n = len(keep)
+    text = torch.zeros(n, lmax, dtype=torch.int32)
+    tl = torch.zeros(n, dtype=torch.int64)
+    iw = torch.zeros(n, dtype=torch.int64)
+    for i, k in enumerate(keep):
+        L = text_seqs[k].shape[0]
+        text[i, :L] = text_seqs[k]
+        tl[i], iw[i] = L, ows[k]
+    image = torch.empty(n, 1, output_height, wmax, dtype=dtype, device=device)
+    return image, {"text_seq": text, "text_len": tl, "image_width": iw}, keep
+
+
+def _line_records(kp: list[AugParams], output_height: int):
+    """The kept samples' device records and the [n][3] offsets (source, intermediate, horizontal pass) of ocrs_augment_lines."""
+    ows = [line_output_width(p.out_size[0], p.out_size[1], output_height) for p in kp]
+    rec = _records(kp, line=True, widths=ows)
+    src = np.array([p.size[0] * p.size[1] for p in kp], dtype=np.int64)
+    inter = np.array([p.out_size[0] * p.out_size[1] for p in kp], dtype=np.int64)
+    hp = np.array([p.out_size[0] * w for p, w in zip(kp, ows)], dtype=np.int64)
+    return rec, np.stack([np.cumsum(a) - a for a in (src, inter, hp)], axis=1)
+
+
+def _launch_lines(crops_d, masks_d, offs_d, rec_d, kp: list[AugParams], image, output_height: int, kind: int, augment: bool):
+    """The five launches of ocrs_augment_lines on packed device crops (and masks) into ``image``."""
+    inter = sum(p.out_size[0] * p.out_size[1] for p in kp)
+    hp = sum(p.out_size[0] * line_output_width(p.out_size[0], p.out_size[1], output_height) for p in kp)
+    n = len(kp)
+    ws = torch.empty(lib().augment_lines_ws_floats(n, inter, hp), dtype=torch.float32, device=image.device)
+    lib().augment_lines(ptr(crops_d), ptr(masks_d), ptr(offs_d), ptr(rec_d), ptr(ws), inter, ptr(image), n, max(p.out_size[0] for p in kp),
+                        max(p.out_size[1] for p in kp), output_height, image.shape[-1], kind, int(augment), _DT[image.dtype])
+
+
 def collate_lines(samples: list[dict], device, augment: bool, output_height: int = 64, dtype: torch.dtype = torch.float32,
                   generator: torch.Generator | None = None, rng: random.Random | None = None, params: list[AugParams] | None = None) -> dict:
     """List of {'image': (1,h,w) uint8 or fp32 un-resized line crop, 'text_seq': (L,) int32, optional 'mask': (1,h,w) uint8/bool 0/1}
@@ -307,22 +346,8 @@ def collate_lines(samples: list[dict], device, augment: bool, output_height: int
         params = sample_line_params(sizes, generator, rng) if augment else [AugParams(-1, s, s) for s in sizes]
     if [tuple(p.size) for p in params] != sizes:
         raise RuntimeError("collate_lines: params do not match the image sizes")
-    ows = [line_output_width(p.out_size[0], p.out_size[1], output_height) for p in params]
-
-    # metadata: collate_samples' rules on the resized widths (round_up quirk, bucket over every sample, infeasible-sample drop)
-    wmax = round_up(max(ows), 256)
-    lmax = round_up(max(s["text_seq"].shape[0] for s in samples), 64)
-    keep = [k for k, s in enumerate(samples) if ctc_input_and_target_compatible(ows[k] // 4, s["text_seq"])]
-    n = len(keep)
-    text = torch.zeros(n, lmax, dtype=torch.int32)
-    tl = torch.zeros(n, dtype=torch.int64)
-    iw = torch.zeros(n, dtype=torch.int64)
-    for i, k in enumerate(keep):
-        L = samples[k]["text_seq"].shape[0]
-        text[i, :L] = samples[k]["text_seq"]
-        tl[i], iw[i] = L, ows[k]
-    image = torch.empty(n, 1, output_height, wmax, dtype=dtype, device=device)
-    if n:
+    image, meta, keep = _line_batch_plan([s["text_seq"] for s in samples], params, output_height, dtype, device)
+    if keep:
         ks = [samples[k] for k in keep]
         kinds = {s["image"].dtype for s in ks}
         if kinds not in ({torch.uint8}, {torch.float32}):
@@ -332,20 +357,13 @@ def collate_lines(samples: list[dict], device, augment: bool, output_height: int
             raise RuntimeError("collate_lines: give a mask for every sample or for none")
         if any(has_mask) and any(tuple(s["mask"].shape) != tuple(s["image"].shape) for s in ks):
             raise RuntimeError("collate_lines: a mask must have its image's shape")
-        kp = [params[k] for k in keep]
-        rec = _records(kp, line=True, widths=[ows[k] for k in keep])
-        src = np.array([p.size[0] * p.size[1] for p in kp], dtype=np.int64)
-        inter = np.array([p.out_size[0] * p.out_size[1] for p in kp], dtype=np.int64)
-        hp = np.array([p.out_size[0] * ows[k] for p, k in zip(kp, keep)], dtype=np.int64)
-        offs = np.stack([np.cumsum(a) - a for a in (src, inter, hp)], axis=1)
+        rec, offs = _line_records([params[k] for k in keep], output_height)
         if all(has_mask) and any(s["mask"].dtype not in (torch.uint8, torch.bool) for s in ks):
             raise RuntimeError("collate_lines: masks must be uint8 or bool")
         parts = [rec, offs, [s["image"] for s in ks]] + ([[s["mask"] for s in ks]] if all(has_mask) else [])
         up = _upload(parts, device, "collate_lines")
         rec_d, offs_d, crops_d = up[:3]
         masks_d = up[3] if len(up) > 3 else None
-        ws = torch.empty(lib().augment_lines_ws_floats(n, int(inter.sum()), int(hp.sum())), dtype=torch.float32, device=device)
-        lib().augment_lines(ptr(crops_d), ptr(masks_d), ptr(offs_d), ptr(rec_d), ptr(ws), int(inter.sum()), ptr(image), n,
-                            max(p.out_size[0] for p in kp), max(p.out_size[1] for p in kp), output_height, wmax,
-                            0 if torch.uint8 in kinds else 1, int(augment), _DT[dtype])
-    return {"image": image, "text_seq": text, "text_len": tl, "image_width": iw}
+        _launch_lines(crops_d, masks_d, offs_d, rec_d, [params[k] for k in keep], image, output_height, 0 if torch.uint8 in kinds else 1,
+                      augment)
+    return {"image": image, **meta}

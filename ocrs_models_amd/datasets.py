@@ -1,4 +1,6 @@
-"""The layout model's dataset (ocrs_models/datasets/web_layout.py), resident on the device.
+"""The device-resident datasets: the layout model's WebLayout and the recognition model's HierTextRecognition (further down).
+
+The layout model's dataset (ocrs_models/datasets/web_layout.py), resident on the device.
 
 ``WebLayout`` keeps the reference's constructor and file-selection rules, but parses every selected JSON file ONCE, at construction, into four
 device tensors (a whole training set is a few megabytes of coordinates).  An item or a batch is then one launch of ``ocrs_weblayout_batch``
@@ -11,14 +13,18 @@ dataset, so it is the reference's by construction; what crosses PCIe per batch i
 """
 from __future__ import annotations
 
+import gzip
 import json
 import os
+from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Optional
 
+import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
 from ._lib import lib, ptr
+from .input_pipeline import line_output_width
 
 
 def select_files(root_dir: str, train=True, max_images: Optional[int] = None, filter: Optional[Callable[[str], bool]] = None) -> list:
@@ -167,3 +173,310 @@ class DeviceWebLayoutLoader:
     def __iter__(self):
         for pages, jx, jy in self.plan():
             yield self.dataset.batch(pages, jx, jy)
+
+
+# ---- recognition: HierText text lines (ocrs_models/datasets/hiertext.py:145-427) ------------------------------------------------------
+MAX_LINE_VERTICES = 512  # csrc/line_data.hip's kMaxVerts
+
+
+def bounding_box_size(vertices) -> tuple[int, int]:
+    """datasets/util.py:184-194"""
+    xs, ys = [v[0] for v in vertices], [v[1] for v in vertices]
+    return (max(xs) - min(xs), max(ys) - min(ys))
+
+
+def generate_text_line_annotations(annotations_file: str, lines_file: str):
+    """``HierTextRecognition._generate_text_line_annotations`` (hiertext.py:306-427): the same rule for regeneration, the same five filters,
+    the same JSON object per kept line and the same statistics printout, so the two implementations read each other's lines file."""
+    if os.path.exists(lines_file) and (os.path.getmtime(lines_file) >= os.path.getmtime(annotations_file)):
+        return
+    MIN_WIDTH = 10
+    MIN_HEIGHT = 10
+    MIN_WORD_TO_LINE_AREA_RATIO = 0.8  # area(union of word boxes) / area(line box): below, the line is probably partly illegible
+    MIN_ASPECT_RATIO = 1.0  # width / height of the line box: drops severely rotated lines
+    total = total_usable = total_legible = total_horizontal = total_size_ok = total_area_ok = total_aspect_ok = 0
+    print(f"Extracting text line annotations from {annotations_file}")
+    with gzip.open(annotations_file) as in_fp:
+        annotations = json.load(in_fp)["annotations"]
+        with open(lines_file, "w") as out_fp:
+            for ann in annotations:
+                for para in ann["paragraphs"]:
+                    for line in para["lines"]:
+                        vertices = line["vertices"]
+                        width, height = bounding_box_size(vertices)
+                        aspect_ratio_ok = width / height >= MIN_ASPECT_RATIO
+                        words_width, words_height = bounding_box_size([vertex for word in line["words"] for vertex in word["vertices"]])
+                        area_ratio_ok = (words_width * words_height) / (width * height) >= MIN_WORD_TO_LINE_AREA_RATIO
+                        legible = line["legible"]
+                        horizontal = not line["vertical"]
+                        size_ok = width >= MIN_WIDTH and height >= MIN_HEIGHT
+                        total += 1
+                        total_legible += bool(legible)
+                        total_horizontal += bool(horizontal)
+                        total_size_ok += bool(size_ok)
+                        total_area_ok += bool(area_ratio_ok)
+                        total_aspect_ok += bool(aspect_ratio_ok)
+                        if not (legible and size_ok and horizontal and area_ratio_ok and aspect_ratio_ok):
+                            continue
+                        total_usable += 1
+                        ann_json = json.dumps({"image_id": ann["image_id"], "vertices": vertices, "text": line["text"]})
+                        out_fp.write(f"{ann_json}\n")
+    stats = {
+        "Total lines": total,
+        "Total usable for training": total_usable,
+        "Legible": total_legible,
+        "Horizontal": total_horizontal,
+        f"Aspect ratio (width/height) >= {MIN_ASPECT_RATIO}": total_aspect_ok,
+        f"Width >= {MIN_WIDTH} and Height >= {MIN_HEIGHT}": total_size_ok,
+        f"Words/line area ratio >= {MIN_WORD_TO_LINE_AREA_RATIO}": total_area_ok,
+    }
+    for description, value in stats.items():
+        percent = round((value / total) * 100, 1)
+        print(f"{description}: {value} ({percent}%)")
+
+
+def line_bounding_box(vertices) -> tuple[int, int, int, int]:
+    """(min_x, min_y, max_x, max_y) of hiertext.py:248-253"""
+    xs, ys = [v[0] for v in vertices], [v[1] for v in vertices]
+    min_x = max(0, min(xs))
+    max_x = max(min_x, max(xs))
+    min_y = max(0, min(ys))
+    max_y = max(min_y, max(ys))
+    return min_x, min_y, max_x, max_y
+
+
+def _read_gray(path: str) -> np.ndarray:
+    """(H, W) uint8.  A JPEG is decoded to libjpeg's own luma (``draft("L")``), as torchvision's ImageReadMode.GRAY asks libjpeg for."""
+    from PIL import Image
+
+    with Image.open(path) as im:
+        if im.format == "JPEG":
+            im.draft("L", im.size)
+        return np.array(im.convert("L"), dtype=np.uint8)
+
+
+def _page_crops(img_dir: str, cache_dir: str, image_id: str, boxes: list) -> list:
+    """The cached crops of one page's boxes (``_get_line_image``, hiertext.py:198-233): read where the cache file exists, otherwise cut from
+    the page (decoded once for all of them), written through .tmp + rename.  None for a crop that is empty after clamping."""
+    from PIL import Image
+
+    page, out = None, []
+    for min_x, min_y, max_x, max_y in boxes:
+        cache_path = f"{cache_dir}/{image_id}/{min_x}_{min_y}_{max_x}_{max_y}.png"
+        if not os.path.exists(cache_path):
+            if page is None:
+                page = _read_gray(f"{img_dir}/{image_id}.jpg")
+            ph, pw = page.shape
+            clamp = lambda v, hi: max(0, min(v, hi))  # noqa: E731
+            crop = page[clamp(min_y, ph - 1):clamp(max_y, ph - 1), clamp(min_x, pw - 1):clamp(max_x, pw - 1)]
+            if crop.shape[0] == 0 or crop.shape[1] == 0:
+                out.append(None)
+                continue
+            os.makedirs(os.path.dirname(cache_path), exist_ok=True)
+            tmp_path = cache_path + ".tmp"
+            Image.fromarray(np.ascontiguousarray(crop), "L").save(tmp_path, format="PNG")
+            os.rename(tmp_path, cache_path)
+        out.append(_read_gray(cache_path))
+    return out
+
+
+class HierTextRecognition(Dataset):
+    """HierText dataset for text recognition: the reference's ``HierTextRecognition`` (hiertext.py:145-304; same directory layout, lines
+    file and crop cache) with every line crop resident in device memory.  ``augment`` stands where the reference takes ``transform``: the
+    augmentations run inside the batch kernels (augment.py), so it is a flag.  A line whose crop is empty after clamping to the page is
+    dropped at construction with a counted message (the reference fails on such an item)."""
+
+    def __init__(self, root_dir: str, train=True, augment=False, max_images=None, alphabet=None, output_height: int = 64, device="cuda",
+                 transform=None):
+        super().__init__()
+        from .text import DEFAULT_ALPHABET, encode_text
+
+        if transform is not None or callable(augment):
+            raise TypeError("HierTextRecognition takes augment=True/False, not a transform: the augmentations of "
+                            "text_recognition_data_augmentations() run inside the batch kernels on the device")
+        self.alphabet = [c for c in (DEFAULT_ALPHABET if alphabet is None else alphabet)]
+        split = "train" if train else "validation"
+        self._img_dir = f"{root_dir}/{split}"
+        self._cache_dir = f"{root_dir}/{split}-lines-cache"
+        annotations_file = f"{root_dir}/gt/{split}.jsonl.gz"
+        if not os.path.exists(self._img_dir):
+            raise Exception(f'Image directory "{self._img_dir}" not found')
+        if not os.path.exists(annotations_file):
+            raise Exception(f'Label data file "{annotations_file}" not found')
+        lines_file = annotations_file.replace(".jsonl.gz", "-lines.jsonl")
+        generate_text_line_annotations(annotations_file, lines_file)
+        with open(lines_file) as fp:
+            text_lines = [line for line in fp]
+        if max_images:
+            text_lines = text_lines[:max_images]
+        self.augment = bool(augment)
+        self.output_height = output_height
+        self.device = torch.device(device)
+
+        lines = [json.loads(t) for t in text_lines]
+        by_page: dict = {}
+        for k, ln in enumerate(lines):
+            if any(int(c) != c for v in ln["vertices"] for c in v[:2]):
+                raise RuntimeError(f"line {k} of {lines_file} (image {ln['image_id']}): vertex coordinates must be whole numbers "
+                                   "(the mask kernel and the cache file names take them as integers)")
+            poly = [(int(c[0]), int(c[1])) for c in ln["vertices"]]
+            if not 2 <= len(poly) <= MAX_LINE_VERTICES or any(abs(c) > 65535 for v in poly for c in v):
+                raise RuntimeError(f"line {k} of {lines_file} (image {ln['image_id']}): polygons of 2 .. {MAX_LINE_VERTICES} vertices with "
+                                   f"coordinates within +-65535 are supported, this one has {len(poly)}")
+            ln["poly"], ln["box"] = poly, line_bounding_box(poly)
+            by_page.setdefault(ln["image_id"], []).append(k)
+        crops: list = [None] * len(lines)
+        pages = list(by_page.items())
+        with ThreadPoolExecutor(max_workers=max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
+            for (_, ks), got in zip(pages, pool.map(lambda pg: _page_crops(self._img_dir, self._cache_dir, pg[0], [lines[k]["box"] for k in pg[1]]),
+                                                    pages)):
+                for k, c in zip(ks, got):
+                    crops[k] = c
+        keep = [k for k, c in enumerate(crops) if c is not None]
+        if len(keep) != len(lines):
+            print(f"Dropped {len(lines) - len(keep)} of {len(lines)} lines whose crop is empty after clamping to the page")
+        self._set_store([lines[k]["image_id"] for k in keep], [crops[k] for k in keep],
+                        [[(x - lines[k]["box"][0], y - lines[k]["box"][1]) for x, y in lines[k]["poly"]] for k in keep],
+                        [encode_text(lines[k]["text"], self.alphabet, unknown_char="?") for k in keep])
+
+    @classmethod
+    def from_lines(cls, crops, polygons, text_seqs, image_ids=None, augment=False, output_height: int = 64, device="cuda"):
+        """A store made from memory instead of a directory (measurement and tests): ``crops`` (h, w) uint8 arrays, ``polygons`` integer
+        vertices relative to each crop's origin, ``text_seqs`` encoded int32 tensors."""
+        from .text import DEFAULT_ALPHABET
+
+        self = cls.__new__(cls)
+        Dataset.__init__(self)
+        self.alphabet = [c for c in DEFAULT_ALPHABET]
+        self.augment, self.output_height, self.device = bool(augment), output_height, torch.device(device)
+        if any(not 2 <= len(p) <= MAX_LINE_VERTICES for p in polygons):
+            raise RuntimeError(f"polygons of 2 .. {MAX_LINE_VERTICES} vertices are supported")
+        self._set_store(list(image_ids) if image_ids is not None else [str(k) for k in range(len(crops))], [np.ascontiguousarray(c) for c in crops],
+                        polygons, list(text_seqs))
+        return self
+
+    def _set_store(self, image_ids, crops, polygons, text_seqs):
+        self.image_ids, self.text_seqs = image_ids, text_seqs
+        self.sizes = [tuple(c.shape) for c in crops]  # (h, w) of every crop
+        self.widths = [line_output_width(h, w, self.output_height) for h, w in self.sizes]  # un-augmented item widths, for the samplers
+        area = np.array([h * w for h, w in self.sizes], dtype=np.int64)
+        counts = np.array([len(p) for p in polygons], dtype=np.int32)
+        verts = np.array([v for p in polygons for v in p], dtype=np.int32).reshape(-1, 2)
+        self._host = None
+        if crops:
+            self._host = (torch.from_numpy(np.concatenate([c.reshape(-1) for c in crops])), torch.from_numpy(np.cumsum(area) - area),
+                          torch.tensor(self.sizes, dtype=torch.int32), torch.from_numpy(verts),
+                          torch.from_numpy(np.cumsum(counts, dtype=np.int64) - counts), torch.from_numpy(counts))
+        self._dev = None
+        if crops and self.device.type == "cuda" and torch.cuda.is_available():
+            self._tensors()
+
+    def _tensors(self):
+        """pixels uint8 | pixel offsets int64 (L,) | sizes int32 (L, 2) | vertices int32 (V, 2) | vertex offsets int64 (L,) | counts int32 (L,)"""
+        if self._dev is None:
+            if self.device.type != "cuda" or not torch.cuda.is_available():
+                raise RuntimeError("ocrs_models_amd.datasets.HierTextRecognition runs on MI355X only (no CPU path)")
+            self._dev = tuple(t.to(self.device) for t in self._host)
+            self._host = None  # nothing per pixel stays on the host
+        return self._dev
+
+    def __len__(self):
+        return len(self.image_ids)
+
+    def draw_params(self, indices) -> list:
+        """One augmentation draw per line, in order, from torch's and Python's global generators (``augment``), else the identity."""
+        from .augment import AugParams, sample_line_params
+
+        sizes = [self.sizes[i] for i in indices]
+        return sample_line_params(sizes) if self.augment else [AugParams(-1, s, s) for s in sizes]
+
+    def raw(self, indices):
+        """Debug hook: [(crop uint8 (1, h, w), mask uint8 0/1 (1, h, w))] device tensors of the lines, as ``ocrs_line_batch`` makes them
+        (the reference's line_img before transform_image, and its generate_mask)."""
+        indices = [range(len(self))[int(i)] for i in indices]
+        px, px_off, sizes, verts, v_off, v_cnt = self._tensors()
+        area = np.array([self.sizes[i][0] * self.sizes[i][1] for i in indices], dtype=np.int64)
+        offs = np.zeros((len(indices), 3), dtype=np.int64)
+        offs[:, 0] = np.cumsum(area) - area
+        from .augment import _upload
+
+        idx_d, offs_d = _upload([np.array(indices, dtype=np.int32), offs], self.device, "HierTextRecognition")
+        crops = torch.empty(int(area.sum()), dtype=torch.uint8, device=self.device)
+        masks = torch.empty_like(crops)
+        lib().line_batch(ptr(px), ptr(px_off), ptr(sizes), ptr(verts), ptr(v_off), ptr(v_cnt), len(self), ptr(idx_d), len(indices),
+                         max(self.sizes[i][0] for i in indices), ptr(offs_d), ptr(crops), ptr(masks))
+        return [(crops[o:o + a].view(1, *self.sizes[i]), masks[o:o + a].view(1, *self.sizes[i])) for i, o, a in zip(indices, offs[:, 0].tolist(), area.tolist())]
+
+    def batch(self, indices, params=None, drop_infeasible=True, dtype=torch.float32) -> dict:
+        """``collate_samples`` over the items ``indices`` (train_rec.py:248-304) with ``image`` on the device: one pinned upload (records,
+        offsets, indices), ``ocrs_line_batch`` and the five launches of ``ocrs_augment_lines``; nothing synchronises."""
+        from .augment import _launch_lines, _line_batch_plan, _line_records, _upload
+
+        indices = [range(len(self))[int(i)] for i in indices]
+        if not indices:
+            raise RuntimeError("HierTextRecognition.batch: empty batch")
+        params = self.draw_params(indices) if params is None else params
+        if [tuple(p.size) for p in params] != [self.sizes[i] for i in indices]:
+            raise RuntimeError("HierTextRecognition.batch: params do not match the line sizes")
+        texts = [self.text_seqs[i] for i in indices]
+        image, meta, keep = _line_batch_plan(texts, params, self.output_height, dtype, self.device)
+        if not drop_infeasible and len(keep) != len(indices):
+            keep = list(range(len(indices)))
+            image = torch.empty(len(keep), *image.shape[1:], dtype=dtype, device=self.device)
+        if keep:
+            px, px_off, sizes, verts, v_off, v_cnt = self._tensors()
+            kp = [params[k] for k in keep]
+            rec, offs = _line_records(kp, self.output_height)
+            rec_d, offs_d, idx_d = _upload([rec, offs, np.array([indices[k] for k in keep], dtype=np.int32)], self.device, "HierTextRecognition")
+            total = sum(p.size[0] * p.size[1] for p in kp)
+            crops = torch.empty(total, dtype=torch.uint8, device=self.device)
+            masks = torch.empty_like(crops)
+            lib().line_batch(ptr(px), ptr(px_off), ptr(sizes), ptr(verts), ptr(v_off), ptr(v_cnt), len(self), ptr(idx_d), len(keep),
+                             max(p.size[0] for p in kp), ptr(offs_d), ptr(crops), ptr(masks))
+            _launch_lines(crops, masks, offs_d, rec_d, kp, image, self.output_height, 0, self.augment)
+        return {"image": image, **meta}
+
+    def __getitem__(self, idx: int):
+        """The reference's item: {"image_id", "image": (1, output_height, w) fp32 device tensor, "text_seq"}, augmented per the flag."""
+        idx = range(len(self))[idx]
+        params = self.draw_params([idx])
+        w = line_output_width(params[0].out_size[0], params[0].out_size[1], self.output_height)
+        image = self.batch([idx], params, drop_infeasible=False)["image"]
+        return {"image_id": self.image_ids[idx], "image": image[0, :, :, :w], "text_seq": self.text_seqs[idx]}
+
+
+class _LineIndices(Dataset):
+    def __init__(self, n: int):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return i
+
+
+class DeviceLineLoader:
+    """Iterable of ``collate_samples`` batch dicts with ``image`` on the device.  It stands where ``DataLoader(HierTextRecognition(...),
+    batch_size, shuffle, collate_fn=collate_samples)`` stands in train_rec.py:357-376: a stock ``DataLoader`` over a host index dataset
+    consumes the sampler's random stream, so the order is torch's by construction; the augmentation draws follow in batch order.
+    ``batch_sampler`` takes e.g. a ``sampler.WidthBucketedDistributedSampler(dataset.widths, ...)``."""
+
+    def __init__(self, dataset: HierTextRecognition, batch_size: int = 1, shuffle=False, generator=None, batch_sampler=None):
+        self.dataset = dataset
+        collate = lambda items: [int(i) for i in items]  # noqa: E731
+        if batch_sampler is not None:
+            self._loader = DataLoader(_LineIndices(len(dataset)), batch_sampler=batch_sampler, collate_fn=collate)
+        else:
+            self._loader = DataLoader(_LineIndices(len(dataset)), batch_size=batch_size, shuffle=shuffle, generator=generator, collate_fn=collate)
+
+    def __len__(self):
+        return len(self._loader)
+
+    def plan(self):
+        """One epoch's lists of line indices, one per batch; touches no GPU."""
+        return iter(self._loader)
+
+    def __iter__(self):
+        for indices in self.plan():
+            yield self.dataset.batch(indices)

@@ -1,9 +1,13 @@
 """Recognition training step, the body of the reference's ``train()`` loop (ocrs_models/train_rec.py:107-153):
 bf16 autocast forward + CTC loss, accuracy stats, NaN guard, backward, clip_grad_norm_(4.0), Adam step -- and the validation loop
-``test()`` (ocrs_models/train_rec.py:163-217): eval-mode forward, CTC loss, greedy decode + character error rate."""
+``test()`` (ocrs_models/train_rec.py:163-217): eval-mode forward, CTC loss, greedy decode + character error rate; and its ``main()``
+(train_rec.py:307-462) on the device-resident dataset of ``ocrs_models_amd.datasets``:
+``python -m ocrs_models_amd.train_rec hiertext DATA_DIR``.  No experiment tracking here."""
 from __future__ import annotations
 
 import math
+import os
+from argparse import ArgumentParser, BooleanOptionalAction
 
 import torch
 
@@ -133,3 +137,111 @@ def test(device, dataloader, model, preview: int = 10, stats: str = "host"):
             mean_loss += loss_fn(pred_seq, text_seq, input_lengths, target_lengths)
             n += 1
     return float(mean_loss.item()) / max(n, 1), stats
+
+
+CHECKPOINT_FILE = "text-rec-checkpoint.pt"
+
+
+def main(argv=None):
+    """The reference's training script (train_rec.py:307-462) without wandb: same arguments, seed, validation-size rule, print lines,
+    scheduler and checkpoint file.  ``--stats device`` (extension) keeps the accuracy statistics on the GPU.  Started by a launcher with
+    WORLD_SIZE > 1 it is one rank of a data-parallel run: the model is wrapped in ``ddp.DistributedDataParallel``, the training batches
+    come from a ``WidthBucketedDistributedSampler`` over the dataset's widths, every rank validates (the scheduler steps on the validation
+    loss everywhere), and rank 0 alone prints and saves."""
+    from .datasets import DeviceLineLoader, HierTextRecognition
+    from .recognition import RecognitionModel
+    from .text import DEFAULT_ALPHABET
+
+    parser = ArgumentParser(description="Train text recognition model.")
+    parser.add_argument("dataset_type", type=str, choices=["hiertext"])
+    parser.add_argument("data_dir")
+    parser.add_argument("--augment", default=True, action=BooleanOptionalAction, help="Enable data augmentations")
+    parser.add_argument("--batch-size", type=int, default=20)
+    parser.add_argument("--checkpoint", type=str, help="Model checkpoint to load")
+    parser.add_argument("--export", type=str, help="Export model to ONNX format")
+    parser.add_argument("--lr", type=float, help="Initial learning rate")
+    parser.add_argument("--max-epochs", type=int, help="Maximum number of epochs to train for")
+    parser.add_argument("--max-images", type=int, help="Maximum number of items to train on")
+    parser.add_argument("--validate-only", action="store_true", help="Run validation on an exiting model")
+    parser.add_argument("--stats", choices=["host", "device"], default="host", help="Where the accuracy statistics are computed")
+    args = parser.parse_args(argv)
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("ocrs_models_amd.train_rec runs on MI355X only (no CPU path)")
+    torch.manual_seed(1234)
+
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    distributed = world > 1
+    if distributed:
+        import torch.distributed as dist
+
+        torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)))
+        if not dist.is_initialized():
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", torch.cuda.current_device()))
+    device = torch.device("cuda", torch.cuda.current_device())
+    say = print if rank == 0 else (lambda *a, **k: None)
+
+    max_images = args.max_images
+    validation_max_images = max(10, int(max_images * 0.1)) if max_images else None
+    if distributed and rank != 0:
+        dist.barrier()  # rank 0 writes the lines files and the crop cache alone; the others then only read them
+    train_dataset = HierTextRecognition(args.data_dir, train=True, max_images=max_images, augment=args.augment, device=device)
+    train_sampler = None
+    if distributed:
+        from .sampler import WidthBucketedDistributedSampler
+
+        train_sampler = WidthBucketedDistributedSampler(train_dataset.widths, args.batch_size, rank=rank, world_size=world, seed=1234)
+        train_dataloader = DeviceLineLoader(train_dataset, batch_sampler=train_sampler)
+    else:
+        train_dataloader = DeviceLineLoader(train_dataset, batch_size=args.batch_size, shuffle=True)
+    val_dataset = HierTextRecognition(args.data_dir, train=False, max_images=validation_max_images, device=device)
+    val_dataloader = DeviceLineLoader(val_dataset, batch_size=args.batch_size, shuffle=True)
+    if distributed and rank == 0:
+        dist.barrier()
+
+    model = RecognitionModel(alphabet=DEFAULT_ALPHABET).to(device)
+    optimizer = make_optimizer(model, lr=args.lr or 1e-3)  # 1e-3 is the Adam default
+    scheduler = make_scheduler(optimizer)
+    total_params = sum(p.numel() for p in model.parameters() if p.requires_grad)
+    say(f"Model param count {total_params}")
+
+    epoch = 0
+    if args.checkpoint:
+        checkpoint = load_checkpoint(args.checkpoint, model, optimizer, device)
+        epoch = checkpoint["epoch"]
+
+    if args.export:
+        from .export import export_onnx
+
+        test_batch = next(iter(val_dataloader))
+        if rank == 0:
+            export_onnx(model, args.export, test_batch["image"].to(device))
+        return
+
+    if args.validate_only:
+        val_loss, val_stats = test(device, val_dataloader, model, stats=args.stats)
+        say(f"Validation loss {val_loss} char error rate {val_stats.char_error_rate()}")
+        return
+
+    net = model
+    if distributed:
+        from .ddp import DistributedDataParallel
+
+        net = DistributedDataParallel(model)
+
+    while args.max_epochs is None or epoch < args.max_epochs:
+        if train_sampler is not None:
+            train_sampler.set_epoch(epoch)
+        train_loss, train_stats = train(epoch, device, train_dataloader, net, optimizer, stats=args.stats)
+        say(f"Epoch {epoch} train loss {train_loss} char error rate {train_stats.char_error_rate()}")
+        val_loss, val_stats = test(device, val_dataloader, model, stats=args.stats)  # (every rank: the scheduler steps on it everywhere)
+        say(f"Epoch {epoch} validation loss {val_loss} char error rate {val_stats.char_error_rate()}")
+        scheduler.step(val_loss)
+        say(f"Current learning rate {scheduler.get_last_lr()}")
+        if rank == 0:
+            save_checkpoint(CHECKPOINT_FILE, model, optimizer, epoch=epoch)
+        epoch += 1
+
+
+if __name__ == "__main__":
+    main()
