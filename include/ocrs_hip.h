@@ -535,7 +535,7 @@ int ocrs_weblayout_batch(const double* coords, const int* para, const long long*
  * (x, y), polygon i = vertex_counts[i] (2 .. 512) vertices from vertex_offs[i], coordinates within +-65535 (the host checks both); sizes [n][2] int32 (h, w) of its canvas; its 0/1 byte mask
  * (h * w, row-major) is written at out_u8 + out_offs[i].  max_h >= every h (it sizes the grid).  Self-intersecting polygons get whatever the
  * restated scanline rules give (tests/hiertext_ref.py), and so do polygons that pass twice through one vertex; parity with PIL (12.2.0) is
- * pinned for simple polygons only (DESIGN.md section 10 says on how many). */
+ * pinned for simple polygons only (DESIGN.md section 12 says on how many). */
 int ocrs_line_mask(const int* vertices, const long long* vertex_offs, const int* vertex_counts, const int* sizes, const long long* out_offs,
                    void* out_u8, int n, int max_h, hipStream_t st);
 /* One batch of HierTextRecognition._get_line_image + generate_mask (hiertext.py:256-263) from the line store in device memory: pixels_u8 = the
@@ -546,6 +546,30 @@ int ocrs_line_mask(const int* vertices, const long long* vertex_offs, const int*
 int ocrs_line_batch(const void* pixels_u8, const long long* pixel_offs, const int* sizes, const int* vertices, const long long* vertex_offs,
                     const int* vertex_counts, int N, const int* indices, int B, int max_h, const long long* batch_offs, void* out_crops_u8,
                     void* out_masks_u8, hipStream_t st);
+
+/* ------------------------------------------------------------------ detection page store ------ */
+/* Detection training data (csrc/page_data.hip; Python: ocrs_models_amd/datasets.py HierText / DDI100 / DevicePageLoader).
+ * ocrs_shrink_polygons: shrink_polygon(poly, dist) of ocrs_models/datasets/util.py:54-75 as generate_mask calls it (util.py:96-102), for n
+ * polygons in one launch, one thread each, by the project's own rule (the mitred inward offset with GEOS' mitre limit
+ * of 5, a ring that would split or flip is skipped; tests/detdata_ref.py states it operation by operation).  vertices [..][2] int32 (x, y),
+ * polygon i = vertex_counts[i] (<= 512) vertices from vertex_offs[i], coordinates within +-65535 (the host checks both).  Polygon i's result
+ * starts at element 2 * vertex_offs[i] of out_xy [..][2] fp64 (the shrunk ring) and of out_vertices [..][2] int32 (the same truncated as PIL
+ * converts float polygon coordinates: towards zero); both hold 2 * (all vertices) points.  out_counts [n] = its vertex count, 0 = skipped,
+ * -1 = more than 512; out_rows [n][2] = the first and last row its fill can touch (y_min, y_max of out_vertices; 0, -1 when skipped).
+ * ws: 3 * (all vertices) ints.  dist == 0.0 copies the vertices (generate_mask's bypass, util.py:97-100). */
+int ocrs_shrink_polygons(const int* vertices, const long long* vertex_offs, const int* vertex_counts, int n, double dist, int* ws, double* out_xy,
+                         int* out_vertices, int* out_counts, int* out_rows, hipStream_t st);
+/* One batch of HierText.__getitem__ / DDI100.__getitem__ up to the transform (hiertext.py:73-92, ddi100.py:77-94) from the page store in
+ * device memory: pixels_u8 = the grey pages back to back, page l = sizes[l] (h, w) bytes from pixel_offs[l]; N pages.  For b < B, page
+ * indices[b] (0 .. N-1) is copied to out_pages_u8 + batch_offs[b] and generate_mask(w, h, its polygons) (util.py:78-110: the union of PIL's
+ * ImageDraw.polygon(fill, outline=None) over the shrunk polygons, each by ocrs_line_mask's rules) is written as 0/1 bytes at out_masks_u8 +
+ * batch_offs[b]: batch_offs is the offset table of ocrs_augment_det, which runs next on these two buffers.  polys [n_polys][4] int32 = {first
+ * vertex in vertices, vertex count (0 = skipped), y_min, y_max} with each page's polygons sorted by y_min; bands [..][2] int32 = the slice
+ * [lo, hi) of polys that can touch a band of 16 rows, page l's ceil(h / 16) bands starting at band_offs[l].  Pixel, batch and output offsets
+ * that are multiples of 16 move 16 bytes per lane.  max_h / max_w >= the height / width of every page of the batch. */
+int ocrs_page_batch(const void* pixels_u8, const long long* pixel_offs, const int* sizes, const int* vertices, long n_vertices, const int* polys,
+                    int n_polys, const long long* band_offs, const int* bands, int N, const int* indices, int B, int max_h, int max_w,
+                    const long long* batch_offs, void* out_pages_u8, void* out_masks_u8, hipStream_t st);
 
 /* ------------------------------------------------------------------ optimiser ---------------- */
 /* table [nt][5] int64 {param, grad, exp_avg, exp_avg_sq, numel}; chunks [nchunks][2] int32 {tensor, chunk of ocrs_opt_chunk()}. */

@@ -16,6 +16,7 @@ from __future__ import annotations
 import gzip
 import json
 import os
+import pickle
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Optional
 
@@ -480,3 +481,334 @@ class DeviceLineLoader:
     def __iter__(self):
         for indices in self.plan():
             yield self.dataset.batch(indices)
+
+
+# ---- detection: pages with word polygons (ocrs_models/datasets/hiertext.py:22-130, ddi100.py:34-107) ----------------------------------
+MAX_POLYGON_VERTICES = 512  # csrc/poly_fill.h's kMaxVerts
+SHRINK_DISTANCE = 3.0  # datasets/util.py:18
+BAND_ROWS = 16  # csrc/page_data.hip's kBandRows
+_ROW_KEY, _ROW_BIAS = 1 << 22, 1 << 21  # sort key = page * _ROW_KEY + row + _ROW_BIAS (a shrunk ring stays within +-2^20)
+
+
+def generate_json_lines_annotations(annotations_file: str, lines_file: str):
+    """``HierText._generate_json_lines_annotations`` (hiertext.py:107-130): the same file, the same line per image, the same rule for
+    regeneration, so the two implementations read each other's file."""
+    if os.path.exists(lines_file) and (os.path.getmtime(lines_file) >= os.path.getmtime(annotations_file)):
+        return
+    print("Converting annotations from JSON to JSONL format...")
+    with gzip.open(annotations_file) as in_fp:
+        annotations = json.load(in_fp)["annotations"]
+        with open(lines_file, "w") as out_fp:
+            for ann in annotations:
+                ann_json = json.dumps(ann)
+                out_fp.write(f"{ann_json}\n")
+
+
+def hiertext_word_polygons(annotations: dict) -> list:
+    """hiertext.py:77-86: every word of every line of every paragraph, in that order."""
+    return [[tuple(coord) for coord in word["vertices"]] for para in annotations["paragraphs"] for line in para["lines"] for word in line["words"]]
+
+
+class DDI100Unpickler(pickle.Unpickler):
+    """ddi100.py:11-31: numpy's dtype, ndarray and array reconstructor, nothing else.  (The reconstructor is admitted under the module name
+    numpy 2 writes into a pickle as well: it is the same function.)"""
+
+    def find_class(self, module, name):
+        path = f"{module}.{name}"
+        if path == "numpy.dtype":
+            return np.dtype
+        if path == "numpy.ndarray":
+            return np.ndarray
+        if path in ("numpy.core.multiarray._reconstruct", "numpy._core.multiarray._reconstruct"):
+            try:
+                from numpy._core.multiarray import _reconstruct
+            except ImportError:
+                from numpy.core.multiarray import _reconstruct
+            return _reconstruct
+        raise pickle.UnpicklingError(f"Disallowed class {module}.{name}")
+
+
+def _whole_polygon(poly, what: str) -> list:
+    pts = [tuple(c) for c in (poly.tolist() if hasattr(poly, "tolist") else poly)]
+    if any(len(c) < 2 or int(c[0]) != c[0] or int(c[1]) != c[1] for c in pts):
+        raise RuntimeError(f"{what}: vertex coordinates must be whole numbers (the shrink kernel takes them as integers)")
+    pts = [(int(c[0]), int(c[1])) for c in pts]
+    if len(pts) > MAX_POLYGON_VERTICES or any(abs(c) > 65535 for v in pts for c in v):
+        raise RuntimeError(f"{what}: polygons of at most {MAX_POLYGON_VERTICES} vertices with coordinates within +-65535 are supported, "
+                           f"this one has {len(pts)}")
+    return pts
+
+
+class _PageStore(Dataset):
+    """What HierText and DDI100 share: the pages' grey pixels and the word polygons in device memory, shrunk once at construction
+    (``ocrs_shrink_polygons``), sorted by first row and binned per band of rows; an item or a batch is then ``ocrs_page_batch`` (gather +
+    ``generate_mask``) followed by ``ocrs_augment_det`` (``prepare_transform(mask_size, augment)``)."""
+
+    def _init_args(self, augment, device, mask_size, transform, shrink_dist=SHRINK_DISTANCE):
+        name = type(self).__name__
+        if transform is not None or callable(augment):
+            raise TypeError(f"{name} takes augment=True/False and mask_size, not a transform: prepare_transform(mask_size, augment) runs "
+                            "inside the batch kernels on the device")
+        self.augment, self.device, self.mask_size, self.shrink_dist = bool(augment), torch.device(device), tuple(mask_size), float(shrink_dist)
+
+    @classmethod
+    def from_pages(cls, pages, polygons, paths=None, augment=False, device="cuda", mask_size=None, shrink_dist=SHRINK_DISTANCE):
+        """A store made from memory instead of a directory (measurement and tests): ``pages`` (h, w) uint8 arrays, ``polygons`` one list of
+        integer-vertex polygons per page."""
+        from .augment import MASK_SIZE
+
+        self = cls.__new__(cls)
+        Dataset.__init__(self)
+        self._init_args(augment, device, mask_size or MASK_SIZE, None, shrink_dist)
+        self._set_store(list(paths) if paths is not None else [str(k) for k in range(len(pages))], [np.ascontiguousarray(p) for p in pages], polygons)
+        return self
+
+    def _set_store(self, paths, pages, polygons):
+        from .augment import _check_sizes
+
+        name = type(self).__name__
+        if len(polygons) != len(pages) or len(paths) != len(pages):
+            raise RuntimeError(f"{name}: need one path and one polygon list per page")
+        if any(p.ndim != 2 or p.dtype != np.uint8 for p in pages):
+            raise RuntimeError(f"{name}: pages must be (h, w) uint8 arrays")
+        self.paths = paths
+        self.sizes = [tuple(int(s) for s in p.shape) for p in pages]  # (h, w) of every page
+        _check_sizes(self.sizes, name)
+        polys = [[_whole_polygon(q, f"{name}: page {paths[k]}") for q in page_polys] for k, page_polys in enumerate(polygons)]
+        self.poly_counts = [len(p) for p in polys]
+        area = np.array([h * w for h, w in self.sizes], dtype=np.int64)
+        padded = (area + 15) // 16 * 16  # every page starts on a 16-byte boundary (16 bytes per lane in the gather)
+        px_off = np.cumsum(padded) - padded
+        counts = np.array([len(q) for p in polys for q in p], dtype=np.int32)
+        verts = np.array([v for p in polys for q in p for v in q], dtype=np.int32).reshape(-1, 2)
+        if 2 * len(verts) >= 2**31:
+            raise RuntimeError(f"{name}: {len(verts)} polygon vertices are too many for one store: use max_images")
+        self._host = None
+        if pages:
+            pixels = np.zeros(int(padded.sum()), dtype=np.uint8)
+            for p, o, a in zip(pages, px_off.tolist(), area.tolist()):
+                pixels[o:o + a] = p.reshape(-1)
+            self._host = (torch.from_numpy(pixels), torch.from_numpy(px_off), torch.tensor(self.sizes, dtype=torch.int32), torch.from_numpy(verts),
+                          torch.from_numpy(np.cumsum(counts, dtype=np.int64) - counts), torch.from_numpy(counts),
+                          torch.from_numpy(np.repeat(np.arange(len(pages), dtype=np.int64), self.poly_counts)))
+        self._dev = None
+        self.skipped = None  # how many polygons the shrink dropped: known once the store is on the device
+        if pages and self.device.type == "cuda" and torch.cuda.is_available():
+            self._tensors()
+
+    def _tensors(self):
+        """pixels uint8 | pixel offsets int64 (P,) | sizes int32 (P, 2) | shrunk vertices int32 (2V, 2) | polygon records int32 (Q, 4) =
+        first vertex, count, y_min, y_max, sorted by (page, y_min) | band offsets int64 (P,) | bands int32 (.., 2)"""
+        if self._dev is None:
+            name = type(self).__name__
+            if self.device.type != "cuda" or not torch.cuda.is_available():
+                raise RuntimeError(f"ocrs_models_amd.datasets.{name} runs on MI355X only (no CPU path)")
+            if self._host is None:
+                raise RuntimeError(f"ocrs_models_amd.datasets.{name}: the store is empty")
+            pixels, px_off, sizes, verts, v_off, v_cnt, poly_page = self._host
+            V, Q = verts.shape[0], v_cnt.shape[0]
+            need = pixels.numel() + 72 * V + 64 * Q + (1 << 20)  # the pages, the shrink's buffers, the records
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if need > free:
+                raise RuntimeError(f"ocrs_models_amd.datasets.{name}: the store needs {need} bytes of device memory ({pixels.numel()} of them "
+                                   f"pixels) and {free} are free: load fewer pages with max_images")
+            dev = self.device
+            d_px, d_pxoff, d_sizes = pixels.to(dev), px_off.to(dev), sizes.to(dev)
+            out_verts = torch.zeros(max(2 * V, 1), 2, dtype=torch.int32, device=dev)
+            records = torch.zeros(0, 4, dtype=torch.int32, device=dev)
+            if Q:
+                d_verts, d_voff, d_vcnt, d_page = verts.to(dev), v_off.to(dev), v_cnt.to(dev), poly_page.to(dev)
+                ws = torch.empty(max(3 * V, 1), dtype=torch.int32, device=dev)
+                out_xy = torch.empty(max(2 * V, 1), 2, dtype=torch.float64, device=dev)
+                out_cnt = torch.empty(Q, dtype=torch.int32, device=dev)
+                out_rows = torch.empty(Q, 2, dtype=torch.int32, device=dev)
+                lib().shrink_polygons(ptr(d_verts), ptr(d_voff), ptr(d_vcnt), Q, self.shrink_dist, ptr(ws), ptr(out_xy), ptr(out_verts), ptr(out_cnt),
+                                      ptr(out_rows))
+                if bool((out_cnt < 0).any()):  # (construction may wait for the device; a batch never does)
+                    raise RuntimeError(f"{name}: a shrunk polygon has more than {MAX_POLYGON_VERTICES} vertices (every reflex corner past the "
+                                       "mitre limit adds one)")
+                kept = torch.nonzero(out_cnt > 0).reshape(-1)
+                key = d_page[kept] * _ROW_KEY + out_rows[kept, 0].long() + _ROW_BIAS
+                kept = kept[torch.argsort(key, stable=True)]
+                records = torch.stack([(2 * d_voff[kept]).int(), out_cnt[kept], out_rows[kept, 0], out_rows[kept, 1]], dim=1).contiguous()
+                self.skipped = Q - int(kept.numel())
+                del ws, out_xy
+            else:
+                self.skipped = 0
+            # the band table: polygons [lo, hi) of the sorted records can touch rows [16 k, 16 k + 15] of their page
+            nb = (sizes[:, 0].long() + BAND_ROWS - 1) // BAND_ROWS
+            band_off = torch.cumsum(nb, 0) - nb
+            b_page = torch.repeat_interleave(torch.arange(len(nb)), nb)
+            b_row0 = (torch.arange(int(nb.sum())) - band_off[b_page]) * BAND_ROWS
+            b_row1 = torch.minimum(b_row0 + BAND_ROWS - 1, sizes[:, 0].long()[b_page] - 1)
+            b_page, b_row0, b_row1 = b_page.to(dev), b_row0.to(dev), b_row1.to(dev)
+            if records.shape[0]:
+                r_page = d_page[kept]
+                first_key = r_page * _ROW_KEY + records[:, 2].long() + _ROW_BIAS
+                last_key = torch.cummax(r_page * _ROW_KEY + records[:, 3].long() + _ROW_BIAS, 0)[0]
+                lo = torch.searchsorted(last_key, b_page * _ROW_KEY + b_row0 + _ROW_BIAS, right=False)
+                hi = torch.searchsorted(first_key, b_page * _ROW_KEY + b_row1 + _ROW_BIAS, right=True)
+                bands = torch.stack([lo, torch.maximum(hi, lo)], dim=1).int().contiguous()
+            else:
+                bands = torch.zeros(int(nb.sum()), 2, dtype=torch.int32, device=dev)
+            self._dev = (d_px, d_pxoff, d_sizes, out_verts, records, band_off.to(dev), bands)
+            self._host = None  # nothing per pixel stays on the host
+        return self._dev
+
+    def __len__(self):
+        return len(self.paths)
+
+    def draw_params(self, indices) -> list:
+        """One ``prepare_transform(mask_size, augment)`` draw per page, in order, from torch's and Python's global generators, else the identity."""
+        from .augment import AugParams, sample_detection_params
+
+        sizes = [self.sizes[i] for i in indices]
+        return sample_detection_params(sizes) if self.augment else [AugParams(-1, s, s) for s in sizes]
+
+    def _gather(self, indices, extra: list):
+        """``ocrs_page_batch`` for checked ``indices`` -> (pages, masks) packed uint8 device buffers, the uploaded offsets and ``extra``
+        sections (one pinned upload for all of them), the host offsets."""
+        from .augment import _upload
+
+        px, px_off, sizes, verts, records, band_off, bands = self._tensors()
+        area = np.array([self.sizes[i][0] * self.sizes[i][1] for i in indices], dtype=np.int64)
+        padded = (area + 15) // 16 * 16
+        offs = np.cumsum(padded) - padded
+        up = _upload([offs, np.array(indices, dtype=np.int32)] + extra, self.device, type(self).__name__)
+        pages = torch.empty(int(padded.sum()), dtype=torch.uint8, device=self.device)
+        masks = torch.empty_like(pages)
+        lib().page_batch(ptr(px), ptr(px_off), ptr(sizes), ptr(verts), verts.shape[0], ptr(records) if records.shape[0] else None, records.shape[0],
+                         ptr(band_off), ptr(bands), len(self), ptr(up[1]), len(indices), max(self.sizes[i][0] for i in indices),
+                         max(self.sizes[i][1] for i in indices), ptr(up[0]), ptr(pages), ptr(masks))
+        return pages, masks, up[0], up[2:], offs
+
+    def raw(self, indices):
+        """Debug hook: [(page uint8 (1, h, w), mask uint8 0/1 (1, h, w))] device tensors of the pages, as ``ocrs_page_batch`` makes them
+        (the reference's read_image before transform_image, and its generate_mask)."""
+        indices = [range(len(self))[int(i)] for i in indices]
+        if not indices:
+            return []
+        pages, masks, _, _, offs = self._gather(indices, [])
+        return [(pages[o:o + h * w].view(1, h, w), masks[o:o + h * w].view(1, h, w)) for (h, w), o in zip((self.sizes[i] for i in indices), offs.tolist())]
+
+    def batch(self, indices, params=None, dtype=torch.float32) -> dict:
+        """The default collate of the items ``indices`` (train_detection.py:350-366) on the device: {"path": [...], "image": (B, 1, *mask_size)
+        ``dtype``, "text_mask": (B, 1, *mask_size) fp32}.  One pinned upload (records, offsets, indices), ``ocrs_page_batch`` and the three
+        launches of ``ocrs_augment_det``; nothing synchronises."""
+        from .augment import _DT, _records
+
+        name = type(self).__name__
+        indices = [range(len(self))[int(i)] for i in indices]
+        if not indices:
+            raise RuntimeError(f"{name}.batch: empty batch")
+        params = self.draw_params(indices) if params is None else params
+        if [tuple(p.size) for p in params] != [self.sizes[i] for i in indices]:
+            raise RuntimeError(f"{name}.batch: params do not match the page sizes")
+        B, (oh, ow) = len(indices), self.mask_size
+        pages, masks, offs_d, (rec_d,), _ = self._gather(indices, [_records(params, line=False)])
+        image = torch.empty(B, 1, oh, ow, dtype=dtype, device=self.device)
+        text_mask = torch.empty(B, 1, oh, ow, dtype=torch.float32, device=self.device)
+        ws = torch.empty(lib().augment_det_ws_floats(B), dtype=torch.float32, device=self.device)
+        lib().augment_det(ptr(pages), ptr(masks), ptr(offs_d), ptr(rec_d), ptr(ws), ptr(image), ptr(text_mask), B, max(self.sizes[i][0] for i in indices),
+                          max(self.sizes[i][1] for i in indices), oh, ow, 0, _DT[dtype])
+        return {"path": [self.paths[i] for i in indices], "image": image, "text_mask": text_mask}
+
+    def __getitem__(self, idx: int):
+        """The reference's item: {"path", "image": (1, *mask_size) fp32 device tensor, "text_mask": (1, *mask_size)}, augmented per the flag."""
+        idx = range(len(self))[idx]
+        b = self.batch([idx])
+        return {"path": b["path"][0], "image": b["image"][0], "text_mask": b["text_mask"][0]}
+
+
+def _decode_pages(paths: list, read) -> list:
+    with ThreadPoolExecutor(max_workers=max(1, min(16, len(os.sched_getaffinity(0))))) as pool:
+        return list(pool.map(read, paths))
+
+
+class HierText(_PageStore):
+    """HierText dataset for text detection: the reference's ``HierText`` (hiertext.py:22-130; same directory layout and JSONL file) with every
+    page and its word polygons resident in device memory.  ``augment`` and ``mask_size`` stand where the reference takes ``transform``:
+    ``prepare_transform(mask_size, augment)`` runs inside the batch kernels (augment.py)."""
+
+    def __init__(self, root_dir: str, train=True, augment=False, max_images=None, device="cuda", mask_size=None, transform=None):
+        from .augment import MASK_SIZE
+
+        super().__init__()
+        self._init_args(augment, device, mask_size or MASK_SIZE, transform)
+        split = "train" if train else "validation"
+        self._img_dir = f"{root_dir}/{split}"
+        annotations_file = f"{root_dir}/gt/{split}.jsonl.gz"
+        if not os.path.exists(self._img_dir):
+            raise Exception(f'Image directory "{self._img_dir}" not found')
+        if not os.path.exists(annotations_file):
+            raise Exception(f'Label data file "{annotations_file}" not found')
+        lines_file = annotations_file.replace(".jsonl.gz", ".jsonl")
+        generate_json_lines_annotations(annotations_file, lines_file)
+        with open(lines_file) as fp:
+            self._annotations = [line for line in fp]
+        if max_images:
+            self._annotations = self._annotations[:max_images]
+        anns = [json.loads(a) for a in self._annotations]
+        paths = [f"{self._img_dir}/{a['image_id']}.jpg" for a in anns]
+        self._set_store(paths, _decode_pages(paths, _read_gray), [hiertext_word_polygons(a) for a in anns])
+
+
+def _read_one_channel(path: str) -> np.ndarray:
+    from PIL import Image
+
+    with Image.open(path) as im:
+        if len(im.getbands()) != 1:
+            raise RuntimeError(f"{path}: DDI100 pages must have one channel, this image has {len(im.getbands())} ({im.mode}): convert it to "
+                               "greyscale (the reference fails on it when it stacks the image and its mask)")
+    return _read_gray(path)
+
+
+class DDI100(_PageStore):
+    """Distorted Document Images (DDI-100) dataset for text detection: the reference's ``DDI100`` (ddi100.py:34-107; ``gen_imgs/`` and
+    ``gen_boxes/*.pickle``, sorted listing, max_images before the 90/10 split) with the pages and word quads resident in device memory.
+    The quads are ``w["box"]`` as ``__getitem__`` passes them to generate_mask (ddi100.py:89-93)."""
+
+    def __init__(self, root_dir: str, train=True, augment=False, max_images=None, device="cuda", mask_size=None, transform=None):
+        from .augment import MASK_SIZE
+
+        super().__init__()
+        self._init_args(augment, device, mask_size or MASK_SIZE, transform)
+        self._img_dir = f"{root_dir}/gen_imgs"
+        self._boxes_dir = f"{root_dir}/gen_boxes"
+        if not os.path.exists(self._img_dir):
+            raise Exception(f"Dataset images not found in {self._img_dir}")
+        if not os.path.exists(self._boxes_dir):
+            raise Exception(f"Dataset masks not found in {self._boxes_dir}")
+        self._img_filenames = sorted(os.listdir(self._img_dir))
+        if max_images is not None:
+            self._img_filenames = self._img_filenames[:max_images]
+        train_split_idx = int(len(self._img_filenames) * 0.9)
+        self._img_filenames = self._img_filenames[:train_split_idx] if train else self._img_filenames[train_split_idx:]
+        paths = [f"{self._img_dir}/{f}" for f in self._img_filenames]
+        quads = []
+        for f in self._img_filenames:
+            with open(f"{self._boxes_dir}/{os.path.splitext(f)[0]}.pickle", "rb") as fp:
+                quads.append([w["box"] for w in DDI100Unpickler(fp).load()])
+        self._set_store(paths, _decode_pages(paths, _read_one_channel), quads)
+
+
+class DevicePageLoader:
+    """Iterable of detection batch dicts with ``image`` and ``text_mask`` on the device.  It stands where ``DataLoader(HierText(...) or
+    DDI100(...), batch_size, shuffle)`` stands in train_detection.py:350-366: a stock ``DataLoader`` over a host index dataset consumes the
+    sampler's random stream, so the order is torch's by construction; the augmentation draws follow in batch order."""
+
+    def __init__(self, dataset: _PageStore, batch_size: int = 1, shuffle=False, generator=None, dtype=torch.float32):
+        self.dataset, self.dtype = dataset, dtype
+        self._loader = DataLoader(_LineIndices(len(dataset)), batch_size=batch_size, shuffle=shuffle, generator=generator,
+                                  collate_fn=lambda items: [int(i) for i in items])
+
+    def __len__(self):
+        return len(self._loader)
+
+    def plan(self):
+        """One epoch's lists of page indices, one per batch; touches no GPU."""
+        return iter(self._loader)
+
+    def __iter__(self):
+        for indices in self.plan():
+            yield self.dataset.batch(indices, dtype=self.dtype)
