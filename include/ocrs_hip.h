@@ -467,6 +467,28 @@ long ocrs_resize_aa_packed_ws_floats(long hpass_floats);
 int ocrs_resize_aa_packed(const float* packed, const int* plan, const int* count, long cap, const long long* chunks, int nchunks, int max_batch, float* ws,
                           long ws_floats, float* out, long out_floats, int output_height, hipStream_t st);
 
+/* ------------------------------------------------------------------ text lines ---------------- */
+/* Words -> lines in reading order by the geometric rule of DESIGN.md §14 (csrc/text_lines.hip; Python: inference.find_lines; restated in
+ * tests/lines_ref.py).  quads [cap][4][2] fp32 as above; n = min(*count, cap) words (count nullable: n = cap); rows, and entries of every
+ * output, past n are neither read nor written.  The four stages run in this order on one stream and share ws
+ * (ocrs_text_lines_ws_bytes(cap) bytes, 16-byte aligned), which carries the word frames, heads, ranks and line table from one to the next.
+ * Nothing synchronises and there are no float atomics: equal input gives equal bytes.
+ *
+ * ocrs_line_links: word frames, every word's candidate successor with the smallest s (ties: smallest j), acceptance by the chosen word
+ * of its nearest chooser (64-bit integer atomicMin of (bits(s) << 32 | k)); next_word [cap] int = the linked successor or -1. */
+long ocrs_text_lines_ws_bytes(long cap);
+int ocrs_line_links(const float* quads, const int* count, long cap, float max_gap, float min_cos, int* next_word, void* ws, long ws_bytes, hipStream_t st);
+/* Head, position in the line and line length of every word by pointer jumping, ceil(log2 cap) rounds: one workgroup in LDS for cap <= 2048,
+ * one launch per round above that.  next_word: what ocrs_line_links wrote. */
+int ocrs_line_rank(const int* count, long cap, const int* next_word, void* ws, long ws_bytes, hipStream_t st);
+/* Lines sorted by their head's (centre y, centre x, word index): n_lines [1] int = L; line_offsets [cap + 1] int, entries 0..L = exclusive scan
+ * of the line lengths; word_order [cap] int, the words of line l in chain order at line_offsets[l]; line_of_word [cap] int. */
+int ocrs_line_order(const int* count, long cap, int* n_lines, int* line_of_word, int* word_order, int* line_offsets, void* ws, long ws_bytes, hipStream_t st);
+/* line_quads [cap][4][2] fp32, rows 0..L-1 (the rest untouched): a one-word line is the word's quad copied; otherwise the rectangle around all
+ * corners in the frame u_L = normalise(sum of long side * u over the words in chain order), corners (minU,minV), (maxU,minV), (maxU,maxV), (minU,maxV). */
+int ocrs_line_quads(const float* quads, const int* count, long cap, const int* n_lines, const int* line_offsets, const int* word_order, float* line_quads,
+                    void* ws, long ws_bytes, hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

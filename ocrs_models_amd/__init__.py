@@ -8,5 +8,5 @@ from .recognition import RecognitionModel  # noqa: F401
 from .layout import LayoutModel  # noqa: F401
 from . import losses, train_detection, train_layout, train_rec  # noqa: F401,E402
 from . import inference  # noqa: F401,E402
-from .inference import (MASK_SIZE, SHRINK_DISTANCE, binarize_resize, crop_plan, crops_to_batches, detect_words, expand_quads,  # noqa: F401,E402
-                        ocr_page, recognize_crops, rectify_crops)
+from .inference import (MASK_SIZE, SHRINK_DISTANCE, TextLines, binarize_resize, crop_plan, crops_to_batches, detect_words,  # noqa: F401,E402
+                        expand_quads, find_lines, ocr_lines, ocr_page, read_lines, recognize_crops, rectify_crops)

@@ -1,11 +1,13 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
-    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT]
+    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
 on the page).  With ``--rec-model`` the words are recognised too (``inference.ocr_page``'s stages) and printed, one JSON object per line.
-The image is read and the pictures are written with PIL on the host; that is not a hot path.
+With ``--lines`` the words are grouped into text lines first (``inference.find_lines``): ``-text-lines.png`` shows the line quads, and with
+``--rec-model`` every LINE is recognised (``inference.read_lines``) and printed as one JSON object with its quad, its text and its words' quads
+in reading order, instead of the words.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -47,6 +49,8 @@ def main(argv=None):
     parser.add_argument("image")
     parser.add_argument("out_basename")
     parser.add_argument("--rec-model", help="recognition checkpoint: also recognise the words and print them as JSON lines")
+    parser.add_argument("--lines", action="store_true", help="group the words into text lines: write -text-lines.png and, with --rec-model, "
+                        "recognise and print one JSON object per line instead of per word")
     args = parser.parse_args(argv)
 
     device = torch.device("cuda:0")
@@ -72,10 +76,22 @@ def main(argv=None):
     quads = det["quads"].tolist()
     draw_quads(page_h, quads).save(f"{args.out_basename}-text-words.png")
 
+    rec = None
     if args.rec_model and det["n"]:
         rec = RecognitionModel(DEFAULT_ALPHABET).to(device)
         load_model_state(args.rec_model, rec, device)
         rec.eval()
+    if args.lines:
+        if rec is not None:
+            lines = inference.read_lines(rec, page, det["quads"])
+            for line in lines:
+                print(json.dumps(line))
+            line_quads = [line["quad"] for line in lines]
+        else:
+            found = inference.find_lines(det["quads"])
+            line_quads = found.quads[:int(found.n_lines)].tolist()
+        draw_quads(page_h, line_quads).save(f"{args.out_basename}-text-lines.png")
+    elif rec is not None:
         plan = inference.crop_plan(det["quads"])
         packed = inference.rectify_crops(page, det["quads"], plan)
         texts = inference.recognize_crops(rec, inference.crops_to_batches(packed, plan))

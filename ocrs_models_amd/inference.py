@@ -32,6 +32,10 @@ pixel k, as ``extract_cc_quads`` produces them.
   ``origin + (x + 0.5) / w_i * long * u + (y + 0.5) / h_i * short * v``; sampling is bilinear on the ``transform_image`` values of the page,
   with coordinates clamped to the page (border padding).  All of this is fp32 arithmetic.
 * Output width.  ``line_output_width(h_i, w_i, output_height)``, unchanged.
+
+Lines.  ``find_lines`` groups the word quads into text lines in reading order (csrc/text_lines.hip, C ABI section "text lines"; the rule is
+stated once in DESIGN.md §14 and restated for the tests in tests/lines_ref.py) without a host synchronisation, and ``ocr_lines`` is
+``ocr_page`` with that stage in between: one crop and one string per line, the recogniser's training unit, with the same three waits.
 """
 from __future__ import annotations
 
@@ -129,21 +133,27 @@ class CropPlan:
 
     def host_perm(self) -> list[int]:
         """Position of quad i in output-width order as a host list (from the copy ``host()`` made): ``sorted_results[perm[i]]`` is quad i's"""
-        self.host()
-        return self._host_table[:, 6].tolist()
+        n = self.host()[0]
+        return self._host_table[:n, 6].tolist()
 
 
-def crop_plan(quads: torch.Tensor, output_height: int = 64) -> CropPlan:
+def crop_plan(quads: torch.Tensor, output_height: int = 64, count: torch.Tensor | None = None) -> CropPlan:
     """Geometry of the crop of every quad (N,4,2) by the module's crop-frame rule, offsets into the packed buffers and the order by output
-    width.  One kernel, no synchronisation."""
+    width.  One kernel, no synchronisation.  ``count`` (1,) int32 on the device: only the first ``min(count, N)`` quads are planned (the
+    table's other rows are left as allocated); the later stages take that number from ``plan.host()[0]``."""
     _need_cuda(quads, "crop_plan")
     if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
         raise RuntimeError("crop_plan: expected (N,4,2) float32 quads")
+    if count is not None:
+        _need_cuda(count, "crop_plan")
+        if count.dtype != torch.int32 or count.numel() != 1:
+            raise RuntimeError("crop_plan: count must be one int32 on the device")
+        count = count.contiguous()
     q = quads.contiguous()
     n = q.shape[0]
     table = torch.empty(n, 8, dtype=torch.int32, device=q.device)
     totals = torch.empty(4 + _OW_BINS, dtype=torch.int64, device=q.device)
-    lib().crop_plan(ptr(q), None, n, int(output_height), ptr(table), ptr(totals))
+    lib().crop_plan(ptr(q), ptr(count), n, int(output_height), ptr(table), ptr(totals))
     return CropPlan(table, totals, int(output_height))
 
 
@@ -214,7 +224,7 @@ def crops_to_batches(packed: torch.Tensor, plan: CropPlan, max_batch: int = 256,
         ws_floats = L.resize_aa_packed_ws_floats(hpass)
         ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
         L.resize_aa_packed(ptr(packed), ptr(plan.table), None, n, ptr(chunks_d), len(chunks), int(max_batch), ptr(ws), ws_floats, ptr(out), off, OH)
-    widths_sorted = plan.table[:, 2][plan.table[:, 7].long()].long() if n else torch.empty(0, dtype=torch.int64, device=dev)
+    widths_sorted = plan.table[:n, 2][plan.table[:n, 7].long()].long() if n else torch.empty(0, dtype=torch.int64, device=dev)
     image_widths = [widths_sorted[p:p + cnt] for p, cnt, _ in chunks]
     return batches, image_widths, plan.host_perm()
 
@@ -253,3 +263,97 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thresh
     quads_h.copy_(quads, non_blocking=True)
     texts = recognize_crops(rec_model, batches, alphabet)
     return [{"quad": q, "text": t} for q, t in zip(quads_h.tolist(), texts)]
+
+
+# ------------------------------------------------------------------ words -> lines -------------------------------------------------------
+@dataclass
+class TextLines:
+    """What ``find_lines`` returns, all on the device.  With L = ``n_lines[0]`` and n the number of words: ``quads[:L]`` are the line quads in
+    line order; line l holds the words ``word_order[line_offsets[l]:line_offsets[l + 1]]`` in chain (reading) order; ``line_of_word[i]`` is the
+    line of word i and ``next_word[i]`` the word linked after it, or -1.  Rows of ``quads`` from L on, entries of ``line_offsets`` after L and
+    entries of the per-word tensors from n on are not written."""
+    quads: torch.Tensor         # (N,4,2) fp32
+    n_lines: torch.Tensor       # (1,) int32
+    line_of_word: torch.Tensor  # (N,) int32
+    word_order: torch.Tensor    # (N,) int32
+    line_offsets: torch.Tensor  # (N+1,) int32
+    next_word: torch.Tensor     # (N,) int32
+
+
+def _empty_lines(n: int, device) -> TextLines:
+    i32 = dict(dtype=torch.int32, device=device)
+    n_lines = torch.empty(1, **i32) if n else torch.zeros(1, **i32)  # (with words, k_line_scan writes it)
+    return TextLines(torch.empty(n, 4, 2, dtype=torch.float32, device=device), n_lines, torch.empty(n, **i32), torch.empty(n, **i32),
+                     torch.empty(n + 1, **i32), torch.empty(n, **i32))
+
+
+def find_lines(quads: torch.Tensor, count: torch.Tensor | None = None, max_gap: float = 2.0, min_cos: float = 0.9,
+               out: TextLines | None = None) -> TextLines:
+    """Group word quads (N,4,2) into text lines in reading order by the geometric rule of DESIGN.md §14 (csrc/text_lines.hip): every word
+    links to the nearest word that follows it along its own long axis within ``max_gap`` times the taller of the two heights, on the same
+    baseline and with ``min_cos`` between the axes; a word accepts its nearest chooser; lines are the chains, sorted by their first word's
+    (centre y, centre x, index).  ``count`` (1,) int32 on the device: only the first ``min(count, N)`` rows are words.  ``out``: write into
+    these tensors instead of new ones.  Four stages of kernels, no host synchronisation; ``N == 0`` launches nothing."""
+    _need_cuda(quads, "find_lines")
+    if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
+        raise RuntimeError("find_lines: expected (N,4,2) float32 quads")
+    if count is not None:
+        _need_cuda(count, "find_lines")
+        if count.dtype != torch.int32 or count.numel() != 1:
+            raise RuntimeError("find_lines: count must be one int32 on the device")
+        count = count.contiguous()
+    q = quads.contiguous()
+    n = q.shape[0]
+    if out is None:
+        out = _empty_lines(n, q.device)
+    else:
+        for name, shape in (("quads", (n, 4, 2)), ("n_lines", (1,)), ("line_of_word", (n,)), ("word_order", (n,)), ("line_offsets", (n + 1,)), ("next_word", (n,))):
+            t, dtype = getattr(out, name), torch.float32 if name == "quads" else torch.int32
+            _need_cuda(t, "find_lines")
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise RuntimeError(f"find_lines: out.{name} must be a contiguous {shape} {dtype} tensor")
+    if n == 0:
+        return out
+    L = lib()
+    ws_bytes = L.text_lines_ws_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+    L.line_links(ptr(q), ptr(count), n, float(max_gap), float(min_cos), ptr(out.next_word), ptr(ws), ws_bytes)
+    L.line_rank(ptr(count), n, ptr(out.next_word), ptr(ws), ws_bytes)
+    L.line_order(ptr(count), n, ptr(out.n_lines), ptr(out.line_of_word), ptr(out.word_order), ptr(out.line_offsets), ptr(ws), ws_bytes)
+    L.line_quads(ptr(q), ptr(count), n, ptr(out.n_lines), ptr(out.line_offsets), ptr(out.word_order), ptr(out.quads), ptr(ws), ws_bytes)
+    return out
+
+
+def _to_host_async(t: torch.Tensor) -> torch.Tensor:
+    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    h.copy_(t, non_blocking=True)
+    return h
+
+
+def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
+               alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9) -> list[dict]:
+    """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
+    synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
+    ahead of the recogniser on the same stream, so they have arrived when the labels have."""
+    lines = find_lines(quads, None, max_gap, min_cos)
+    plan = crop_plan(lines.quads, output_height, lines.n_lines)
+    packed = rectify_crops(page_u8, lines.quads, plan)
+    batches = crops_to_batches(packed, plan, max_batch, width_unit)
+    n_lines = plan.host()[0]
+    quads_h, lq_h, order_h, offs_h = (_to_host_async(t) for t in (quads, lines.quads, lines.word_order, lines.line_offsets))
+    texts = recognize_crops(rec_model, batches, alphabet)
+    words, order, offs, lq = quads_h.tolist(), order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
+    return [{"quad": lq[l], "text": texts[l], "words": [words[i] for i in order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+
+
+def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
+              output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
+              min_cos: float = 0.9) -> list[dict]:
+    """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
+    ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
+    synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
+    returns ``[]`` without launching the recogniser."""
+    det = detect_words(det_model, page_u8, size, threshold, expand)
+    if det["n"] == 0:
+        return []
+    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos)
