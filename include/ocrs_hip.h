@@ -489,6 +489,43 @@ int ocrs_line_order(const int* count, long cap, int* n_lines, int* line_of_word,
 int ocrs_line_quads(const float* quads, const int* count, long cap, const int* n_lines, const int* line_offsets, const int* word_order, float* line_quads,
                     void* ws, long ws_bytes, hipStream_t st);
 
+/* ------------------------------------------------------------------ page batches -------------- */
+/* The page-inference and text-line stages for B pages of different sizes at once (Python: inference.detect_words_batch,
+ * find_lines_pages, rectify_crops_pages, ocr_pages).  page_sizes [B][2] int = (H_p, W_p); a page store is the pages' bytes back to back in one
+ * uint8 buffer with page_offs [B] int64, the byte offset of each.  ocrs_cc_quads, ocrs_expand_quads, ocrs_crop_plan and ocrs_resize_aa_packed
+ * serve batches as they are.  Nothing here synchronises.
+ *
+ * The masks of all pages in one launch: prob (B,h,w) fp32 -> out (B,Hmax,Wmax) uint8 with Hmax >= H_p, Wmax >= W_p.  Inside (H_p, W_p) the
+ * bytes ocrs_binarize_resize_nearest writes for prob[p] and that size alone, 0 outside (written by the same launch).  Padding is background, so
+ * ocrs_cc_quads(B, Hmax, Wmax) finds every page's own components in their own raster order. */
+int ocrs_binarize_resize_pages(const float* prob, const int* page_sizes, unsigned char* out, int B, int h, int w, int Hmax, int Wmax, float threshold,
+                               hipStream_t st);
+/* quads [B][cap][4][2] with counts [B] (what ocrs_cc_quads wrote) -> word_offs [B + 1] int = exclusive scan of min(counts, cap); out (nullable)
+ * [out_cap][4][2] = the rows of page 0, page 1, ... back to back, each page in its own order, and page_of_word [out_cap] int (rows from out_cap
+ * on are dropped).  out == NULL writes word_offs only: the caller reads word_offs[B] to size out, then calls again.  B <= 65535. */
+int ocrs_gather_page_quads(const float* quads, const int* counts, int B, long cap, float* out, int* page_of_word, int* word_offs, long out_cap, hipStream_t st);
+/* The four text-line stages over the flat words of B pages: page p's words are word_offs[p] .. word_offs[p + 1], n = min(word_offs[B], cap).
+ * The rule of §14 with two additions: a word's candidate successors are words of its own page only, and lines are sorted by (page, centre y,
+ * centre x, word index) of their head.  The links and order kernels stage only the words of a workgroup's own page (work: sum of n_p^2).
+ * Outputs as in "text lines", indices into the flat arrays, plus line_page_offs [B + 1] int (the lines of page p are line_page_offs[p] ..
+ * line_page_offs[p + 1]; the last entry is L) and page_of_line [cap] int, rows 0..L-1.  ws: ocrs_text_lines_pages_ws_bytes(cap, B) bytes, 16-byte
+ * aligned, shared by the four stages in this order; ocrs_line_rank_pages and ocrs_line_quads_pages are the single-page kernels run on the
+ * flat array (links never leave a page).  cap == 0 or B == 0 launches nothing. */
+long ocrs_text_lines_pages_ws_bytes(long cap, int B);
+int ocrs_line_links_pages(const float* quads, const int* word_offs, int B, long cap, float max_gap, float min_cos, int* next_word, void* ws, long ws_bytes,
+                          hipStream_t st);
+int ocrs_line_rank_pages(const int* word_offs, int B, long cap, const int* next_word, void* ws, long ws_bytes, hipStream_t st);
+int ocrs_line_order_pages(const int* word_offs, int B, long cap, int* n_lines, int* line_of_word, int* word_order, int* line_offsets, int* line_page_offs,
+                          int* page_of_line, void* ws, long ws_bytes, hipStream_t st);
+int ocrs_line_quads_pages(const float* quads, const int* word_offs, int B, long cap, const int* n_lines, const int* line_offsets, const int* word_order,
+                          float* line_quads, void* ws, long ws_bytes, hipStream_t st);
+/* ocrs_rectify_crops from a page store: crop i is cut from page page_of_quad[i] (page_of_line for line crops, page_of_word for word crops),
+ * whose pointer and size are looked up per workgroup; a page index outside 0..B-1 or a page outside pages_bytes writes nothing.  Same frame,
+ * taps and arithmetic: a crop's bytes are those ocrs_rectify_crops writes for it from its own page. */
+int ocrs_rectify_crops_pages(const unsigned char* pages, long pages_bytes, const long long* page_offs, const int* page_sizes, int B, const float* quads,
+                             const int* page_of_quad, const int* plan, const long long* totals, long max_tiles, float* packed, long packed_floats,
+                             hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

@@ -7,6 +7,11 @@
 //   k_rectify_crops             (new) rotated rectangles cut out of the uint8 page, transform_image fused, bilinear
 //   k_resize_aa_packed_{h,v}    resize(.., antialias=True) per crop    hiertext.py:288-294        + collate_samples' right padding
 //
+// Page batches: the same stages for B pages of different sizes at once.
+//   k_binarize_resize_pages     k_binarize_resize_nearest per page into one zero-padded (B, Hmax, Wmax) canvas, padding included
+//   k_gather_page_quads         (B, cap) quads with counts -> flat rows grouped by page, page_of_word, word_offs
+//   k_rectify_crops_pages       k_rectify_crops with the page looked up per crop in a packed page store
+//
 // All of them are small and byte-bound: no LDS tiles, no MFMA; coalesced 4..16-byte vector accesses; every count stays on the device.
 #include "input_pipe.h"
 
@@ -50,6 +55,49 @@ __global__ __launch_bounds__(256) void k_binarize_resize_nearest(const float* __
     }
 }
 
+// The same per page into one canvas (B, Hmax, Wmax): inside (H_p, W_p) the byte k_binarize_resize_nearest writes for that page alone (the
+// same float scales h / H_p and w / W_p, the same floorf and clamp), 0 outside.  One lane = 16 consecutive canvas bytes, padding included,
+// taken one canvas row at a time: the page's size and scales are looked up per row piece, not per byte.
+__global__ __launch_bounds__(256) void k_binarize_resize_pages(const float* __restrict__ prob, const int* __restrict__ page_sizes, uint8_t* __restrict__ out, int h,
+                                                               int w, int Hmax, int Wmax, long total, float threshold) {
+    const long nchunks = (total + 15) / 16;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < nchunks; c += (long)gridDim.x * 256) {
+        const long e = c * 16;
+        long row = e / Wmax;  // b * Hmax + y
+        int x = (int)(e - row * Wmax);
+        long b = row / Hmax;
+        int y = (int)(row - b * Hmax);
+        const int nv = (int)min(16L, total - e);
+        unsigned long long lo = 0ULL, hi = 0ULL;  // bytes 0..7 and 8..15
+        for (int k = 0; k < nv;) {
+            const int run = min(nv - k, Wmax - x);  // the piece of row (b, y) from x on
+            const int H = min(page_sizes[2 * b], Hmax), W = min(page_sizes[2 * b + 1], Wmax);
+            if (y < H && x < W) {
+                const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+                const float* src = prob + (b * h + min((int)floorf((float)y * sy), h - 1)) * (long)w;
+                const int m = min(run, W - x);
+                for (int q = 0; q < m; ++q) {
+                    const int xs = min((int)floorf((float)(x + q) * sx), w - 1);
+                    if (src[xs] > threshold) {
+                        const int bit = 8 * (k + q);
+                        if (bit < 64) lo |= 1ULL << bit; else hi |= 1ULL << (bit - 64);
+                    }
+                }
+            }
+            k += run, x += run;
+            if (x == Wmax) {
+                x = 0;
+                if (++y == Hmax) y = 0, ++b;
+            }
+        }
+        if (nv == 16) {
+            *reinterpret_cast<uint4*>(out + e) = make_uint4((unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32));
+        } else {
+            for (int k = 0; k < nv; ++k) out[e + k] = (uint8_t)(((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8)))) & 0xff);
+        }
+    }
+}
+
 // ---- quad expansion --------------------------------------------------------------------------------------------------------------
 // One lane = one quad (two 16-byte loads, two 16-byte stores).  fp64 inside, so the result is the correctly rounded fp32 of the rule.
 __global__ __launch_bounds__(256) void k_expand_quads(const float* __restrict__ quads, float* __restrict__ out, const int* __restrict__ counts, long cap,
@@ -79,6 +127,30 @@ __global__ __launch_bounds__(256) void k_expand_quads(const float* __restrict__ 
     const double ax = ha * ux, ay = ha * uy, bx = hb * vx, by = hb * vy;
     reinterpret_cast<float4*>(out)[2 * i] = make_float4((float)(cx - ax - bx), (float)(cy - ay - by), (float)(cx + ax - bx), (float)(cy + ay - by));
     reinterpret_cast<float4*>(out)[2 * i + 1] = make_float4((float)(cx + ax + bx), (float)(cy + ay + by), (float)(cx - ax + bx), (float)(cy - ay + by));
+}
+
+// ---- compaction of the per-page quads ---------------------------------------------------------------------------------------------
+// grid (ceil(cap / 256), B): workgroup (c, b) copies rows c * 256 .. of page b to the flat rows that start at the sum of the earlier counts
+// (B is small: every lane adds them up, one address per step).  Workgroup (0, 0) writes word_offs.  out == nullptr: word_offs only.
+__device__ __forceinline__ long page_count(const int* __restrict__ counts, int b, long cap) { return min((long)max(counts[b], 0), cap); }
+__global__ __launch_bounds__(256) void k_gather_page_quads(const float* __restrict__ quads, const int* __restrict__ counts, int B, long cap, float* __restrict__ out,
+                                                           int* __restrict__ page_of_word, int* __restrict__ word_offs, long out_cap) {
+    const int b = blockIdx.y;
+    if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
+        long run = 0;
+        for (int q = 0; q < B; ++q) word_offs[q] = (int)run, run += page_count(counts, q, cap);
+        word_offs[B] = (int)run;
+    }
+    if (!out) return;
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if ((long)blockIdx.x * 256 >= page_count(counts, b, cap)) return;  // (block-uniform, before the sum)
+    long base = 0;
+    for (int q = 0; q < b; ++q) base += page_count(counts, q, cap);
+    if (r >= page_count(counts, b, cap) || base + r >= out_cap) return;
+    const float4* src = reinterpret_cast<const float4*>(quads) + 2 * ((long)b * cap + r);
+    float4* dst = reinterpret_cast<float4*>(out) + 2 * (base + r);
+    dst[0] = src[0], dst[1] = src[1];
+    page_of_word[base + r] = b;
 }
 
 // ---- crop frame: the one statement of the geometry rule, used by the plan and by the sampler ----------------------------------------
@@ -244,6 +316,59 @@ __global__ __launch_bounds__(256) void k_rectify_crops(const uint8_t* __restrict
     *reinterpret_cast<float4*>(packed + pl.w + e0) = make_float4(out[0], out[1], out[2], out[3]);
 }
 
+// The same from a store of pages: crop lo comes from page page_of_quad[lo], whose pointer and size are looked up once per workgroup
+// (wave-uniform, like the frame).  The sampling below is k_rectify_crops' text, operation for operation: a crop's bytes are those it gets
+// from ocrs_rectify_crops on its own page.
+__global__ __launch_bounds__(256) void k_rectify_crops_pages(const uint8_t* __restrict__ pages, long pages_bytes, const long long* __restrict__ page_offs,
+                                                             const int* __restrict__ page_sizes, int B, const float* __restrict__ quads,
+                                                             const int* __restrict__ page_of_quad, const int* __restrict__ plan,
+                                                             const long long* __restrict__ totals, float* __restrict__ packed, long packed_floats) {
+    const long long tile = blockIdx.x;
+    const long n = (long)totals[0];
+    if (n <= 0 || tile >= totals[3]) return;
+    long lo = 0, hi = n - 1;
+    while (lo < hi) {  // the last crop whose first tile is <= tile
+        const long mid = (lo + hi + 1) >> 1;
+        if (plan[mid * 8 + 5] <= tile) lo = mid; else hi = mid - 1;
+    }
+    const int pg = page_of_quad[lo];
+    if ((unsigned)pg >= (unsigned)B) return;
+    const int H = page_sizes[2 * pg], W = page_sizes[2 * pg + 1];
+    const long long poff = page_offs[pg];
+    if (H <= 0 || W <= 0 || poff < 0 || poff + (long long)H * W > pages_bytes) return;  // a page that is not inside the store is not read
+    const uint8_t* page = pages + poff;
+    const CropFrame f = crop_frame(quads + lo * 8);
+    const int4 pl = *reinterpret_cast<const int4*>(plan + lo * 8);  // h, w, ow, packed offset
+    const int h = pl.x, w = pl.y;
+    const long hw = (long)h * w;
+    const long e0 = (long)(tile - plan[lo * 8 + 5]) * kTileElems + threadIdx.x * 4;
+    if (e0 >= hw || (long)pl.w + e0 + 4 > packed_floats) return;
+    const float vx = -f.uy, vy = f.ux;
+    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
+    float out[4];
+    int y = (int)(e0 / w), x = (int)(e0 - (long)y * w);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float val = 0.0f;
+        if (e0 + k < hw) {
+            const float su = ((float)x + 0.5f) / (float)w * f.lng, sv = ((float)y + 0.5f) / (float)h * f.sht;
+            float px = f.ox + su * f.ux + sv * vx, py = f.oy + su * f.uy + sv * vy;
+            px = fminf(fmaxf(px, 0.0f), xmax), py = fminf(fmaxf(py, 0.0f), ymax);  // border padding
+            const int x0 = (int)px, y0 = (int)py;
+            const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+            const float fx = px - (float)x0, fy = py - (float)y0;
+            const uint8_t* r0 = page + (size_t)y0 * W;
+            const uint8_t* r1 = page + (size_t)y1 * W;
+            const float a = px_u8(r0[x0]), b = px_u8(r0[x1]), c = px_u8(r1[x0]), d = px_u8(r1[x1]);
+            const float top = a + (b - a) * fx, bot = c + (d - c) * fx;
+            val = top + (bot - top) * fy;
+            if (++x == w) x = 0, ++y;
+        }
+        out[k] = val;
+    }
+    *reinterpret_cast<float4*>(packed + pl.w + e0) = make_float4(out[0], out[1], out[2], out[3]);
+}
+
 // ---- antialiased resize of the packed crops into padded batches ------------------------------------------------------------------
 // Same two passes in the same order as ocrs_resize_aa (horizontal, then vertical), through the same aa_span / aa_dot: same bits.
 // crop i: packed (h, w) -> ws (h, ow).  grid (cap, ceil(800 / 256)); one lane = one output column, its span computed once for all rows.
@@ -322,6 +447,44 @@ int ocrs_rectify_crops(const unsigned char* page, int H, int W, const float* qua
     if (max_tiles == 0) return OCRS_OK;
     OCRS_CHECK_ARG(page && quads && plan && totals && packed && aligned16(quads) && aligned16(plan) && aligned16(packed));
     hipLaunchKernelGGL(k_rectify_crops, dim3((unsigned)max_tiles), dim3(256), 0, st, page, H, W, quads, plan, totals, packed, packed_floats);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+// ---- page batches ------------------------------------------------------------------------------------------------------------------
+int ocrs_binarize_resize_pages(const float* prob, const int* page_sizes, unsigned char* out, int B, int h, int w, int Hmax, int Wmax, float threshold,
+                               hipStream_t st) {
+    OCRS_CHECK_ARG(B >= 0 && h > 0 && w > 0 && Hmax > 0 && Wmax > 0);
+    const long total = (long)B * Hmax * Wmax;
+    if (total == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(prob && page_sizes && out && aligned16(out));
+    long g = ((total + 15) / 16 + 255) / 256;
+    g = g > kNumCU * 8 ? kNumCU * 8 : g;
+    hipLaunchKernelGGL(k_binarize_resize_pages, dim3((unsigned)g), dim3(256), 0, st, prob, page_sizes, out, h, w, Hmax, Wmax, total, threshold);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+int ocrs_gather_page_quads(const float* quads, const int* counts, int B, long cap, float* out, int* page_of_word, int* word_offs, long out_cap, hipStream_t st) {
+    OCRS_CHECK_ARG(B >= 0 && B <= 65535 && cap >= 0 && out_cap >= 0 && (long)B * cap < (1L << 31) && word_offs);
+    OCRS_CHECK_ARG(B == 0 || counts);
+    OCRS_CHECK_ARG(!out || out_cap == 0 || (quads && page_of_word && aligned16(quads) && aligned16(out)));
+    const bool rows = out && out_cap > 0 && cap > 0 && B > 0;
+    const long gx = rows ? (cap + 255) / 256 : 1;
+    hipLaunchKernelGGL(k_gather_page_quads, dim3((unsigned)gx, (unsigned)(B > 0 ? B : 1)), dim3(256), 0, st, quads, counts, B, cap, rows ? out : nullptr, page_of_word,
+                       word_offs, out_cap);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+int ocrs_rectify_crops_pages(const unsigned char* pages, long pages_bytes, const long long* page_offs, const int* page_sizes, int B, const float* quads,
+                             const int* page_of_quad, const int* plan, const long long* totals, long max_tiles, float* packed, long packed_floats,
+                             hipStream_t st) {
+    OCRS_CHECK_ARG(B >= 0 && pages_bytes >= 0 && max_tiles >= 0 && max_tiles < (1L << 31) && packed_floats >= 0);
+    if (max_tiles == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(pages && page_offs && page_sizes && quads && page_of_quad && plan && totals && packed && aligned16(quads) && aligned16(plan) && aligned16(packed));
+    hipLaunchKernelGGL(k_rectify_crops_pages, dim3((unsigned)max_tiles), dim3(256), 0, st, pages, pages_bytes, page_offs, page_sizes, B, quads, page_of_quad, plan,
+                       totals, packed, packed_floats);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

@@ -11,6 +11,16 @@
 //   k_line_scatter   word_order and line_of_word
 //   k_line_quads     one wave per line: direction sum in chain order, min / max of the projections by wave reduction
 //
+// Page batches: the words of B pages in one flat array, page p's at word_offs[p] .. word_offs[p + 1].  A word's candidates are
+// the words of its own page and lines are ordered by (page, c.y, c.x, word index); frames, resolve, rank, scan, scatter and quads run unchanged
+// on the flat array with the total word_offs[B] as their device count.
+//   k_pages_init         chosen = -1, line_idx = 0 (words that no page covers stay in bounds), per-page head counters = 0
+//   k_page_blocks        blk_offs [B + 1]: exclusive scan of ceil(n_p / 256), the workgroups of each page; one workgroup
+//   k_line_links_pages   k_line_links with one page per workgroup: only that page's frames are staged
+//   k_line_order_pages   k_line_order likewise -> rank of each head among its page's heads, heads counted per page
+//   k_page_scan          line_page_offs [B + 1]: exclusive scan of the head counts; one workgroup
+//   k_line_place_pages   line index = line_page_offs[page] + rank in the page; len_sorted, head_of_line, page_of_line
+//
 // All decision arithmetic is fp32 with one rounding per operation (no fused multiply-add), so the restatement follows it operation by
 // operation.  No float atomics: the only atomic is an integer minimum whose result does not depend on the order of arrival.
 #include "common.h"
@@ -313,9 +323,187 @@ __global__ __launch_bounds__(256) void k_line_quads(const float* __restrict__ qu
     }
 }
 
+// ---- page batches ------------------------------------------------------------------------------------------------------------------
+struct PagesWs {
+    int *blk_offs;  // [B + 1] first workgroup of every page
+    int *heads;     // [B] heads (= lines) per page
+};
+inline PagesWs ws_split_pages(void* ws, long cap, int B) {
+    PagesWs w;
+    char* p = static_cast<char*>(ws) + ws_cap(cap) * kWsBytesPerWord;
+    w.blk_offs = reinterpret_cast<int*>(p), p += ws_cap(B + 1) * 4;
+    w.heads = reinterpret_cast<int*>(p);
+    return w;
+}
+
+// word range of page p, clamped so that offsets that are not an ascending scan still index inside the n words
+__device__ __forceinline__ int2 page_range(const int* __restrict__ word_offs, int p, int n) {
+    const int lo = min(max(word_offs[p], 0), n);
+    return make_int2(lo, min(max(word_offs[p + 1], lo), n));
+}
+// the page of workgroup k: the last p with blk_offs[p] <= k (pages without words own no workgroup and are passed over); k < blk_offs[B]
+__device__ __forceinline__ int page_of_block(const int* __restrict__ blk_offs, int B, int k) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk_offs[mid] <= k) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// the page of word i: the last p with word_offs[p] <= i
+__device__ __forceinline__ int page_of_index(const int* __restrict__ word_offs, int B, int i) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (word_offs[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_pages_init(const int* __restrict__ count, long cap, int B, int* __restrict__ chosen, int* __restrict__ line_idx,
+                                                    int* __restrict__ heads) {
+    const int n = word_count(count, cap);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) chosen[i] = -1, line_idx[i] = 0;
+    if (i < B) heads[i] = 0;
+}
+
+// One workgroup: out[0..B] = exclusive scan over the pages, 256 at a time, of ceil(n_p / per) (per > 0, from word_offs) or of vals[p] (per == 0).
+__global__ __launch_bounds__(256) void k_page_scan(const int* __restrict__ word_offs, const int* __restrict__ vals, const int* __restrict__ count, long cap, int B,
+                                                   int per, int* __restrict__ out) {
+    __shared__ int s_scan[256];
+    const int n = word_count(count, cap);
+    const int t = threadIdx.x;
+    int base = 0;
+    for (int p0 = 0; p0 < B; p0 += 256) {
+        const int p = p0 + t;
+        int v = 0;
+        if (p < B) {
+            if (per > 0) {
+                const int2 r = page_range(word_offs, p, n);
+                v = (r.y - r.x + per - 1) / per;
+            } else {
+                v = min(max(vals[p], 0), n);
+            }
+        }
+        __syncthreads();
+        s_scan[t] = v;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
+            const int add = t >= o ? s_scan[t - o] : 0;
+            __syncthreads();
+            s_scan[t] += add;
+            __syncthreads();
+        }
+        if (p < B) out[p] = base + s_scan[t] - v;
+        base += s_scan[255];
+    }
+    if (t == 0) out[B] = base;
+}
+
+// k_line_links for the words of one page per workgroup: the same walk in index order and the same arithmetic, over word_offs[p] .. word_offs[p + 1]
+// only, so a word of another page is never a candidate and the work is the sum of n_p^2.
+__global__ __launch_bounds__(kTile) void k_line_links_pages(const float* __restrict__ frames, const int* __restrict__ word_offs, const int* __restrict__ blk_offs, int B,
+                                                            const int* __restrict__ count, long cap, float max_gap, float min_cos, int* __restrict__ chosen,
+                                                            unsigned long long* __restrict__ accept) {
+    __shared__ float4 s_a[kTile], s_b[kTile];
+    const int n = word_count(count, cap);
+    const int k = blockIdx.x;
+    if (k >= blk_offs[B]) return;  // (block-uniform)
+    const int p = page_of_block(blk_offs, B, k);
+    const int2 r = page_range(word_offs, p, n);
+    const int t = threadIdx.x, i = r.x + (k - blk_offs[p]) * kTile + t;
+    float4 fa = make_float4(0.0f, 0.0f, 1.0f, 0.0f), fb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (i < r.y) fa = reinterpret_cast<const float4*>(frames)[2 * (long)i], fb = reinterpret_cast<const float4*>(frames)[2 * (long)i + 1];
+    const float cxi = fa.x, cyi = fa.y, uxi = fa.z, uyi = fa.w, lngi = fb.x, shti = fb.y;
+    const float vxi = -uyi, vyi = uxi;
+    const float halfi = 0.5f * lngi;
+    float best_s = 0.0f;
+    int best_j = -1;
+    for (int j0 = r.x; j0 < r.y; j0 += kTile) {
+        const int m = min(kTile, r.y - j0);
+        __syncthreads();
+        if (t < m) s_a[t] = reinterpret_cast<const float4*>(frames)[2 * (long)(j0 + t)], s_b[t] = reinterpret_cast<const float4*>(frames)[2 * (long)(j0 + t) + 1];
+        __syncthreads();
+#pragma unroll 4
+        for (int q = 0; q < m; ++q) {
+            const float4 ja = s_a[q], jb = s_b[q];
+            const float dx = ja.x - cxi, dy = ja.y - cyi;
+            const float s = dx * uxi + dy * uyi;
+            const float tt = dx * vxi + dy * vyi;
+            const float gap = (s - halfi) - 0.5f * jb.x;
+            const float cs = uxi * ja.z + uyi * ja.w;
+            const bool cand = s > 0.0f && fabsf(tt) <= 0.5f * fminf(shti, jb.y) && gap <= max_gap * fmaxf(shti, jb.y) && cs >= min_cos &&
+                              (dx > 0.0f || (dx == 0.0f && dy > 0.0f));
+            if (cand && (best_j < 0 || s < best_s)) best_s = s, best_j = j0 + q;
+        }
+    }
+    if (i < r.y) {
+        chosen[i] = best_j;
+        if (best_j >= 0) atomicMin(&accept[best_j], ((unsigned long long)__float_as_uint(best_s) << 32) | (unsigned)i);
+    }
+}
+
+// k_line_order per page: the rank of head i among the heads of its own page under (c.y, c.x, word index), left in line_idx[i] for
+// k_line_place_pages; the heads of each page are counted with an integer atomic.
+__global__ __launch_bounds__(kTile) void k_line_order_pages(const float* __restrict__ frames, const int* __restrict__ word_offs, const int* __restrict__ blk_offs, int B,
+                                                            const int* __restrict__ count, long cap, const int* __restrict__ head, int* __restrict__ line_idx,
+                                                            int* __restrict__ heads) {
+    __shared__ float s_cy[kTile], s_cx[kTile];
+    __shared__ int s_is_head[kTile];
+    const int n = word_count(count, cap);
+    const int k = blockIdx.x;
+    if (k >= blk_offs[B]) return;
+    const int p = page_of_block(blk_offs, B, k);
+    const int2 r = page_range(word_offs, p, n);
+    const int t = threadIdx.x, i = r.x + (k - blk_offs[p]) * kTile + t;
+    const bool mine = i < r.y && head[i] == i;
+    float cxi = 0.0f, cyi = 0.0f;
+    if (i < r.y) cxi = frames[8 * (long)i], cyi = frames[8 * (long)i + 1];
+    int before = 0;
+    for (int j0 = r.x; j0 < r.y; j0 += kTile) {
+        const int m = min(kTile, r.y - j0);
+        __syncthreads();
+        if (t < m) {
+            const float2 c = *reinterpret_cast<const float2*>(frames + 8 * (long)(j0 + t));
+            s_cx[t] = c.x, s_cy[t] = c.y, s_is_head[t] = head[j0 + t] == j0 + t;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int q = 0; q < m; ++q) {
+            const float cy = s_cy[q], cx = s_cx[q];
+            const bool less = cy < cyi || (cy == cyi && (cx < cxi || (cx == cxi && j0 + q < i)));
+            before += (s_is_head[q] && less) ? 1 : 0;
+        }
+    }
+    if (mine) {
+        line_idx[i] = before;
+        atomicAdd(&heads[p], 1);  // (integer: the sum does not depend on the order)
+    }
+}
+
+__global__ __launch_bounds__(256) void k_line_place_pages(const int* __restrict__ word_offs, int B, const int* __restrict__ count, long cap, const int* __restrict__ head,
+                                                          const int* __restrict__ len, const int* __restrict__ line_page_offs, int* __restrict__ line_idx,
+                                                          int* __restrict__ len_sorted, int* __restrict__ head_of_line, int* __restrict__ page_of_line) {
+    const int n = word_count(count, cap);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || head[i] != i) return;
+    const int p = page_of_index(word_offs, B, i);
+    const int l = line_page_offs[p] + line_idx[i];
+    if ((unsigned)l >= (unsigned)n) {  // (never, on finite input with ascending offsets)
+        line_idx[i] = 0;
+        return;
+    }
+    line_idx[i] = l;
+    len_sorted[l] = len[i];
+    head_of_line[l] = i;
+    page_of_line[l] = p;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned blocks(long n, int per) { return (unsigned)((n + per - 1) / per); }
 constexpr long kMaxWords = 1L << 24;
+constexpr int kMaxPages = 1 << 20;
 
 }  // namespace
 
@@ -383,6 +571,67 @@ int ocrs_line_quads(const float* quads, const int* count, long cap, const int* n
                        line_quads);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
+}
+
+// ---- page batches: the total word_offs[B] is the device count of the unchanged kernels ----------------------------------------------
+long ocrs_text_lines_pages_ws_bytes(long cap, int B) {
+    return cap > 0 && cap <= kMaxWords && B > 0 && B <= kMaxPages ? ws_cap(cap) * kWsBytesPerWord + 2 * ws_cap(B + 1) * 4 : 0;
+}
+
+int ocrs_line_links_pages(const float* quads, const int* word_offs, int B, long cap, float max_gap, float min_cos, int* next_word, void* ws, long ws_bytes,
+                          hipStream_t st) {
+    OCRS_CHECK_ARG(cap >= 0 && cap <= kMaxWords && B >= 0 && B <= kMaxPages);
+    if (cap == 0 || B == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(quads && word_offs && next_word && ws && aligned16(quads) && aligned16(ws) && ws_bytes >= ocrs_text_lines_pages_ws_bytes(cap, B));
+    const LinesWs w = ws_split(ws, cap);
+    const PagesWs pw = ws_split_pages(ws, cap, B);
+    const int* count = word_offs + B;
+    const unsigned page_blocks = blocks(cap, kTile) + (unsigned)B;  // >= the sum of ceil(n_p / kTile)
+    hipLaunchKernelGGL(k_line_frames, dim3(blocks(cap, 256)), dim3(256), 0, st, quads, count, cap, w.frames, w.accept, w.len_sorted, w.head_of_line);
+    hipLaunchKernelGGL(k_pages_init, dim3(blocks(cap > B ? cap : B, 256)), dim3(256), 0, st, count, cap, B, w.chosen, w.line_idx, pw.heads);
+    hipLaunchKernelGGL(k_page_scan, dim3(1), dim3(256), 0, st, word_offs, (const int*)nullptr, count, cap, B, kTile, pw.blk_offs);
+    hipLaunchKernelGGL(k_line_links_pages, dim3(page_blocks), dim3(kTile), 0, st, (const float*)w.frames, word_offs, (const int*)pw.blk_offs, B, count, cap, max_gap,
+                       min_cos, w.chosen, w.accept);
+    hipLaunchKernelGGL(k_line_resolve, dim3(blocks(cap, 256)), dim3(256), 0, st, count, cap, (const int*)w.chosen, (const unsigned long long*)w.accept, next_word,
+                       w.pa, w.da);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+int ocrs_line_rank_pages(const int* word_offs, int B, long cap, const int* next_word, void* ws, long ws_bytes, hipStream_t st) {
+    OCRS_CHECK_ARG(cap >= 0 && cap <= kMaxWords && B >= 0 && B <= kMaxPages);
+    if (cap == 0 || B == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(word_offs && ws_bytes >= ocrs_text_lines_pages_ws_bytes(cap, B));
+    return ocrs_line_rank(word_offs + B, cap, next_word, ws, ws_bytes, st);  // links never leave a page: the chains are the flat array's
+}
+
+int ocrs_line_order_pages(const int* word_offs, int B, long cap, int* n_lines, int* line_of_word, int* word_order, int* line_offsets, int* line_page_offs,
+                          int* page_of_line, void* ws, long ws_bytes, hipStream_t st) {
+    OCRS_CHECK_ARG(cap >= 0 && cap <= kMaxWords && B >= 0 && B <= kMaxPages);
+    if (cap == 0 || B == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(word_offs && n_lines && line_offsets && line_of_word && word_order && line_page_offs && page_of_line && ws && aligned16(ws) &&
+                   ws_bytes >= ocrs_text_lines_pages_ws_bytes(cap, B));
+    const LinesWs w = ws_split(ws, cap);
+    const PagesWs pw = ws_split_pages(ws, cap, B);
+    const int* count = word_offs + B;
+    hipLaunchKernelGGL(k_line_order_pages, dim3(blocks(cap, kTile) + (unsigned)B), dim3(kTile), 0, st, (const float*)w.frames, word_offs, (const int*)pw.blk_offs, B,
+                       count, cap, (const int*)w.head, w.line_idx, pw.heads);
+    hipLaunchKernelGGL(k_page_scan, dim3(1), dim3(256), 0, st, word_offs, (const int*)pw.heads, count, cap, B, 0, line_page_offs);
+    hipLaunchKernelGGL(k_line_place_pages, dim3(blocks(cap, 256)), dim3(256), 0, st, word_offs, B, count, cap, (const int*)w.head, (const int*)w.len,
+                       (const int*)line_page_offs, w.line_idx, w.len_sorted, w.head_of_line, page_of_line);
+    hipLaunchKernelGGL(k_line_scan, dim3(1), dim3(256), 0, st, count, cap, (const int*)w.head, (const int*)w.len_sorted, line_offsets, n_lines);
+    hipLaunchKernelGGL(k_line_scatter, dim3(blocks(cap, 256)), dim3(256), 0, st, count, cap, (const int*)w.head, (const int*)w.rank, (const int*)w.line_idx,
+                       (const int*)line_offsets, line_of_word, word_order);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+int ocrs_line_quads_pages(const float* quads, const int* word_offs, int B, long cap, const int* n_lines, const int* line_offsets, const int* word_order,
+                          float* line_quads, void* ws, long ws_bytes, hipStream_t st) {
+    OCRS_CHECK_ARG(cap >= 0 && cap <= kMaxWords && B >= 0 && B <= kMaxPages);
+    if (cap == 0 || B == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(word_offs && ws_bytes >= ocrs_text_lines_pages_ws_bytes(cap, B));
+    return ocrs_line_quads(quads, word_offs + B, cap, n_lines, line_offsets, word_order, line_quads, ws, ws_bytes, st);  // a line's words are one page's
 }
 
 }  // extern "C"

@@ -36,6 +36,11 @@ pixel k, as ``extract_cc_quads`` produces them.
 Lines.  ``find_lines`` groups the word quads into text lines in reading order (csrc/text_lines.hip, C ABI section "text lines"; the rule is
 stated once in DESIGN.md §14 and restated for the tests in tests/lines_ref.py) without a host synchronisation, and ``ocr_lines`` is
 ``ocr_page`` with that stage in between: one crop and one string per line, the recogniser's training unit, with the same three waits.
+
+Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
+zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
+for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
+per page.  The single-page functions above are what its tests compare it with.
 """
 from __future__ import annotations
 
@@ -278,6 +283,8 @@ class TextLines:
     word_order: torch.Tensor    # (N,) int32
     line_offsets: torch.Tensor  # (N+1,) int32
     next_word: torch.Tensor     # (N,) int32
+    line_page_offs: torch.Tensor | None = None  # (B+1,) int32, find_lines_pages only: the lines of page p are line_page_offs[p]:line_page_offs[p+1]
+    page_of_line: torch.Tensor | None = None    # (N,) int32, find_lines_pages only: rows up to L
 
 
 def _empty_lines(n: int, device) -> TextLines:
@@ -357,3 +364,245 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thres
     if det["n"] == 0:
         return []
     return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos)
+
+
+# ------------------------------------------------------------------ page batches ---------------------------------------------------------
+def _to_device_async(values, dtype, device) -> torch.Tensor:
+    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
+
+
+def _check_pages(pages, who: str):
+    """the pages of a batch: (1,H,W) uint8 tensors on one device"""
+    pages = list(pages)
+    for p in pages:
+        if not isinstance(p, torch.Tensor):
+            raise RuntimeError(f"{who}: expected a list of (1,H,W) uint8 device pages")
+        _need_cuda(p, who)
+        if p.dtype != torch.uint8 or p.dim() != 3 or p.shape[0] != 1 or p.shape[1] < 1 or p.shape[2] < 1:
+            raise RuntimeError(f"{who}: expected (1,H,W) uint8 pages")
+        if p.device != pages[0].device:
+            raise RuntimeError(f"{who}: the pages of a batch must be on one device")
+    return pages
+
+
+def pack_pages(pages):
+    """A list of (1,H_p,W_p) uint8 device pages -> ``(pages_packed, page_offs, page_sizes)``: the pages back to back in one uint8 buffer
+    (one device-to-device copy each), their byte offsets (B,) int64 and their ``(h, w)`` (B,2) int32 on the device -- the layout of the page
+    stores of ``datasets.py``.  No synchronisation."""
+    pages = _check_pages(pages, "pack_pages")
+    if not pages:
+        raise RuntimeError("pack_pages: expected at least one page")
+    dev = pages[0].device
+    sizes = [(int(p.shape[1]), int(p.shape[2])) for p in pages]
+    offs, off = [], 0
+    for h, w in sizes:
+        offs.append(off)
+        off += h * w
+    packed = torch.empty(off, dtype=torch.uint8, device=dev)
+    for p, o, (h, w) in zip(pages, offs, sizes):
+        packed[o:o + h * w].view(1, h, w).copy_(p)
+    return packed, _to_device_async(offs, torch.int64, dev), _to_device_async(sizes, torch.int32, dev)
+
+
+def binarize_resize_pages(probs: torch.Tensor, page_sizes: torch.Tensor, canvas, threshold: float = 0.5) -> torch.Tensor:
+    """(B,h,w) fp32 probabilities and (B,2) int32 device page sizes ``(H_p, W_p)`` -> the uint8 canvas (B,Hmax,Wmax), ``canvas = (Hmax, Wmax)``
+    at least as large as every page: ``binarize_resize(probs[p], (H_p, W_p))`` in the top left corner of plane p and 0 elsewhere, in one
+    launch that writes the padding too."""
+    _need_cuda(probs, "binarize_resize_pages")
+    _need_cuda(page_sizes, "binarize_resize_pages")
+    if probs.dtype != torch.float32 or probs.dim() != 3:
+        raise RuntimeError("binarize_resize_pages: expected (B,h,w) float32 probabilities")
+    B, h, w = probs.shape
+    if page_sizes.dtype != torch.int32 or tuple(page_sizes.shape) != (B, 2):
+        raise RuntimeError("binarize_resize_pages: page_sizes must be (B,2) int32 on the device")
+    Hmax, Wmax = int(canvas[0]), int(canvas[1])
+    out = torch.empty(B, Hmax, Wmax, dtype=torch.uint8, device=probs.device)
+    lib().binarize_resize_pages(ptr(probs.contiguous()), ptr(page_sizes.contiguous()), ptr(out), B, h, w, Hmax, Wmax, float(threshold))
+    return out
+
+
+def gather_page_quads(quads: torch.Tensor, counts: torch.Tensor):
+    """Quads (B,cap,4,2) fp32 with device counts (B,) int32, as ``ocrs_cc_quads`` writes them -> ``(flat quads (N_total,4,2), page_of_word
+    (N_total,) int32, word_offs (B+1,) int32, counts as a host list)``: the rows of every page back to back in their own (raster) order.
+    Reading ``word_offs`` to size the flat rows is the one host synchronisation; it stands for the B waits for component counts."""
+    _need_cuda(quads, "gather_page_quads")
+    _need_cuda(counts, "gather_page_quads")
+    if quads.dtype != torch.float32 or quads.dim() != 4 or tuple(quads.shape[2:]) != (4, 2):
+        raise RuntimeError("gather_page_quads: expected (B,cap,4,2) float32 quads")
+    B, cap = quads.shape[:2]
+    if counts.dtype != torch.int32 or counts.numel() != B:
+        raise RuntimeError("gather_page_quads: counts must be int32 with one entry per page")
+    q, counts = quads.contiguous(), counts.contiguous()
+    L = lib()
+    word_offs = torch.empty(B + 1, dtype=torch.int32, device=q.device)
+    L.gather_page_quads(ptr(q), ptr(counts), B, cap, None, None, ptr(word_offs), 0)
+    offs_h = _to_host_async(word_offs)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(q.device))
+    done.synchronize()  # (waits for the copy only, not for whatever else the stream holds)
+    offs = offs_h.tolist()
+    n = offs[B]
+    flat = torch.empty(n, 4, 2, dtype=torch.float32, device=q.device)
+    page_of_word = torch.empty(n, dtype=torch.int32, device=q.device)
+    if n:
+        L.gather_page_quads(ptr(q), ptr(counts), B, cap, ptr(flat), ptr(page_of_word), ptr(word_offs), n)
+    return flat, page_of_word, word_offs, [b - a for a, b in zip(offs, offs[1:])]
+
+
+def _cc_quads_pages_sizes(B: int, H: int, W: int):
+    L = lib()
+    ws_bytes, cap = L.cc_quads_ws_bytes(B, H, W), L.cc_quads_capacity(H, W)
+    if ws_bytes <= 0 or B > 65535 or B * cap >= 2 ** 31:
+        raise ValueError(f"a batch of {B} masks of {H}x{W} is not supported")
+    return ws_bytes, cap
+
+
+def cc_quads_pages(text_masks: torch.Tensor):
+    """``extract_cc_quads_device`` for the (B,Hmax,Wmax) uint8 canvas of ``binarize_resize_pages``: ``ocrs_cc_quads`` on the whole canvas, then
+    ``gather_page_quads`` -> ``(quads (N_total,4,2), page_of_word, word_offs, counts)``.  The padding is background, so page p's rows are the
+    quads of its own mask in their own order.  One host synchronisation."""
+    _need_cuda(text_masks, "cc_quads_pages")
+    if text_masks.dtype != torch.uint8 or text_masks.dim() != 3:
+        raise RuntimeError("cc_quads_pages: expected a (B,Hmax,Wmax) uint8 canvas")
+    B, H, W = text_masks.shape
+    ws_bytes, cap = _cc_quads_pages_sizes(B, H, W)
+    m = text_masks.contiguous()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=m.device)
+    ncomp = torch.empty(B, dtype=torch.int32, device=m.device)
+    raw = torch.empty(B, cap, 4, 2, dtype=torch.float32, device=m.device)
+    lib().cc_quads(ptr(m), 1, 0.5, B, H, W, ptr(ncomp), ptr(raw), None, ptr(ws))
+    return gather_page_quads(raw, ncomp)
+
+
+def detect_words_batch(model, pages, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE) -> dict:
+    """``detect_words`` for a list of (1,H_p,W_p) uint8 device pages of any sizes: one eval forward of the (B,1,h,w) batch of
+    ``resize(transform_image(page), size)``, the masks of all pages in one zero-padded canvas, ``ocrs_cc_quads`` on the canvas, the quads
+    compacted and expanded.  -> ``probs`` (B,h,w), ``text_masks`` (B,Hmax,Wmax) uint8, ``quads`` (N_total,4,2) grouped by page in raster order,
+    ``page_of_word`` (N_total,) int32, ``word_offs`` (B+1,) int32 and ``counts``, the words per page as a host list.  One host synchronisation
+    (the word offsets).  A canvas ``ocrs_cc_quads`` cannot take raises ValueError, as ``extract_cc_quads_device`` does."""
+    pages = _check_pages(pages, "detect_words_batch")
+    if not pages:
+        raise RuntimeError("detect_words_batch: expected at least one page")
+    if model.training:
+        raise RuntimeError("detect_words_batch: the model must be in eval mode (model.eval())")
+    dev = pages[0].device
+    sizes = [(int(p.shape[1]), int(p.shape[2])) for p in pages]
+    canvas = (max(h for h, _ in sizes), max(w for _, w in sizes))
+    _cc_quads_pages_sizes(len(pages), *canvas)  # (refuses the batch before anything is launched)
+    img = torch.stack([resize(transform_image(p), size) for p in pages])
+    with torch.inference_mode():
+        probs = model(img)[:, 0]
+    text_masks = binarize_resize_pages(probs, _to_device_async(sizes, torch.int32, dev), canvas, threshold)
+    flat, page_of_word, word_offs, counts = cc_quads_pages(text_masks)
+    quads = expand_quads(flat, expand) if flat.shape[0] else flat
+    return {"probs": probs, "text_masks": text_masks, "quads": quads, "page_of_word": page_of_word, "word_offs": word_offs, "counts": counts}
+
+
+def find_lines_pages(quads: torch.Tensor, page_of_word: torch.Tensor, word_offs: torch.Tensor, max_gap: float = 2.0, min_cos: float = 0.9) -> TextLines:
+    """``find_lines`` over the flat words of B pages (``detect_words_batch``'s ``quads``, ``page_of_word`` and ``word_offs``): the rule of
+    DESIGN.md §14 with two additions -- a word links only to words of its own page, and lines are ordered by (page, centre y, centre x, word
+    index) of their first word.  Indices in the result count through the flat arrays; ``line_page_offs`` (B+1,) and ``page_of_line`` say which
+    lines are which page's.  The kernels stage only the words of a workgroup's own page, so the work is the sum of n_p^2.  No host
+    synchronisation; N == 0 launches nothing."""
+    for t in (quads, page_of_word, word_offs):
+        _need_cuda(t, "find_lines_pages")
+    if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
+        raise RuntimeError("find_lines_pages: expected (N,4,2) float32 quads")
+    n = quads.shape[0]
+    if page_of_word.dtype != torch.int32 or tuple(page_of_word.shape) != (n,):
+        raise RuntimeError("find_lines_pages: page_of_word must be (N,) int32")
+    if word_offs.dtype != torch.int32 or word_offs.dim() != 1 or word_offs.numel() < 2:
+        raise RuntimeError("find_lines_pages: word_offs must be (B+1,) int32 with B >= 1")
+    B = word_offs.numel() - 1
+    q, offs = quads.contiguous(), word_offs.contiguous()
+    out = _empty_lines(n, q.device)
+    i32 = dict(dtype=torch.int32, device=q.device)
+    out.line_page_offs = torch.empty(B + 1, **i32) if n else torch.zeros(B + 1, **i32)
+    out.page_of_line = torch.empty(n, **i32)
+    if n == 0:
+        return out
+    L = lib()
+    ws_bytes = L.text_lines_pages_ws_bytes(n, B)
+    if ws_bytes <= 0:
+        raise RuntimeError(f"find_lines_pages: {n} words on {B} pages are not supported")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+    L.line_links_pages(ptr(q), ptr(offs), B, n, float(max_gap), float(min_cos), ptr(out.next_word), ptr(ws), ws_bytes)
+    L.line_rank_pages(ptr(offs), B, n, ptr(out.next_word), ptr(ws), ws_bytes)
+    L.line_order_pages(ptr(offs), B, n, ptr(out.n_lines), ptr(out.line_of_word), ptr(out.word_order), ptr(out.line_offsets), ptr(out.line_page_offs),
+                       ptr(out.page_of_line), ptr(ws), ws_bytes)
+    L.line_quads_pages(ptr(q), ptr(offs), B, n, ptr(out.n_lines), ptr(out.line_offsets), ptr(out.word_order), ptr(out.quads), ptr(ws), ws_bytes)
+    return out
+
+
+def rectify_crops_pages(pages_packed: torch.Tensor, page_offs: torch.Tensor, page_sizes: torch.Tensor, quads: torch.Tensor, page_of_quad: torch.Tensor,
+                        plan: CropPlan) -> torch.Tensor:
+    """``rectify_crops`` from a page store (``pack_pages``): crop i is cut out of page ``page_of_quad[i]`` -- ``page_of_line`` for line crops,
+    ``page_of_word`` for word crops.  One launch for the crops of all pages; a crop's values are those ``rectify_crops`` gives it on its own page."""
+    for t in (pages_packed, page_offs, page_sizes, quads, page_of_quad):
+        _need_cuda(t, "rectify_crops_pages")
+    if pages_packed.dtype != torch.uint8 or pages_packed.dim() != 1:
+        raise RuntimeError("rectify_crops_pages: expected the flat uint8 buffer of pack_pages")
+    B = page_offs.numel()
+    if page_offs.dtype != torch.int64 or page_sizes.dtype != torch.int32 or tuple(page_sizes.shape) != (B, 2):
+        raise RuntimeError("rectify_crops_pages: page_offs must be (B,) int64 and page_sizes (B,2) int32")
+    if quads.dtype != torch.float32 or quads.dim() != 3 or quads.shape[0] != plan.table.shape[0]:
+        raise RuntimeError("rectify_crops_pages: quads must be the (N,4,2) float32 quads the plan was made from")
+    if page_of_quad.dtype != torch.int32 or tuple(page_of_quad.shape) != (quads.shape[0],):
+        raise RuntimeError("rectify_crops_pages: page_of_quad must be (N,) int32")
+    _, packed_floats, _, tiles = plan.host()[:4]
+    q = quads.contiguous()
+    packed = torch.empty(packed_floats, dtype=torch.float32, device=q.device)
+    lib().rectify_crops_pages(ptr(pages_packed.contiguous()), pages_packed.numel(), ptr(page_offs.contiguous()), ptr(page_sizes.contiguous()), B, ptr(q),
+                              ptr(page_of_quad.contiguous()), ptr(plan.table), ptr(plan.totals), tiles, ptr(packed), packed_floats)
+    return packed
+
+
+def split_by_page(items: list, offs: list) -> list[list]:
+    """flat results grouped by page -> one list per page: ``items[offs[p]:offs[p + 1]]`` (``offs``: B + 1 ascending host offsets)"""
+    if any(b < a for a, b in zip(offs, offs[1:])) or (offs and (offs[0] != 0 or offs[-1] != len(items))):
+        raise RuntimeError("split_by_page: the offsets must ascend from 0 to the number of items")
+    return [items[a:b] for a, b in zip(offs, offs[1:])]
+
+
+def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
+              output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
+              min_cos: float = 0.9) -> list[list[dict]]:
+    """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
+    (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
+    ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
+    crop's chunk, and with it the padded width the recogniser sees, depends on the whole batch.  Three host synchronisations
+    for the batch: the word offsets, the plan's totals (the line count and ``line_page_offs`` travel with them) and the labels.  A page
+    without words yields ``[]``; a batch without words returns without launching the recogniser; ``pages == []`` launches nothing."""
+    pages = _check_pages(pages, "ocr_pages")
+    if not pages:
+        return []
+    B = len(pages)
+    det = detect_words_batch(det_model, pages, size, threshold, expand)
+    words = det["quads"]
+    if words.shape[0] == 0:
+        return [[] for _ in range(B)]
+    packed_pages, page_offs, page_sizes = pack_pages(pages)
+    word_offs_h = [0]
+    for c in det["counts"]:
+        word_offs_h.append(word_offs_h[-1] + c)
+    if lines:
+        tl = find_lines_pages(words, det["page_of_word"], det["word_offs"], max_gap, min_cos)
+        plan = crop_plan(tl.quads, output_height, tl.n_lines)
+        lpo_h = _to_host_async(tl.line_page_offs)  # queued ahead of the plan's totals: it has arrived when they have
+        packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, tl.quads, tl.page_of_line, plan)
+    else:
+        plan = crop_plan(words, output_height)
+        packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, words, det["page_of_word"], plan)
+    batches = crops_to_batches(packed, plan, max_batch, width_unit)
+    # quads and line tables travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have
+    words_h = _to_host_async(words)
+    if lines:
+        n_lines = plan.host()[0]
+        lq_h, order_h, offs_h = (_to_host_async(t) for t in (tl.quads, tl.word_order, tl.line_offsets))
+    texts = recognize_crops(rec_model, batches, alphabet)
+    wl = words_h.tolist()
+    if not lines:
+        return split_by_page([{"quad": q, "text": t} for q, t in zip(wl, texts)], word_offs_h)
+    order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
+    flat = [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+    return split_by_page(flat, lpo_h.tolist())
