@@ -312,7 +312,6 @@ __global__ __launch_bounds__(256) void k_aug_line_v(const long long* __restrict_
     store4(out + ((size_t)b * OH + oy) * Wpad + x0, v[0], v[1], v[2], v[3]);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ws = [B][planes][kStatChunks] fp64 partials, then [B][planes] fp32 contrast terms (rounded up to 4 floats)
 long stats_ws_floats(int B, int planes) { return (long)B * planes * kStatChunks * 2 + ((long)B * planes + 3) / 4 * 4; }

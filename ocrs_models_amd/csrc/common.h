@@ -21,6 +21,9 @@
 
 static constexpr int kNumCU = 256;
 
+// the vector accesses of the kernels (float4 / int4 / uint4) need 16-byte aligned bases: checked by the launchers
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // ----------------------------------------------------------------------------------------------
 // storage types: activations live in HBM as NHWC, either fp32 or bf16; all arithmetic is fp32.
 // ----------------------------------------------------------------------------------------------

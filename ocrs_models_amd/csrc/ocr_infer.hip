@@ -10,7 +10,8 @@
 // Page batches: the same stages for B pages of different sizes at once.
 //   k_binarize_resize_pages     k_binarize_resize_nearest per page into one zero-padded (B, Hmax, Wmax) canvas, padding included
 //   k_gather_page_quads         (B, cap) quads with counts -> flat rows grouped by page, page_of_word, word_offs
-//   k_rectify_crops_pages       k_rectify_crops with the page looked up per crop in a packed page store
+//   k_rectify_crops_pages       k_rectify_crops with the page looked up per crop in a packed page store; both find the crop with
+//                               crop_of_tile() and sample it with rectify_tile(), the one statement of the sampler
 //
 // All of them are small and byte-bound: no LDS tiles, no MFMA; coalesced 4..16-byte vector accesses; every count stays on the device.
 #include "input_pipe.h"
@@ -273,22 +274,24 @@ __global__ __launch_bounds__(256) void k_crop_plan(const float* __restrict__ qua
 // One workgroup = one tile of kTileElems consecutive elements of one crop; the crop is found by bisecting the plan's tile prefix and its
 // frame is computed once (wave-uniform: scalar registers).  One lane = 4 consecutive samples -> one 16-byte store; the taps are byte loads
 // of the page, which stays in L2 (a page is a few MB).
-__global__ __launch_bounds__(256) void k_rectify_crops(const uint8_t* __restrict__ page, int H, int W, const float* __restrict__ quads,
-                                                       const int* __restrict__ plan, const long long* __restrict__ totals, float* __restrict__ packed,
-                                                       long packed_floats) {
-    const long long tile = blockIdx.x;
-    const long n = (long)totals[0];
-    if (n <= 0 || tile >= totals[3]) return;
+
+// the last of the n > 0 crops whose first tile is <= tile
+__device__ __forceinline__ long crop_of_tile(const int* __restrict__ plan, long n, long long tile) {
     long lo = 0, hi = n - 1;
-    while (lo < hi) {  // the last crop whose first tile is <= tile
+    while (lo < hi) {
         const long mid = (lo + hi + 1) >> 1;
         if (plan[mid * 8 + 5] <= tile) lo = mid; else hi = mid - 1;
     }
-    const CropFrame f = crop_frame(quads + lo * 8);
-    const int4 pl = *reinterpret_cast<const int4*>(plan + lo * 8);  // h, w, ow, packed offset
+    return lo;
+}
+// The sampler: this lane's 4 samples of tile `tile` of crop `crop`, taken from the (H, W) page.
+__device__ __forceinline__ void rectify_tile(const uint8_t* __restrict__ page, int H, int W, const float* __restrict__ quads, const int* __restrict__ plan, long crop,
+                                             long long tile, float* __restrict__ packed, long packed_floats) {
+    const CropFrame f = crop_frame(quads + crop * 8);
+    const int4 pl = *reinterpret_cast<const int4*>(plan + crop * 8);  // h, w, ow, packed offset
     const int h = pl.x, w = pl.y;
     const long hw = (long)h * w;
-    const long e0 = (long)(tile - plan[lo * 8 + 5]) * kTileElems + threadIdx.x * 4;
+    const long e0 = (long)(tile - plan[crop * 8 + 5]) * kTileElems + threadIdx.x * 4;
     if (e0 >= hw || (long)pl.w + e0 + 4 > packed_floats) return;
     const float vx = -f.uy, vy = f.ux;
     const float xmax = (float)(W - 1), ymax = (float)(H - 1);
@@ -316,9 +319,17 @@ __global__ __launch_bounds__(256) void k_rectify_crops(const uint8_t* __restrict
     *reinterpret_cast<float4*>(packed + pl.w + e0) = make_float4(out[0], out[1], out[2], out[3]);
 }
 
-// The same from a store of pages: crop lo comes from page page_of_quad[lo], whose pointer and size are looked up once per workgroup
-// (wave-uniform, like the frame).  The sampling below is k_rectify_crops' text, operation for operation: a crop's bytes are those it gets
-// from ocrs_rectify_crops on its own page.
+__global__ __launch_bounds__(256) void k_rectify_crops(const uint8_t* __restrict__ page, int H, int W, const float* __restrict__ quads,
+                                                       const int* __restrict__ plan, const long long* __restrict__ totals, float* __restrict__ packed,
+                                                       long packed_floats) {
+    const long long tile = blockIdx.x;
+    const long n = (long)totals[0];
+    if (n <= 0 || tile >= totals[3]) return;
+    rectify_tile(page, H, W, quads, plan, crop_of_tile(plan, n, tile), tile, packed, packed_floats);
+}
+
+// The same from a store of pages: the crop comes from page page_of_quad[crop], whose pointer and size are looked up once per workgroup
+// (wave-uniform, like the frame), so a crop's bytes are those it gets from ocrs_rectify_crops on its own page.
 __global__ __launch_bounds__(256) void k_rectify_crops_pages(const uint8_t* __restrict__ pages, long pages_bytes, const long long* __restrict__ page_offs,
                                                              const int* __restrict__ page_sizes, int B, const float* __restrict__ quads,
                                                              const int* __restrict__ page_of_quad, const int* __restrict__ plan,
@@ -326,47 +337,13 @@ __global__ __launch_bounds__(256) void k_rectify_crops_pages(const uint8_t* __re
     const long long tile = blockIdx.x;
     const long n = (long)totals[0];
     if (n <= 0 || tile >= totals[3]) return;
-    long lo = 0, hi = n - 1;
-    while (lo < hi) {  // the last crop whose first tile is <= tile
-        const long mid = (lo + hi + 1) >> 1;
-        if (plan[mid * 8 + 5] <= tile) lo = mid; else hi = mid - 1;
-    }
-    const int pg = page_of_quad[lo];
+    const long crop = crop_of_tile(plan, n, tile);
+    const int pg = page_of_quad[crop];
     if ((unsigned)pg >= (unsigned)B) return;
     const int H = page_sizes[2 * pg], W = page_sizes[2 * pg + 1];
     const long long poff = page_offs[pg];
     if (H <= 0 || W <= 0 || poff < 0 || poff + (long long)H * W > pages_bytes) return;  // a page that is not inside the store is not read
-    const uint8_t* page = pages + poff;
-    const CropFrame f = crop_frame(quads + lo * 8);
-    const int4 pl = *reinterpret_cast<const int4*>(plan + lo * 8);  // h, w, ow, packed offset
-    const int h = pl.x, w = pl.y;
-    const long hw = (long)h * w;
-    const long e0 = (long)(tile - plan[lo * 8 + 5]) * kTileElems + threadIdx.x * 4;
-    if (e0 >= hw || (long)pl.w + e0 + 4 > packed_floats) return;
-    const float vx = -f.uy, vy = f.ux;
-    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
-    float out[4];
-    int y = (int)(e0 / w), x = (int)(e0 - (long)y * w);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float val = 0.0f;
-        if (e0 + k < hw) {
-            const float su = ((float)x + 0.5f) / (float)w * f.lng, sv = ((float)y + 0.5f) / (float)h * f.sht;
-            float px = f.ox + su * f.ux + sv * vx, py = f.oy + su * f.uy + sv * vy;
-            px = fminf(fmaxf(px, 0.0f), xmax), py = fminf(fmaxf(py, 0.0f), ymax);  // border padding
-            const int x0 = (int)px, y0 = (int)py;
-            const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-            const float fx = px - (float)x0, fy = py - (float)y0;
-            const uint8_t* r0 = page + (size_t)y0 * W;
-            const uint8_t* r1 = page + (size_t)y1 * W;
-            const float a = px_u8(r0[x0]), b = px_u8(r0[x1]), c = px_u8(r1[x0]), d = px_u8(r1[x1]);
-            const float top = a + (b - a) * fx, bot = c + (d - c) * fx;
-            val = top + (bot - top) * fy;
-            if (++x == w) x = 0, ++y;
-        }
-        out[k] = val;
-    }
-    *reinterpret_cast<float4*>(packed + pl.w + e0) = make_float4(out[0], out[1], out[2], out[3]);
+    rectify_tile(pages + poff, H, W, quads, plan, crop, tile, packed, packed_floats);
 }
 
 // ---- antialiased resize of the packed crops into padded batches ------------------------------------------------------------------
@@ -403,8 +380,6 @@ __global__ __launch_bounds__(256) void k_resize_aa_packed_v(const float* __restr
     const float* src = ws + hoff + (size_t)s.lo * ow;
     for (int x = threadIdx.x; x < Wpad; x += 256) out[row + x] = x < ow ? aa_dot(s, src + x, ow) : 0.0f;  // pad value 0.0 (train_rec.py:295)
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

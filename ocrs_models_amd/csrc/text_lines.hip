@@ -15,11 +15,13 @@
 // the words of its own page and lines are ordered by (page, c.y, c.x, word index); frames, resolve, rank, scan, scatter and quads run unchanged
 // on the flat array with the total word_offs[B] as their device count.
 //   k_pages_init         chosen = -1, line_idx = 0 (words that no page covers stay in bounds), per-page head counters = 0
-//   k_page_blocks        blk_offs [B + 1]: exclusive scan of ceil(n_p / 256), the workgroups of each page; one workgroup
+//   k_page_scan          blk_offs [B + 1]: exclusive scan of ceil(n_p / 256), the workgroups of each page; one workgroup
 //   k_line_links_pages   k_line_links with one page per workgroup: only that page's frames are staged
 //   k_line_order_pages   k_line_order likewise -> rank of each head among its page's heads, heads counted per page
-//   k_page_scan          line_page_offs [B + 1]: exclusive scan of the head counts; one workgroup
+//   k_page_scan          (again) line_page_offs [B + 1]: exclusive scan of the head counts
 //   k_line_place_pages   line index = line_page_offs[page] + rank in the page; len_sorted, head_of_line, page_of_line
+// The two links kernels share their walk, nearest_follower() over a word range [lo, hi): k_line_links passes [0, n), the paged kernel its
+// workgroup's page; they differ only in how they find the range.  The two order kernels are still two texts of one count (see k_line_order_pages).
 //
 // All decision arithmetic is fp32 with one rounding per operation (no fused multiply-add), so the restatement follows it operation by
 // operation.  No float atomics: the only atomic is an integer minimum whose result does not depend on the order of arrival.
@@ -81,24 +83,24 @@ __global__ __launch_bounds__(256) void k_line_frames(const float* __restrict__ q
 }
 
 // ---- links -----------------------------------------------------------------------------------------------------------------------
-// Lane i walks every word j in index order (a tile of 256 frames per step, read from LDS at one address per step: a broadcast) and keeps
-// the candidate with the smallest s; the strict `<` keeps the smallest j on a tie.  The chosen word then learns of i through
-// atomicMin(bits(s) << 32 | i): s > 0, so its bit pattern orders as its value, and the low word breaks ties by the smallest chooser.
-__global__ __launch_bounds__(kTile) void k_line_links(const float* __restrict__ frames, const int* __restrict__ count, long cap, float max_gap, float min_cos,
-                                                      int* __restrict__ chosen, unsigned long long* __restrict__ accept) {
+// Lane i walks every word j of [lo, hi) in index order (a tile of 256 frames per step, read from LDS at one address per step: a broadcast)
+// and keeps the candidate with the smallest s; the strict `<` keeps the smallest j on a tie.  Called by all 256 lanes of a workgroup with
+// the same range; a lane whose i is no word walks along for the staging and its result is not used.
+struct Link {
+    float s;  // distance along i's long axis to the chosen word (> 0); meaningless when j < 0
+    int j;    // the chosen word, or -1
+};
+__device__ __forceinline__ Link nearest_follower(const float* __restrict__ frames, int lo, int hi, int i, bool is_word, float max_gap, float min_cos) {
     __shared__ float4 s_a[kTile], s_b[kTile];
-    const int n = word_count(count, cap);
-    const int t = threadIdx.x, i = blockIdx.x * kTile + t;
-    if (blockIdx.x * kTile >= n) return;  // (block-uniform)
+    const int t = threadIdx.x;
     float4 fa = make_float4(0.0f, 0.0f, 1.0f, 0.0f), fb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (i < n) fa = reinterpret_cast<const float4*>(frames)[2 * (long)i], fb = reinterpret_cast<const float4*>(frames)[2 * (long)i + 1];
+    if (is_word) fa = reinterpret_cast<const float4*>(frames)[2 * (long)i], fb = reinterpret_cast<const float4*>(frames)[2 * (long)i + 1];
     const float cxi = fa.x, cyi = fa.y, uxi = fa.z, uyi = fa.w, lngi = fb.x, shti = fb.y;
     const float vxi = -uyi, vyi = uxi;
     const float halfi = 0.5f * lngi;
-    float best_s = 0.0f;
-    int best_j = -1;
-    for (int j0 = 0; j0 < n; j0 += kTile) {
-        const int m = min(kTile, n - j0);
+    Link best = {0.0f, -1};
+    for (int j0 = lo; j0 < hi; j0 += kTile) {
+        const int m = min(kTile, hi - j0);
         __syncthreads();
         if (t < m) s_a[t] = reinterpret_cast<const float4*>(frames)[2 * (long)(j0 + t)], s_b[t] = reinterpret_cast<const float4*>(frames)[2 * (long)(j0 + t) + 1];
         __syncthreads();
@@ -112,13 +114,24 @@ __global__ __launch_bounds__(kTile) void k_line_links(const float* __restrict__ 
             const float cs = uxi * ja.z + uyi * ja.w;
             const bool cand = s > 0.0f && fabsf(tt) <= 0.5f * fminf(shti, jb.y) && gap <= max_gap * fmaxf(shti, jb.y) && cs >= min_cos &&
                               (dx > 0.0f || (dx == 0.0f && dy > 0.0f));
-            if (cand && (best_j < 0 || s < best_s)) best_s = s, best_j = j0 + q;
+            if (cand && (best.j < 0 || s < best.s)) best.s = s, best.j = j0 + q;
         }
     }
-    if (i < n) {
-        chosen[i] = best_j;
-        if (best_j >= 0) atomicMin(&accept[best_j], ((unsigned long long)__float_as_uint(best_s) << 32) | (unsigned)i);
-    }
+    return best;
+}
+// Word i records its choice, and the chosen word learns of i through atomicMin(bits(s) << 32 | i): s > 0, so its bit pattern orders as its
+// value, and the low word breaks ties by the smallest chooser.
+__device__ __forceinline__ void store_link(int i, Link best, int* __restrict__ chosen, unsigned long long* __restrict__ accept) {
+    chosen[i] = best.j;
+    if (best.j >= 0) atomicMin(&accept[best.j], ((unsigned long long)__float_as_uint(best.s) << 32) | (unsigned)i);
+}
+__global__ __launch_bounds__(kTile) void k_line_links(const float* __restrict__ frames, const int* __restrict__ count, long cap, float max_gap, float min_cos,
+                                                      int* __restrict__ chosen, unsigned long long* __restrict__ accept) {
+    const int n = word_count(count, cap);
+    const int i = blockIdx.x * kTile + threadIdx.x;
+    if (blockIdx.x * kTile >= n) return;  // (block-uniform)
+    const Link best = nearest_follower(frames, 0, n, i, i < n, max_gap, min_cos);
+    if (i < n) store_link(i, best, chosen, accept);
 }
 
 // A link i -> j exists iff i chose j and j accepted i.  Start of the pointer jumping: p = predecessor (itself for a head), d = 1 / 0.
@@ -219,10 +232,26 @@ __global__ __launch_bounds__(kTile) void k_line_order(const float* __restrict__ 
     }
 }
 
+// Inclusive scan of one int per lane over the 256 lanes of a workgroup -> (this lane's prefix, the total of all 256).
+__device__ __forceinline__ int2 block_scan_256(int v) {
+    __shared__ int s_scan[256];
+    const int t = threadIdx.x;
+    __syncthreads();  // (an earlier call's total may still be read)
+    s_scan[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int add = t >= o ? s_scan[t - o] : 0;
+        __syncthreads();
+        s_scan[t] += add;
+        __syncthreads();
+    }
+    return make_int2(s_scan[t], s_scan[255]);
+}
+
 // One workgroup: L = number of heads, then line_offsets[0..L] = exclusive scan of the line lengths in line order, 256 at a time.
 __global__ __launch_bounds__(256) void k_line_scan(const int* __restrict__ count, long cap, const int* __restrict__ head, const int* __restrict__ len_sorted,
                                                    int* __restrict__ line_offsets, int* __restrict__ n_lines) {
-    __shared__ int s_scan[256], s_total;
+    __shared__ int s_total;
     const int n = word_count(count, cap);
     const int t = threadIdx.x;
     if (t == 0) s_total = 0;
@@ -236,17 +265,9 @@ __global__ __launch_bounds__(256) void k_line_scan(const int* __restrict__ count
     for (int l0 = 0; l0 < L; l0 += 256) {
         const int l = l0 + t;
         const int v = l < L ? len_sorted[l] : 0;
-        __syncthreads();
-        s_scan[t] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
-            const int add = t >= o ? s_scan[t - o] : 0;
-            __syncthreads();
-            s_scan[t] += add;
-            __syncthreads();
-        }
-        if (l < L) line_offsets[l] = base + s_scan[t] - v;
-        base += s_scan[255];
+        const int2 sc = block_scan_256(v);
+        if (l < L) line_offsets[l] = base + sc.x - v;
+        base += sc.y;
     }
     if (t == 0) line_offsets[L] = base, *n_lines = L;
 }
@@ -341,21 +362,13 @@ __device__ __forceinline__ int2 page_range(const int* __restrict__ word_offs, in
     const int lo = min(max(word_offs[p], 0), n);
     return make_int2(lo, min(max(word_offs[p + 1], lo), n));
 }
-// the page of workgroup k: the last p with blk_offs[p] <= k (pages without words own no workgroup and are passed over); k < blk_offs[B]
-__device__ __forceinline__ int page_of_block(const int* __restrict__ blk_offs, int B, int k) {
+// the last p in [0, B) with offs[p] <= k, for an ascending offs with offs[0] <= k: the page of workgroup k in blk_offs (k < blk_offs[B]; pages
+// without words own no workgroup and are passed over) and the page of word k in word_offs
+__device__ __forceinline__ int last_le(const int* __restrict__ offs, int B, int k) {
     int lo = 0, hi = B - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (blk_offs[mid] <= k) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-// the page of word i: the last p with word_offs[p] <= i
-__device__ __forceinline__ int page_of_index(const int* __restrict__ word_offs, int B, int i) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (word_offs[mid] <= i) lo = mid; else hi = mid - 1;
+        if (offs[mid] <= k) lo = mid; else hi = mid - 1;
     }
     return lo;
 }
@@ -371,7 +384,6 @@ __global__ __launch_bounds__(256) void k_pages_init(const int* __restrict__ coun
 // One workgroup: out[0..B] = exclusive scan over the pages, 256 at a time, of ceil(n_p / per) (per > 0, from word_offs) or of vals[p] (per == 0).
 __global__ __launch_bounds__(256) void k_page_scan(const int* __restrict__ word_offs, const int* __restrict__ vals, const int* __restrict__ count, long cap, int B,
                                                    int per, int* __restrict__ out) {
-    __shared__ int s_scan[256];
     const int n = word_count(count, cap);
     const int t = threadIdx.x;
     int base = 0;
@@ -386,66 +398,31 @@ __global__ __launch_bounds__(256) void k_page_scan(const int* __restrict__ word_
                 v = min(max(vals[p], 0), n);
             }
         }
-        __syncthreads();
-        s_scan[t] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {  // inclusive scan
-            const int add = t >= o ? s_scan[t - o] : 0;
-            __syncthreads();
-            s_scan[t] += add;
-            __syncthreads();
-        }
-        if (p < B) out[p] = base + s_scan[t] - v;
-        base += s_scan[255];
+        const int2 sc = block_scan_256(v);
+        if (p < B) out[p] = base + sc.x - v;
+        base += sc.y;
     }
     if (t == 0) out[B] = base;
 }
 
-// k_line_links for the words of one page per workgroup: the same walk in index order and the same arithmetic, over word_offs[p] .. word_offs[p + 1]
-// only, so a word of another page is never a candidate and the work is the sum of n_p^2.
+// k_line_links with one page per workgroup: the walk covers word_offs[p] .. word_offs[p + 1] only, so a word of another page is never a
+// candidate and the work is the sum of n_p^2.
 __global__ __launch_bounds__(kTile) void k_line_links_pages(const float* __restrict__ frames, const int* __restrict__ word_offs, const int* __restrict__ blk_offs, int B,
                                                             const int* __restrict__ count, long cap, float max_gap, float min_cos, int* __restrict__ chosen,
                                                             unsigned long long* __restrict__ accept) {
-    __shared__ float4 s_a[kTile], s_b[kTile];
     const int n = word_count(count, cap);
     const int k = blockIdx.x;
     if (k >= blk_offs[B]) return;  // (block-uniform)
-    const int p = page_of_block(blk_offs, B, k);
+    const int p = last_le(blk_offs, B, k);
     const int2 r = page_range(word_offs, p, n);
-    const int t = threadIdx.x, i = r.x + (k - blk_offs[p]) * kTile + t;
-    float4 fa = make_float4(0.0f, 0.0f, 1.0f, 0.0f), fb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (i < r.y) fa = reinterpret_cast<const float4*>(frames)[2 * (long)i], fb = reinterpret_cast<const float4*>(frames)[2 * (long)i + 1];
-    const float cxi = fa.x, cyi = fa.y, uxi = fa.z, uyi = fa.w, lngi = fb.x, shti = fb.y;
-    const float vxi = -uyi, vyi = uxi;
-    const float halfi = 0.5f * lngi;
-    float best_s = 0.0f;
-    int best_j = -1;
-    for (int j0 = r.x; j0 < r.y; j0 += kTile) {
-        const int m = min(kTile, r.y - j0);
-        __syncthreads();
-        if (t < m) s_a[t] = reinterpret_cast<const float4*>(frames)[2 * (long)(j0 + t)], s_b[t] = reinterpret_cast<const float4*>(frames)[2 * (long)(j0 + t) + 1];
-        __syncthreads();
-#pragma unroll 4
-        for (int q = 0; q < m; ++q) {
-            const float4 ja = s_a[q], jb = s_b[q];
-            const float dx = ja.x - cxi, dy = ja.y - cyi;
-            const float s = dx * uxi + dy * uyi;
-            const float tt = dx * vxi + dy * vyi;
-            const float gap = (s - halfi) - 0.5f * jb.x;
-            const float cs = uxi * ja.z + uyi * ja.w;
-            const bool cand = s > 0.0f && fabsf(tt) <= 0.5f * fminf(shti, jb.y) && gap <= max_gap * fmaxf(shti, jb.y) && cs >= min_cos &&
-                              (dx > 0.0f || (dx == 0.0f && dy > 0.0f));
-            if (cand && (best_j < 0 || s < best_s)) best_s = s, best_j = j0 + q;
-        }
-    }
-    if (i < r.y) {
-        chosen[i] = best_j;
-        if (best_j >= 0) atomicMin(&accept[best_j], ((unsigned long long)__float_as_uint(best_s) << 32) | (unsigned)i);
-    }
+    const int i = r.x + (k - blk_offs[p]) * kTile + threadIdx.x;
+    const Link best = nearest_follower(frames, r.x, r.y, i, i < r.y, max_gap, min_cos);
+    if (i < r.y) store_link(i, best, chosen, accept);
 }
 
 // k_line_order per page: the rank of head i among the heads of its own page under (c.y, c.x, word index), left in line_idx[i] for
-// k_line_place_pages; the heads of each page are counted with an integer atomic.
+// k_line_place_pages; the heads of each page are counted with an integer atomic.  The count is k_line_order's text over the page's range: as
+// one inlined function hipcc vectorises the loop differently and the order stage runs 8 to 15 % slower, so the two stay separate texts.
 __global__ __launch_bounds__(kTile) void k_line_order_pages(const float* __restrict__ frames, const int* __restrict__ word_offs, const int* __restrict__ blk_offs, int B,
                                                             const int* __restrict__ count, long cap, const int* __restrict__ head, int* __restrict__ line_idx,
                                                             int* __restrict__ heads) {
@@ -454,7 +431,7 @@ __global__ __launch_bounds__(kTile) void k_line_order_pages(const float* __restr
     const int n = word_count(count, cap);
     const int k = blockIdx.x;
     if (k >= blk_offs[B]) return;
-    const int p = page_of_block(blk_offs, B, k);
+    const int p = last_le(blk_offs, B, k);
     const int2 r = page_range(word_offs, p, n);
     const int t = threadIdx.x, i = r.x + (k - blk_offs[p]) * kTile + t;
     const bool mine = i < r.y && head[i] == i;
@@ -488,7 +465,7 @@ __global__ __launch_bounds__(256) void k_line_place_pages(const int* __restrict_
     const int n = word_count(count, cap);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n || head[i] != i) return;
-    const int p = page_of_index(word_offs, B, i);
+    const int p = last_le(word_offs, B, i);
     const int l = line_page_offs[p] + line_idx[i];
     if ((unsigned)l >= (unsigned)n) {  // (never, on finite input with ascending offsets)
         line_idx[i] = 0;
@@ -500,7 +477,6 @@ __global__ __launch_bounds__(256) void k_line_place_pages(const int* __restrict_
     page_of_line[l] = p;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned blocks(long n, int per) { return (unsigned)((n + per - 1) / per); }
 constexpr long kMaxWords = 1L << 24;
 constexpr int kMaxPages = 1 << 20;

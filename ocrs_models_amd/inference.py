@@ -57,6 +57,40 @@ SHRINK_DISTANCE = 3.0    # datasets/util.py: how far text polygons are shrunk wh
 _OW_BINS = 801           # line_output_width() is in [10, 800]
 
 
+# Argument checks shared by the public functions; ``who`` is the caller's name, so every message starts with the function the user called.
+def _need_quads(quads: torch.Tensor, who: str, shape: str = "(N,4,2)", plan: CropPlan | None = None) -> torch.Tensor:
+    """fp32 quads of that shape on the device (``plan``: as many as the plan has rows) -> contiguous"""
+    _need_cuda(quads, who)
+    if quads.dtype != torch.float32 or quads.dim() != shape.count(",") + 1 or tuple(quads.shape[-2:]) != (4, 2):
+        raise RuntimeError(f"{who}: expected {shape} float32 quads")
+    if plan is not None and quads.shape[0] != plan.table.shape[0]:
+        raise RuntimeError(f"{who}: quads must be the quads the plan was made from")
+    return quads.contiguous()
+
+
+def _need_counts(counts: torch.Tensor, who: str, entries: int = 1) -> torch.Tensor:
+    """int32 device counts, ``entries`` of them (one per batch row or page; a single count by default) -> contiguous"""
+    _need_cuda(counts, who)
+    if counts.dtype != torch.int32 or counts.numel() != entries:
+        raise RuntimeError(f"{who}: expected {entries} int32 count(s) on the device")
+    return counts.contiguous()
+
+
+def _need_page(page_u8: torch.Tensor, who: str) -> torch.Tensor:
+    """a (1,H,W) or (H,W) uint8 page on the device -> contiguous"""
+    _need_cuda(page_u8, who)
+    if page_u8.dtype != torch.uint8 or not (page_u8.dim() == 2 or (page_u8.dim() == 3 and page_u8.shape[0] == 1)):
+        raise RuntimeError(f"{who}: expected a (1,H,W) or (H,W) uint8 page")
+    return page_u8.contiguous()
+
+
+def _to_host_async(t: torch.Tensor) -> torch.Tensor:
+    """a pinned host copy of ``t`` queued on the current stream: valid after the next wait for that stream"""
+    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    h.copy_(t, non_blocking=True)
+    return h
+
+
 def binarize_resize(prob: torch.Tensor, size, threshold: float = 0.5) -> torch.Tensor:
     """(B,1,h,w) or (h,w) fp32 probabilities -> uint8 0/1 mask (B,1,H,W) or (H,W): ``binarize_mask`` followed by
     ``resize(.., size, InterpolationMode.NEAREST)`` (eval_detection.py:54-57) in one launch."""
@@ -75,18 +109,12 @@ def binarize_resize(prob: torch.Tensor, size, threshold: float = 0.5) -> torch.T
 def expand_quads(quads: torch.Tensor, dist: float, counts: torch.Tensor | None = None) -> torch.Tensor:
     """``expand_quads`` (postprocess.py:68-76) on the device: (N,4,2) or (B,cap,4,2) fp32 -> the same shape, every rectangle's edges moved
     outward by ``dist``.  ``counts`` (B,) int32 on the device: rows past ``counts[b]`` are returned as they came."""
-    _need_cuda(quads, "expand_quads")
-    if quads.dtype != torch.float32 or quads.dim() not in (3, 4) or tuple(quads.shape[-2:]) != (4, 2):
-        raise RuntimeError("expand_quads: expected (N,4,2) or (B,cap,4,2) float32 quads")
-    q = quads.contiguous()
+    q = _need_quads(quads, "expand_quads", "(B,cap,4,2)" if quads.dim() == 4 else "(N,4,2)")
     B, cap = (1, q.shape[0]) if q.dim() == 3 else (q.shape[0], q.shape[1])
     if counts is None:
         out = torch.empty_like(q)
     else:
-        _need_cuda(counts, "expand_quads")
-        if counts.dtype != torch.int32 or counts.numel() != B:
-            raise RuntimeError("expand_quads: counts must be int32 with one entry per batch row")
-        counts = counts.contiguous()
+        counts = _need_counts(counts, "expand_quads", B)
         out = q.clone()
     lib().expand_quads(ptr(q), ptr(out), ptr(counts), B, cap, float(dist))
     return out
@@ -126,10 +154,7 @@ class CropPlan:
         """``totals`` on the host: the one synchronisation between the plan and the crops (cached).  The table comes along in the same
         wait, so the order (``host_perm``) costs no second one."""
         if self._host is None:
-            tot = torch.empty(self.totals.shape, dtype=torch.int64, pin_memory=True)
-            tab = torch.empty(self.table.shape, dtype=torch.int32, pin_memory=True)
-            tot.copy_(self.totals, non_blocking=True)
-            tab.copy_(self.table, non_blocking=True)
+            tot, tab = _to_host_async(self.totals), _to_host_async(self.table)
             torch.cuda.current_stream(self.totals.device).synchronize()
             self._host, self._host_table = tot.tolist(), tab
             if max(self._host[1:4]) >= 2 ** 31:
@@ -146,15 +171,9 @@ def crop_plan(quads: torch.Tensor, output_height: int = 64, count: torch.Tensor 
     """Geometry of the crop of every quad (N,4,2) by the module's crop-frame rule, offsets into the packed buffers and the order by output
     width.  One kernel, no synchronisation.  ``count`` (1,) int32 on the device: only the first ``min(count, N)`` quads are planned (the
     table's other rows are left as allocated); the later stages take that number from ``plan.host()[0]``."""
-    _need_cuda(quads, "crop_plan")
-    if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
-        raise RuntimeError("crop_plan: expected (N,4,2) float32 quads")
+    q = _need_quads(quads, "crop_plan")
     if count is not None:
-        _need_cuda(count, "crop_plan")
-        if count.dtype != torch.int32 or count.numel() != 1:
-            raise RuntimeError("crop_plan: count must be one int32 on the device")
-        count = count.contiguous()
-    q = quads.contiguous()
+        count = _need_counts(count, "crop_plan")
     n = q.shape[0]
     table = torch.empty(n, 8, dtype=torch.int32, device=q.device)
     totals = torch.empty(4 + _OW_BINS, dtype=torch.int64, device=q.device)
@@ -165,15 +184,9 @@ def crop_plan(quads: torch.Tensor, output_height: int = 64, count: torch.Tensor 
 def rectify_crops(page_u8: torch.Tensor, quads: torch.Tensor, plan: CropPlan) -> torch.Tensor:
     """Cut every rotated rectangle out of the (1,H,W) / (H,W) uint8 page into one packed fp32 buffer: crop i is (h_i, w_i) row-major at
     ``plan.table[i, 3]``.  ``transform_image`` fused, bilinear, one launch for all crops."""
-    _need_cuda(page_u8, "rectify_crops")
-    _need_cuda(quads, "rectify_crops")
-    if page_u8.dtype != torch.uint8 or not (page_u8.dim() == 2 or (page_u8.dim() == 3 and page_u8.shape[0] == 1)):
-        raise RuntimeError("rectify_crops: expected a (1,H,W) or (H,W) uint8 page")
-    if quads.dtype != torch.float32 or quads.dim() != 3 or quads.shape[0] != plan.table.shape[0]:
-        raise RuntimeError("rectify_crops: quads must be the (N,4,2) float32 quads the plan was made from")
-    H, W = page_u8.shape[-2:]
+    page, q = _need_page(page_u8, "rectify_crops"), _need_quads(quads, "rectify_crops", plan=plan)
+    H, W = page.shape[-2:]
     _, packed_floats, _, tiles = plan.host()[:4]
-    page, q = page_u8.contiguous(), quads.contiguous()
     packed = torch.empty(packed_floats, dtype=torch.float32, device=q.device)
     lib().rectify_crops(ptr(page), H, W, ptr(q), ptr(plan.table), ptr(plan.totals), tiles, ptr(packed), packed_floats)
     return packed
@@ -252,6 +265,22 @@ def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET) -> list[str]:
     return [texts[p] for p in perm]
 
 
+def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLines | None = None, n_lines: int = 0) -> list[dict]:
+    """The tail of ``ocr_page``, ``read_lines`` and ``ocr_pages``: ``recognize_crops`` on ``batches``, then the flat result list -- one
+    ``{"quad", "text"}`` per word, or with ``lines`` one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  The word quads
+    and the line tables travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of
+    their own)."""
+    words_h = _to_host_async(words)
+    if lines is not None:
+        lq_h, order_h, offs_h = (_to_host_async(t) for t in (lines.quads, lines.word_order, lines.line_offsets))
+    texts = recognize_crops(rec_model, batches, alphabet)
+    wl = words_h.tolist()
+    if lines is None:
+        return [{"quad": q, "text": t} for q, t in zip(wl, texts)]
+    order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
+    return [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+
+
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
              output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
@@ -262,12 +291,7 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thresh
     quads = det["quads"]
     plan = crop_plan(quads, output_height)
     packed = rectify_crops(page_u8, quads, plan)
-    batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    # the quads travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of their own)
-    quads_h = torch.empty(quads.shape, dtype=torch.float32, pin_memory=True)
-    quads_h.copy_(quads, non_blocking=True)
-    texts = recognize_crops(rec_model, batches, alphabet)
-    return [{"quad": q, "text": t} for q, t in zip(quads_h.tolist(), texts)]
+    return _read_crops(rec_model, crops_to_batches(packed, plan, max_batch, width_unit), alphabet, quads)
 
 
 # ------------------------------------------------------------------ words -> lines -------------------------------------------------------
@@ -287,11 +311,15 @@ class TextLines:
     page_of_line: torch.Tensor | None = None    # (N,) int32, find_lines_pages only: rows up to L
 
 
-def _empty_lines(n: int, device) -> TextLines:
+def _empty_lines(n: int, device, pages: int | None = None) -> TextLines:
+    """the output tensors of ``find_lines`` for n words, or of ``find_lines_pages`` for n words on ``pages`` pages"""
     i32 = dict(dtype=torch.int32, device=device)
-    n_lines = torch.empty(1, **i32) if n else torch.zeros(1, **i32)  # (with words, k_line_scan writes it)
-    return TextLines(torch.empty(n, 4, 2, dtype=torch.float32, device=device), n_lines, torch.empty(n, **i32), torch.empty(n, **i32),
-                     torch.empty(n + 1, **i32), torch.empty(n, **i32))
+    counts = torch.empty if n else torch.zeros  # (with words, the scan kernels write them)
+    out = TextLines(torch.empty(n, 4, 2, dtype=torch.float32, device=device), counts(1, **i32), torch.empty(n, **i32), torch.empty(n, **i32),
+                    torch.empty(n + 1, **i32), torch.empty(n, **i32))
+    if pages is not None:
+        out.line_page_offs, out.page_of_line = counts(pages + 1, **i32), torch.empty(n, **i32)
+    return out
 
 
 def find_lines(quads: torch.Tensor, count: torch.Tensor | None = None, max_gap: float = 2.0, min_cos: float = 0.9,
@@ -301,15 +329,9 @@ def find_lines(quads: torch.Tensor, count: torch.Tensor | None = None, max_gap: 
     baseline and with ``min_cos`` between the axes; a word accepts its nearest chooser; lines are the chains, sorted by their first word's
     (centre y, centre x, index).  ``count`` (1,) int32 on the device: only the first ``min(count, N)`` rows are words.  ``out``: write into
     these tensors instead of new ones.  Four stages of kernels, no host synchronisation; ``N == 0`` launches nothing."""
-    _need_cuda(quads, "find_lines")
-    if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
-        raise RuntimeError("find_lines: expected (N,4,2) float32 quads")
+    q = _need_quads(quads, "find_lines")
     if count is not None:
-        _need_cuda(count, "find_lines")
-        if count.dtype != torch.int32 or count.numel() != 1:
-            raise RuntimeError("find_lines: count must be one int32 on the device")
-        count = count.contiguous()
-    q = quads.contiguous()
+        count = _need_counts(count, "find_lines")
     n = q.shape[0]
     if out is None:
         out = _empty_lines(n, q.device)
@@ -331,12 +353,6 @@ def find_lines(quads: torch.Tensor, count: torch.Tensor | None = None, max_gap: 
     return out
 
 
-def _to_host_async(t: torch.Tensor) -> torch.Tensor:
-    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    h.copy_(t, non_blocking=True)
-    return h
-
-
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
                alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
@@ -346,11 +362,7 @@ def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_hei
     plan = crop_plan(lines.quads, output_height, lines.n_lines)
     packed = rectify_crops(page_u8, lines.quads, plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    n_lines = plan.host()[0]
-    quads_h, lq_h, order_h, offs_h = (_to_host_async(t) for t in (quads, lines.quads, lines.word_order, lines.line_offsets))
-    texts = recognize_crops(rec_model, batches, alphabet)
-    words, order, offs, lq = quads_h.tolist(), order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
-    return [{"quad": lq[l], "text": texts[l], "words": [words[i] for i in order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0])
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
@@ -425,14 +437,9 @@ def gather_page_quads(quads: torch.Tensor, counts: torch.Tensor):
     """Quads (B,cap,4,2) fp32 with device counts (B,) int32, as ``ocrs_cc_quads`` writes them -> ``(flat quads (N_total,4,2), page_of_word
     (N_total,) int32, word_offs (B+1,) int32, counts as a host list)``: the rows of every page back to back in their own (raster) order.
     Reading ``word_offs`` to size the flat rows is the one host synchronisation; it stands for the B waits for component counts."""
-    _need_cuda(quads, "gather_page_quads")
-    _need_cuda(counts, "gather_page_quads")
-    if quads.dtype != torch.float32 or quads.dim() != 4 or tuple(quads.shape[2:]) != (4, 2):
-        raise RuntimeError("gather_page_quads: expected (B,cap,4,2) float32 quads")
-    B, cap = quads.shape[:2]
-    if counts.dtype != torch.int32 or counts.numel() != B:
-        raise RuntimeError("gather_page_quads: counts must be int32 with one entry per page")
-    q, counts = quads.contiguous(), counts.contiguous()
+    q = _need_quads(quads, "gather_page_quads", "(B,cap,4,2)")
+    B, cap = q.shape[:2]
+    counts = _need_counts(counts, "gather_page_quads", B)
     L = lib()
     word_offs = torch.empty(B + 1, dtype=torch.int32, device=q.device)
     L.gather_page_quads(ptr(q), ptr(counts), B, cap, None, None, ptr(word_offs), 0)
@@ -504,21 +511,17 @@ def find_lines_pages(quads: torch.Tensor, page_of_word: torch.Tensor, word_offs:
     index) of their first word.  Indices in the result count through the flat arrays; ``line_page_offs`` (B+1,) and ``page_of_line`` say which
     lines are which page's.  The kernels stage only the words of a workgroup's own page, so the work is the sum of n_p^2.  No host
     synchronisation; N == 0 launches nothing."""
-    for t in (quads, page_of_word, word_offs):
+    q = _need_quads(quads, "find_lines_pages")
+    n = q.shape[0]
+    for t in (page_of_word, word_offs):
         _need_cuda(t, "find_lines_pages")
-    if quads.dtype != torch.float32 or quads.dim() != 3 or tuple(quads.shape[1:]) != (4, 2):
-        raise RuntimeError("find_lines_pages: expected (N,4,2) float32 quads")
-    n = quads.shape[0]
     if page_of_word.dtype != torch.int32 or tuple(page_of_word.shape) != (n,):
         raise RuntimeError("find_lines_pages: page_of_word must be (N,) int32")
     if word_offs.dtype != torch.int32 or word_offs.dim() != 1 or word_offs.numel() < 2:
         raise RuntimeError("find_lines_pages: word_offs must be (B+1,) int32 with B >= 1")
     B = word_offs.numel() - 1
-    q, offs = quads.contiguous(), word_offs.contiguous()
-    out = _empty_lines(n, q.device)
-    i32 = dict(dtype=torch.int32, device=q.device)
-    out.line_page_offs = torch.empty(B + 1, **i32) if n else torch.zeros(B + 1, **i32)
-    out.page_of_line = torch.empty(n, **i32)
+    offs = word_offs.contiguous()
+    out = _empty_lines(n, q.device, B)
     if n == 0:
         return out
     L = lib()
@@ -538,19 +541,17 @@ def rectify_crops_pages(pages_packed: torch.Tensor, page_offs: torch.Tensor, pag
                         plan: CropPlan) -> torch.Tensor:
     """``rectify_crops`` from a page store (``pack_pages``): crop i is cut out of page ``page_of_quad[i]`` -- ``page_of_line`` for line crops,
     ``page_of_word`` for word crops.  One launch for the crops of all pages; a crop's values are those ``rectify_crops`` gives it on its own page."""
-    for t in (pages_packed, page_offs, page_sizes, quads, page_of_quad):
+    for t in (pages_packed, page_offs, page_sizes, page_of_quad):
         _need_cuda(t, "rectify_crops_pages")
     if pages_packed.dtype != torch.uint8 or pages_packed.dim() != 1:
         raise RuntimeError("rectify_crops_pages: expected the flat uint8 buffer of pack_pages")
     B = page_offs.numel()
     if page_offs.dtype != torch.int64 or page_sizes.dtype != torch.int32 or tuple(page_sizes.shape) != (B, 2):
         raise RuntimeError("rectify_crops_pages: page_offs must be (B,) int64 and page_sizes (B,2) int32")
-    if quads.dtype != torch.float32 or quads.dim() != 3 or quads.shape[0] != plan.table.shape[0]:
-        raise RuntimeError("rectify_crops_pages: quads must be the (N,4,2) float32 quads the plan was made from")
-    if page_of_quad.dtype != torch.int32 or tuple(page_of_quad.shape) != (quads.shape[0],):
+    q = _need_quads(quads, "rectify_crops_pages", plan=plan)
+    if page_of_quad.dtype != torch.int32 or tuple(page_of_quad.shape) != (q.shape[0],):
         raise RuntimeError("rectify_crops_pages: page_of_quad must be (N,) int32")
     _, packed_floats, _, tiles = plan.host()[:4]
-    q = quads.contiguous()
     packed = torch.empty(packed_floats, dtype=torch.float32, device=q.device)
     lib().rectify_crops_pages(ptr(pages_packed.contiguous()), pages_packed.numel(), ptr(page_offs.contiguous()), ptr(page_sizes.contiguous()), B, ptr(q),
                               ptr(page_of_quad.contiguous()), ptr(plan.table), ptr(plan.totals), tiles, ptr(packed), packed_floats)
@@ -594,15 +595,6 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
         plan = crop_plan(words, output_height)
         packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, words, det["page_of_word"], plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    # quads and line tables travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have
-    words_h = _to_host_async(words)
-    if lines:
-        n_lines = plan.host()[0]
-        lq_h, order_h, offs_h = (_to_host_async(t) for t in (tl.quads, tl.word_order, tl.line_offsets))
-    texts = recognize_crops(rec_model, batches, alphabet)
-    wl = words_h.tolist()
     if not lines:
-        return split_by_page([{"quad": q, "text": t} for q, t in zip(wl, texts)], word_offs_h)
-    order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
-    flat = [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
-    return split_by_page(flat, lpo_h.tolist())
+        return split_by_page(_read_crops(rec_model, batches, alphabet, words), word_offs_h)
+    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, plan.host()[0]), lpo_h.tolist())

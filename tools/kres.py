@@ -19,5 +19,5 @@ if r.returncode != 0 or not rows:
 dem = subprocess.run(["c++filt"] + list(rows), capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.splitlines()
 for name, d in zip(dem, rows.values()):
     if pat and not re.search(pat, name): continue
-    short = re.sub(r"\(.*", "", name).replace("void ", "")
+    short = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", "")).replace("void ", "")
     print(f"{short:45s} vgpr {d.get('VGPRs','?'):>4s} agpr {d.get('AGPRs','?'):>3s} scratch {d.get('ScratchSize [bytes/lane]','?'):>4s} occ {d.get('Occupancy [waves/SIMD]','?')} lds {d.get('LDS Size [bytes/block]','?')}")
