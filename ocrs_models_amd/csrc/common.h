@@ -249,12 +249,20 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 static constexpr int KCH = 32;
 
+// bf16 elements per pixel of a C-channel LDS tile [pixel][channel] that is read as MFMA fragments (ds_read_b128: pixel = lane & 15, 16-byte chunk
+// = lane >> 4) and by transpose reads (lds_tr8: 8 pixel rows of 32 bytes per half wave).  gfx950 services a ds_read_b128 in the lane groups
+// {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+32 for the upper half wave) and a ds_read_b64_tr_b16 in two groups of 32 lanes, over 64 banks of
+// 4 bytes: 16- and 32-byte rows are conflict-free as they are; from 64 bytes up a row needs a 32-byte pad (row starts then step through the
+// banks in eights) -- with a 16- or 48-byte pad every such read takes twice its LDS cycles.  Model and table: tools/lds_banks.py.
+constexpr int lds_pitch_bf16(int c) { return c <= 16 ? c : c + 16; }
+
 template <class T>
 struct Mma;
 
 template <>
 struct Mma<bf16> {
-    // LDS tile row: 32 bf16 + 8 pad = 80 B (16-B aligned, conflict-free ds_read_b128 over 16 rows)
+    // LDS tile row of the chunked detection kernels (det_fwd.hip / det_bwd.hip, outside the bf16 train step): 32 bf16 + 8 pad = 80 B (16-B aligned).
+    // Under the lane groups described at lds_pitch_bf16 a ds_read_b128 fragment read over 16 such rows takes 8 LDS cycles instead of 4.
     static constexpr int LDS_PITCH = 40;
     // packed weight fragment: 8 bf16 per lane per (chunk, tile) = one 16-B load
     struct Frag {
@@ -310,6 +318,13 @@ struct Mma<float> {
         for (int ks = 0; ks < KS; ++ks) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[ks], b.v[ks], c, 0, 0, 0);
         return c;
     }
+};
+
+// Tile row of the recognition kernels (rec_conv*.hip), a constant of their own: 32 bf16 + 8 pad / 32 f32 + 4 pad, the values they were tuned and
+// measured with; moving them to lds_pitch_bf16 is a separate change.
+template <class T>
+struct RecTile {
+    static constexpr int PITCH = sizeof(T) == 2 ? 40 : 36;
 };
 
 // gfx950 LDS transpose read (ds_read_b64_tr_b16).  Within every group of 16 lanes, lane i supplies the 8-byte-aligned LDS address of 4

@@ -25,11 +25,6 @@ constexpr int mf_th(int cin, int cout, int nst) { return (nst != 2 && cin == 8 &
 
 namespace {
 
-template <int C>
-struct MmPitch {  // bf16 elements per pixel of an LDS tile: 16 / 32-byte rows are conflict-free as they are, 64-byte rows need the 16-byte pad
-    static constexpr int V = (C == 32) ? 40 : C;
-};
-
 template <int CIN, int COUT, bool PPOOL = false>
 struct MmCfg {
     // Cin = 32 (two M tiles: 16-24 more live registers than fit 128 without spilling): TWO independent 256-thread workgroups per CU with 256
@@ -50,7 +45,12 @@ struct MmCfg {
     static constexpr bool BDB = !(CIN == 8 && COUT == 16 && TH == 12) && !T12P && !N256;
     static constexpr int DW_ = TW + 2, DH_ = TH + 2, DP = DW_ * DH_;  // domain = tile + 1-pixel ring
     static constexpr int CGI = CIN / 8, CGO = COUT / 8;
-    static constexpr int PD = MmPitch<COUT>::V, PX = MmPitch<CIN>::V;
+    // tile pitches (elements).  Cin = 32 -> Cout = 16 keeps the 16-byte pad on tileX: its fragment reads are on the unpadded 16-channel tileD and the
+    // launch measured no faster with the wider rows ("LDS pitch")
+    static constexpr int PD = lds_pitch_bf16(COUT), PX = (CIN == 32 && COUT == 16) ? CIN + 8 : lds_pitch_bf16(CIN);
+    // fp32 copies of the depthwise / pointwise masters in LDS for the prologue's effective-weight fragments -- except at 32 x 32 channels, where
+    // their 5.2 KB would cost the second resident workgroup: that shape reads the masters from global memory (L2 hits, once per block, as every flush does)
+    static constexpr bool WLDS = !(CIN == 32 && COUT == 32);
     static constexpr int MT = (CIN + 15) / 16, NTO = (COUT + 15) / 16;
     static constexpr int KC = (9 * COUT + 31) / 32;                    // K chunks of the dgrad GEMM
     static constexpr int NPW = TP / 16 / NW;                           // dgrad N tiles (16 pixels) per wave
@@ -67,7 +67,7 @@ struct MmCfg {
     static constexpr int OFF_X = (OFF_D + DP * PD * 2 + 63) & ~63;
     static constexpr int OFF_WF = (OFF_X + TP * PX * 2 + 64 + 63) & ~63;  // +64: the Cin = 8 transpose reads run 16 bytes past the last pixel
     static constexpr int OFF_PAR = OFF_WF + MT * KC * 64 * 16;
-    static constexpr int PAR_FLOATS = 3 * CIN + 6 * COUT + 9 * CIN + COUT * CIN + NW * 2 * MT * 16;  // trx | bn | coef | wdw [c][9] | wpw [o][c] | stats slots
+    static constexpr int PAR_FLOATS = 3 * CIN + 6 * COUT + (WLDS ? 9 * CIN + COUT * CIN : 0) + NW * 2 * MT * 16;  // trx | bn | coef | wdw [c][9] | wpw [o][c] (WLDS) | stats slots
     static constexpr int TILE_BYTES = OFF_PAR + PAR_FLOATS * 4;
     static constexpr int SLOT_FLOATS = (NW * NOWN * MT * NTO + NW) * 256 + NW * 2 * MT * 16;  // flush: G slots (own units | shared sub-tile) + stats slots
     static constexpr int SMEM = TILE_BYTES > SLOT_FLOATS * 4 ? TILE_BYTES : SLOT_FLOATS * 4;
@@ -163,8 +163,8 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
     float* s_trx = reinterpret_cast<float*>(smem + C::OFF_PAR);  // [CIN/8][3][8]
     float* s_bn = s_trx + 3 * CIN;                              // [3][COUT]
     float* s_cf = s_bn + 3 * COUT;                              // [3][COUT]
-    float* s_w9 = s_cf + 3 * COUT;                              // [CIN][9]
-    float* s_wp = s_w9 + 9 * CIN;                               // [COUT][CIN]
+    float* s_w9 = s_cf + 3 * COUT;                              // [CIN][9]     (WLDS)
+    float* s_wp = s_w9 + (C::WLDS ? 9 * CIN : 0);               // [COUT][CIN]  (WLDS)
     const int H = tg.H, W = tg.W;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar register: wave-dependent branches and offsets become scalar code)
@@ -177,13 +177,15 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
     } else {
         for (int i = tid; i < 3 * COUT; i += NT) s_cf[i] = coef[i];
     }
-    for (int i = tid; i < 9 * CIN; i += NT) s_w9[i] = wdw[i];
-    for (int i = tid; i < COUT * CIN; i += NT) s_wp[i] = wpw[(i / CIN) * ldw + (i % CIN)];
+    if constexpr (C::WLDS) {
+        for (int i = tid; i < 9 * CIN; i += NT) s_w9[i] = wdw[i];
+        for (int i = tid; i < COUT * CIN; i += NT) s_wp[i] = wpw[(i / CIN) * ldw + (i % CIN)];
+    }
     {   // zero both tiles once (pad columns / the slack behind tileX stay zero)
         const uint4 z4 = make_uint4(0, 0, 0, 0);
         for (int i = tid; i < C::OFF_WF / 16; i += NT) reinterpret_cast<uint4*>(smem)[i] = z4;
     }
-    __syncthreads();
+    if constexpr (C::WLDS) __syncthreads();
     for (int f = tid; f < MT * KC * 64; f += NT) {
         const int l = f & 63, kc = (f >> 6) % KC, mt = (f >> 6) / KC;
         const int m = (FULL && CIN == 8) ? (l & 7) : mt * 16 + (l & 15);  // FULL, CIN = 8: M rows 8..15 duplicate rows 0..7 (unconditional stores)
@@ -191,7 +193,8 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = kc * 32 + (l >> 4) * 8 + j, tap = k / COUT, o = k % COUT;
-            v[j] = (m < CIN && tap < 9) ? s_w9[m * 9 + tap] * s_wp[o * CIN + m] : 0.f;
+            if constexpr (C::WLDS) v[j] = (m < CIN && tap < 9) ? s_w9[m * 9 + tap] * s_wp[o * CIN + m] : 0.f;
+            else v[j] = (m < CIN && tap < 9) ? wdw[m * 9 + tap] * wpw[o * ldw + m] : 0.f;
         }
         s_wf[f] = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
     }
@@ -370,7 +373,7 @@ __global__ __launch_bounds__((MmCfg<CIN, COUT, PPOOL>::NT), (mm_bwd_lb<CIN, COUT
     // producers' BatchNorm-backward sums: per-lane register accumulators (one M tile), or -- with two M tiles, where 16 more live registers
     // spill -- per-tile sums added to this wave's own LDS slots (single writer, fixed order: deterministic)
     constexpr bool STL = STATS && (MT == 2 || C::T12P);
-    float* s_st = s_wp + COUT * CIN;  // [wave][2][MT*16] (STL only)
+    float* s_st = s_wp + (C::WLDS ? COUT * CIN : 0);  // [wave][2][MT*16] (STL only)
     float st1[(STATS && !STL) ? MT : 1][4];
     if constexpr (STATS && !STL) {
 #pragma unroll
@@ -1064,7 +1067,7 @@ struct MfCfg {
     static constexpr int TW = 32, TH = mf_th(CINB, COUT, NST), TP = TW * TH;
     static constexpr int DW_ = TW + 2, DH_ = TH + 2, DP = DW_ * DH_;
     static constexpr int CGB = CINB / 8;
-    static constexpr int PX = MmPitch<CINB>::V;
+    static constexpr int PX = lds_pitch_bf16(CINB);
     static constexpr int MT = (COUT + 15) / 16;
     static constexpr int KC = (9 * CINB + 31) / 32;
     static_assert(TH % 8 == 0, "forward tiles: TH (row pair, column half) units over 8 waves");
@@ -1073,7 +1076,8 @@ struct MfCfg {
     static constexpr int OFF_X = 0;
     static constexpr int OFF_WF = (DP * PX * 2 + 63) & ~63;
     static constexpr int OFF_PAR = OFF_WF + NST * MT * KC * 64 * 16;
-    static constexpr int PAR_FLOATS = 3 * CINB * NST + 9 * CINB * NST + COUT * CINB * NST + NW * MT * 16 * 2;
+    static constexpr bool WLDS = NST == 1;  // fp32 masters in LDS for the prologue (see MmCfg); the two-stage 32 | 32 shape needs their 10.5 KB for its second workgroup
+    static constexpr int PAR_FLOATS = 3 * CINB * NST + (WLDS ? 9 * CINB * NST + COUT * CINB * NST : 0) + NW * MT * 16 * 2;  // trx | wdw | wpw (WLDS) | stats slots
     static constexpr int SMEM = OFF_PAR + PAR_FLOATS * 4;
 };
 }  // namespace
@@ -1132,21 +1136,23 @@ __global__ __launch_bounds__(512, (mm_fwd_lb<CINB, COUT>())) void k_mm_fwd(Src2<
     bf16* tileX = reinterpret_cast<bf16*>(smem + C::OFF_X);     // [DP][PX] x~ on the domain of the current stage (0 outside the image)
     uint4* s_wf = reinterpret_cast<uint4*>(smem + C::OFF_WF);   // [NST][MT][KC][64] effective-weight A fragments
     float* s_trx = reinterpret_cast<float*>(smem + C::OFF_PAR); // [CIN/8][3][8]
-    float* s_w9 = s_trx + 3 * CIN;                               // [CIN][9]
-    float* s_wp = s_w9 + 9 * CIN;                                // [COUT][CIN]
-    float* s_stat = s_wp + COUT * CIN;                           // [wave][MT*16][2]
+    float* s_w9 = s_trx + 3 * CIN;                               // [CIN][9]     (WLDS)
+    float* s_wp = s_w9 + (C::WLDS ? 9 * CIN : 0);                // [COUT][CIN]  (WLDS)
+    float* s_stat = s_wp + (C::WLDS ? COUT * CIN : 0);           // [wave][MT*16][2]
     const int H = tg.H, W = tg.W;
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: tile rows / first columns of the wave's N tiles become scalar code)
 
     fill_tr8(s_trx, x, tra, trb, CIN, tid);
-    for (int i = tid; i < 9 * CIN; i += NT) s_w9[i] = wdw[i];
-    for (int i = tid; i < COUT * CIN; i += NT) s_wp[i] = wpw[i];
+    if constexpr (C::WLDS) {
+        for (int i = tid; i < 9 * CIN; i += NT) s_w9[i] = wdw[i];
+        for (int i = tid; i < COUT * CIN; i += NT) s_wp[i] = wpw[i];
+    }
     {
         const uint4 z4 = make_uint4(0, 0, 0, 0);
         for (int i = tid; i < C::OFF_WF / 16; i += NT) reinterpret_cast<uint4*>(smem)[i] = z4;
     }
-    __syncthreads();
+    if constexpr (C::WLDS) __syncthreads();
     for (int f = tid; f < NST * MT * KC * 64; f += NT) {
         const int l = f & 63, kc = (f >> 6) % KC, mt = ((f >> 6) / KC) % MT, st = (f >> 6) / (KC * MT);
         const int m = (FULL && COUT == 8) ? (l & 7) : mt * 16 + (l & 15);  // FULL, COUT = 8: rows 8..15 duplicate rows 0..7
@@ -1154,7 +1160,8 @@ __global__ __launch_bounds__(512, (mm_fwd_lb<CINB, COUT>())) void k_mm_fwd(Src2<
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = kc * 32 + (l >> 4) * 8 + j, tap = k / CINB, c = st * CINB + k % CINB;
-            v[j] = (m < COUT && tap < 9) ? s_w9[c * 9 + tap] * s_wp[m * CIN + c] : 0.f;
+            if constexpr (C::WLDS) v[j] = (m < COUT && tap < 9) ? s_w9[c * 9 + tap] * s_wp[m * CIN + c] : 0.f;
+            else v[j] = (m < COUT && tap < 9) ? wdw[c * 9 + tap] * wpw[m * CIN + c] : 0.f;
         }
         s_wf[f] = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
     }

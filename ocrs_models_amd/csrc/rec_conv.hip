@@ -18,7 +18,7 @@ template <class T, int MT, int TH, int TW, int WM = 1>
 __global__ __launch_bounds__(256) void k_conv_igemm(const T* __restrict__ x, int ldx, const void* __restrict__ wpk, T* __restrict__ out, int ldo,
                                                     const float* __restrict__ bias, int relu, double* __restrict__ gstat, int Cin, int M,
                                                     int MT_total, int N, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw) {
-    constexpr int PITCH = Mma<T>::LDS_PITCH;
+    constexpr int PITCH = RecTile<T>::PITCH;
     constexpr int NTILES = TH * TW / 16, PTW = NTILES * WM / 4, TPR = TW / 16;  // N-tiles per block / per wave / per tile row
     constexpr int MTW = MT / WM;                                                // M-tiles per wave
     static_assert(NTILES % 4 == 0 && TW % 16 == 0 && MT % WM == 0 && (WM == 1 || WM == 2 || WM == 4), "tile shape");
@@ -1204,7 +1204,7 @@ static int launch_igemm(const void* x, int ldx, const void* wpk, void* out, int 
     const int HP = (TH + KH - 1) * (TW + KW - 1);
 #define IG(MT_)                                                                                                                                  \
     {                                                                                                                                            \
-        const size_t smem = ((HP * Mma<T>::LDS_PITCH * sizeof(T) + 15) & ~15) + 4 * 2 * MT_ * 16 * sizeof(float);                                   \
+        const size_t smem = ((HP * RecTile<T>::PITCH * sizeof(T) + 15) & ~15) + 4 * 2 * MT_ * 16 * sizeof(float);                                   \
         const int gy = (MT_total + MT_ - 1) / MT_;                                                                                               \
         constexpr int WM_ = (Elem<T>::is_bf16 && TH > 1) ? (MT_ >= 8 ? 4 : (MT_ >= 4 ? 2 : 1)) : 1; /* measured: 1382 -> 974 us, 270 -> 230 us */ \
         hipLaunchKernelGGL((k_conv_igemm<T, MT_, TH, TW, WM_>), dim3(persistent_grid(tiles, gy >= 4 ? 2 : 4), gy), dim3(256), smem, st, (const T*)x, ldx, \

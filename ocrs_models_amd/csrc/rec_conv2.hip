@@ -18,7 +18,7 @@ namespace {
 constexpr int C2_UNROLL = 1;  // tap loop unroll factor
 constexpr int C2_SPLIT = 4;   // N tiles whose MFMAs are issued before the LDS commit of the prefetched data (8 = all; 4: 149 -> 145 us)
 constexpr int C2_TW = 16, C2_ROWS = 16, C2_HW = C2_TW + 2;  // tile width, stacked rows, halo width
-constexpr int C2_PITCH = Mma<bf16>::LDS_PITCH;              // 40 bf16 = 80 B per staged pixel
+constexpr int C2_PITCH = RecTile<bf16>::PITCH;             // 40 bf16 = 80 B per staged pixel
 constexpr int C2_MAXHP = 2 * 10 * C2_HW;                    // staged pixels: NI * (TH + 2) * 18 -- 324 (1 x 16 rows) or 360 (2 x 8 rows)
 constexpr int C2_XBYTES = C2_MAXHP * C2_PITCH * 2;          // 28800
 constexpr int C2_WBYTES = 8 * 64 * 16;                      // 8 M tiles x 64 lanes x 16 B
