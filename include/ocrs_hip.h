@@ -526,6 +526,31 @@ int ocrs_rectify_crops_pages(const unsigned char* pages, long pages_bytes, const
                              const int* page_of_quad, const int* plan, const long long* totals, long max_tiles, float* packed, long packed_floats,
                              hipStream_t st);
 
+/* ------------------------------------------------------------------ reading order ------------- */
+/* The lines of every page in the order they are read, column by column, and where a new block starts, by the geometric rule of DESIGN.md §16
+ * (csrc/reading_order.hip; Python: inference.reading_order; restated in tests/reading_ref.py).  line_quads [cap][4][2] fp32 and n_lines [1] int
+ * as ocrs_line_quads / ocrs_line_order wrote them: L = min(*n_lines, cap) lines, in line order.  line_page_offs [B + 1] int as
+ * ocrs_line_order_pages wrote it (the lines of page p are line_page_offs[p] .. line_page_offs[p + 1]); NULL with B = 1: one page, lines 0 .. L.
+ * Every relation holds between lines of one page only; indices are flat line indices.  The three stages run in this order on one stream and
+ * share ws (ocrs_reading_order_ws_bytes(cap, B) bytes, 16-byte aligned; 0 = not supported: cap <= 32768), which carries the line extents from
+ * the first to the third.  Nothing synchronises and there are no atomics: equal input gives equal bytes.  cap == 0 or B == 0 launches nothing.
+ *
+ * ocrs_reading_relation (§16 "Page axis", "Extents", "before"): before [cap][ceil(cap / 32)] uint32, bit (b & 31) of word [a][b >> 5] set iff
+ * before(a, b); every word is written, rows and columns from L on and bits between lines of different pages as 0. */
+long ocrs_reading_order_ws_bytes(long cap, int B);
+int ocrs_reading_relation(const float* line_quads, const int* n_lines, const int* line_page_offs /* NULL = one page */, int B, long cap, unsigned* before,
+                          void* ws, long ws_bytes, hipStream_t st);
+/* §16 "Order": line_order [cap] int, positions line_page_offs[p] .. line_page_offs[p + 1] = the lines of page p in reading order; one workgroup
+ * per page peels the relation: the smallest unemitted line with no unemitted line before it, else (a cycle) the smallest unemitted line.
+ * before may be any matrix of that layout; only bits between lines of the same page are read.  Entries from L on are not written. */
+int ocrs_reading_peel(const int* n_lines, const int* line_page_offs, int B, long cap, const unsigned* before, int* line_order, void* ws, long ws_bytes,
+                      hipStream_t st);
+/* §16 "Blocks": new_block [cap] int, 1 where the line at that position of line_order starts a block (always at a page's first position), 0 where
+ * rule 1 puts the line before it there and the gap between them is at most block_gap times the taller of the two.  Reads the extents
+ * ocrs_reading_relation left in ws.  Entries from L on are not written. */
+int ocrs_reading_blocks(const int* n_lines, const int* line_page_offs, int B, long cap, float block_gap, const int* line_order, int* new_block, void* ws,
+                        long ws_bytes, hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

@@ -1,13 +1,14 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
-    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines]
+    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
 on the page).  With ``--rec-model`` the words are recognised too (``inference.ocr_page``'s stages) and printed, one JSON object per line.
 With ``--lines`` the words are grouped into text lines first (``inference.find_lines``): ``-text-lines.png`` shows the line quads, and with
 ``--rec-model`` every LINE is recognised (``inference.read_lines``) and printed as one JSON object with its quad, its text and its words' quads
-in reading order, instead of the words.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
+in reading order, instead of the words.  ``--lines --reading-order`` prints those objects in the page's reading order (column by column,
+``inference.reading_order``), each with ``"block"``, the number of its text block.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -51,7 +52,11 @@ def main(argv=None):
     parser.add_argument("--rec-model", help="recognition checkpoint: also recognise the words and print them as JSON lines")
     parser.add_argument("--lines", action="store_true", help="group the words into text lines: write -text-lines.png and, with --rec-model, "
                         "recognise and print one JSON object per line instead of per word")
+    parser.add_argument("--reading-order", action="store_true", help="with --lines and --rec-model: print the lines in reading order, column by "
+                        "column, each with the number of its block")
     args = parser.parse_args(argv)
+    if args.reading_order and not args.lines:
+        parser.error("--reading-order needs --lines")
 
     device = torch.device("cuda:0")
     model = DetectionModel().to(device)
@@ -83,7 +88,7 @@ def main(argv=None):
         rec.eval()
     if args.lines:
         if rec is not None:
-            lines = inference.read_lines(rec, page, det["quads"])
+            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order)
             for line in lines:
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]

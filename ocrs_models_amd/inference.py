@@ -37,6 +37,11 @@ Lines.  ``find_lines`` groups the word quads into text lines in reading order (c
 stated once in DESIGN.md §14 and restated for the tests in tests/lines_ref.py) without a host synchronisation, and ``ocr_lines`` is
 ``ocr_page`` with that stage in between: one crop and one string per line, the recogniser's training unit, with the same three waits.
 
+Reading order (csrc/reading_order.hip, C ABI section "reading order"; restated for the tests in tests/reading_ref.py).  Line
+order is top to bottom, so the columns of a page interleave.  ``reading_order`` puts the lines of every page into the order they are read,
+column by column, and marks where a new block starts, again without a host synchronisation; ``read_lines``, ``ocr_lines`` and ``ocr_pages`` take
+``reading_order=True`` to return their lines that way, with the same three waits; ``page_text`` joins such a result into one string.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
@@ -265,20 +270,34 @@ def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET) -> list[str]:
     return [texts[p] for p in perm]
 
 
-def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLines | None = None, n_lines: int = 0) -> list[dict]:
+def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLines | None = None, n_lines: int = 0, order: ReadingOrder | None = None,
+                line_page_offs: list | None = None) -> list[dict]:
     """The tail of ``ocr_page``, ``read_lines`` and ``ocr_pages``: ``recognize_crops`` on ``batches``, then the flat result list -- one
-    ``{"quad", "text"}`` per word, or with ``lines`` one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  The word quads
-    and the line tables travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of
-    their own)."""
+    ``{"quad", "text"}`` per word, or with ``lines`` one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  With ``order``
+    the list is in reading order -- position k holds line ``order.line_order[k]`` -- and every dict has ``"block"``, counted from 0 on every
+    page (``line_page_offs``: the host offsets of the pages' lines; None: one page).  The word quads, the line tables and the reading order
+    travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of their own)."""
     words_h = _to_host_async(words)
     if lines is not None:
         lq_h, order_h, offs_h = (_to_host_async(t) for t in (lines.quads, lines.word_order, lines.line_offsets))
+    if order is not None:
+        ro_h, nb_h = _to_host_async(order.line_order), _to_host_async(order.new_block)
     texts = recognize_crops(rec_model, batches, alphabet)
     wl = words_h.tolist()
     if lines is None:
         return [{"quad": q, "text": t} for q, t in zip(wl, texts)]
-    order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
-    return [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+    word_order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
+    out = [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in word_order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+    if order is None:
+        return out
+    ro, nb, read = ro_h[:n_lines].tolist(), nb_h[:n_lines].tolist(), []
+    pages = [0, n_lines] if line_page_offs is None else line_page_offs
+    for a, b in zip(pages, pages[1:]):
+        block = -1
+        for k in range(a, b):
+            block += 1 if (nb[k] or k == a) else 0
+            read.append({**out[ro[k]], "block": block})
+    return read
 
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
@@ -353,29 +372,102 @@ def find_lines(quads: torch.Tensor, count: torch.Tensor | None = None, max_gap: 
     return out
 
 
+@dataclass
+class ReadingOrder:
+    """What ``reading_order`` returns, all on the device.  With L lines: ``line_order[k]`` is the line read at position k and ``new_block[k]``
+    is 1 where that line starts a block; the positions ``line_page_offs[p]:line_page_offs[p + 1]`` hold the lines of page p (``0:L`` for a single
+    page).  ``before`` is the relation the order was peeled from: bit ``b & 31`` of ``before[a, b >> 5]`` (read as uint32) says that line a comes
+    before line b; bits between lines of different pages and rows and columns from L on are 0.  Entries of ``line_order`` and ``new_block`` from
+    L on are not written."""
+    line_order: torch.Tensor  # (N,) int32
+    new_block: torch.Tensor   # (N,) int32, 0 / 1 by position
+    before: torch.Tensor      # (N, ceil(N / 32)) int32 holding uint32 bit words
+
+
+def reading_order(lines: TextLines, block_gap: float = 1.0, out: ReadingOrder | None = None) -> ReadingOrder:
+    """The lines of ``find_lines`` / ``find_lines_pages`` in the order they are read, by the geometric rule of DESIGN.md §16
+    (csrc/reading_order.hip): all lines are projected on the page's mean text direction; a line comes before every line it overlaps
+    horizontally and lies above, and before every line entirely to its right unless a line between the two in height spans both (Breuel's two
+    rules); the order emits, again and again, the smallest line index with no unemitted line before it, or the smallest unemitted one where
+    the relation has a cycle.  A line starts a new block unless it overlaps the line read before it, lies below it and is at most ``block_gap``
+    times the taller of the two heights away.  Lines of different pages are never related.  ``out``: write into these tensors instead of new
+    ones.  Three stages of kernels, no host synchronisation; ``N == 0`` launches nothing."""
+    who = "reading_order"
+    if not isinstance(lines, TextLines):
+        raise RuntimeError(f"{who}: expected the TextLines of find_lines or find_lines_pages")
+    q = _need_quads(lines.quads, who)
+    n = q.shape[0]
+    n_lines = _need_counts(lines.n_lines, who)
+    offs, B = None, 1
+    if lines.line_page_offs is not None:
+        _need_cuda(lines.line_page_offs, who)
+        if lines.line_page_offs.dtype != torch.int32 or lines.line_page_offs.dim() != 1 or lines.line_page_offs.numel() < 2:
+            raise RuntimeError(f"{who}: line_page_offs must be (B+1,) int32 with B >= 1")
+        offs, B = lines.line_page_offs.contiguous(), lines.line_page_offs.numel() - 1
+    i32 = dict(dtype=torch.int32, device=q.device)
+    if out is None:
+        out = ReadingOrder(torch.empty(n, **i32), torch.empty(n, **i32), torch.empty(n, (n + 31) // 32, **i32))
+    else:
+        for name, shape in (("line_order", (n,)), ("new_block", (n,)), ("before", (n, (n + 31) // 32))):
+            t = getattr(out, name)
+            _need_cuda(t, who)
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous():
+                raise RuntimeError(f"{who}: out.{name} must be a contiguous {shape} int32 tensor")
+    if n == 0:
+        return out
+    L = lib()
+    ws_bytes = L.reading_order_ws_bytes(n, B)
+    if ws_bytes <= 0:
+        raise RuntimeError(f"{who}: {n} lines on {B} pages are not supported")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+    L.reading_relation(ptr(q), ptr(n_lines), ptr(offs), B, n, ptr(out.before), ptr(ws), ws_bytes)
+    L.reading_peel(ptr(n_lines), ptr(offs), B, n, ptr(out.before), ptr(out.line_order), ptr(ws), ws_bytes)
+    L.reading_blocks(ptr(n_lines), ptr(offs), B, n, float(block_gap), ptr(out.line_order), ptr(out.new_block), ptr(ws), ws_bytes)
+    return out
+
+
+_order_lines = reading_order  # (the drivers below take a keyword of the stage's name)
+
+
+def page_text(result: list[dict]) -> str:
+    """One page's result list of ``ocr_lines`` / ``read_lines`` / ``ocr_pages`` with ``reading_order=True`` -> its text: the lines of a block
+    joined with a newline, blocks with a blank line.  A list without ``"block"`` (line order) is one block."""
+    blocks, last = [], None
+    for line in result:
+        block = line.get("block", 0)
+        if not blocks or block != last:
+            blocks.append([])
+        blocks[-1].append(line["text"])
+        last = block
+    return "\n\n".join("\n".join(b) for b in blocks)
+
+
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
-               alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9) -> list[dict]:
+               alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
-    ahead of the recogniser on the same stream, so they have arrived when the labels have."""
+    ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
+    ``reading_order=True`` is queued behind the line stage and changes nothing about the crops (lines are cropped in line order)."""
     lines = find_lines(quads, None, max_gap, min_cos)
+    order = _order_lines(lines, block_gap) if reading_order else None
     plan = crop_plan(lines.quads, output_height, lines.n_lines)
     packed = rectify_crops(page_u8, lines.quads, plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0])
+    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order)
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
-              min_cos: float = 0.9) -> list[dict]:
+              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
-    returns ``[]`` without launching the recogniser."""
+    returns ``[]`` without launching the recogniser.  ``reading_order=True``: the same dicts in reading order (column by column
+    where line order interleaves the columns), each with ``"block"``, the number of its text block counted from 0; still three waits."""
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
-    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos)
+    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap)
 
 
 # ------------------------------------------------------------------ page batches ---------------------------------------------------------
@@ -567,13 +659,14 @@ def split_by_page(items: list, offs: list) -> list[list]:
 
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
-              min_cos: float = 0.9) -> list[list[dict]]:
+              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0) -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
     crop's chunk, and with it the padded width the recogniser sees, depends on the whole batch.  Three host synchronisations
     for the batch: the word offsets, the plan's totals (the line count and ``line_page_offs`` travel with them) and the labels.  A page
-    without words yields ``[]``; a batch without words returns without launching the recogniser; ``pages == []`` launches nothing."""
+    without words yields ``[]``; a batch without words returns without launching the recogniser; ``pages == []`` launches nothing.
+    ``reading_order=True`` (with ``lines``): every page's list in reading order with ``"block"``, as ``ocr_lines`` returns it; the same waits."""
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
@@ -588,6 +681,7 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
         word_offs_h.append(word_offs_h[-1] + c)
     if lines:
         tl = find_lines_pages(words, det["page_of_word"], det["word_offs"], max_gap, min_cos)
+        order = _order_lines(tl, block_gap) if reading_order else None
         plan = crop_plan(tl.quads, output_height, tl.n_lines)
         lpo_h = _to_host_async(tl.line_page_offs)  # queued ahead of the plan's totals: it has arrived when they have
         packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, tl.quads, tl.page_of_line, plan)
@@ -597,4 +691,5 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
     if not lines:
         return split_by_page(_read_crops(rec_model, batches, alphabet, words), word_offs_h)
-    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, plan.host()[0]), lpo_h.tolist())
+    n_lines, lpo = plan.host()[0], lpo_h.tolist()
+    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo), lpo)
