@@ -551,6 +551,36 @@ int ocrs_reading_peel(const int* n_lines, const int* line_page_offs, int B, long
 int ocrs_reading_blocks(const int* n_lines, const int* line_page_offs, int B, long cap, float block_gap, const int* line_order, int* new_block, void* ws,
                         long ws_bytes, hipStream_t st);
 
+/* ------------------------------------------------------------------ characters --------------- */
+/* Per-character time spans, page boxes and word ranges of recognised crops by the rule of DESIGN.md §17 (csrc/char_spans.hip; Python:
+ * text.greedy_decode_spans, inference.char_boxes / word_chars; restated in tests/chars_ref.py).  The span arrays labels, t0, t1 (int), peak,
+ * s0, s1 (fp32) and char_quads ([..][4][2] fp32, 16-byte aligned) have one row per crop at a row pitch of ld entries; the rows of a page are
+ * in the crop plan's width-sorted order: row p is the crop of quad plan[p][7].  Entries of a row from lens[row] on are neither read nor
+ * written.  Nothing synchronises, there are no atomics: equal input gives equal bytes.  Zero rows launch nothing.
+ *
+ * ocrs_ctc_greedy_decode that keeps where every character came from (§17 (a)): lp [T][N][C] fp32 log-probs, in_len [N]; sample n writes row
+ * row0 + n (ld >= T).  labels and lens are exactly what ocrs_ctc_greedy_decode writes (the arg-max is its arg-max: first maximum on ties);
+ * t0 / t1 = first / last time step of the run the character was collapsed from; peak = the largest lp[t][n][label] over the run, a bit copy
+ * of that input value.  amax (int), amax_lp (fp32) [N][T]: the arg-max and its value, written on the way (scratch of the caller's).  Two
+ * launches; the collapse is one wave per sample, 64 steps per round, any T. */
+int ocrs_ctc_decode_spans(const float* lp, const long long* in_len, int* amax, float* amax_lp, int T, int N, int C, long row0, int ld, int* labels, int* t0, int* t1,
+                          float* peak, int* lens, hipStream_t st);
+/* §17 (b) for the first `rows` rows: quads [cap][4][2] and plan [cap][8] as ocrs_crop_plan read and wrote them.  Character k of row p, crop of
+ * quad i = plan[p][7] with ow = plan[i][2]: a0 = clamp(4 t0 - 2, 0, ow), a1 = clamp(4 t1 + 2, 0, ow), s0 = (float)a0 / (float)ow * long side,
+ * s1 likewise (positions along the crop's width axis, page pixels); char_quads = P(s0, 0), P(s1, 0), P(s1, short side), P(s0, short side) in
+ * the crop frame of quad i (the frame ocrs_rectify_crops samples with).  A row whose plan[p][7] is outside 0..cap-1 is skipped. */
+int ocrs_char_boxes(const float* quads, const int* plan, long cap, long rows, int ld, const int* lens, const int* t0, const int* t1, float* s0, float* s1,
+                    float* char_quads, hipStream_t st);
+/* §17 (c), line crops only: words [wcap][4][2] and the line table (line_quads [cap][4][2], n_lines [1], line_offsets, word_order) as the
+ * "text lines" or "page batches" stages wrote them, plan [cap][8] made from line_quads, span rows as above (line l is row plan[l][6]).
+ * Word j of a line's chain owns the characters whose centre 0.5f * (s0 + s1) lies in [B_{j-1}, B_j), B_j = the running maximum of
+ * 0.5f * (hi_j + lo_{j+1}) over the words' extents along the line's axis; the range then gives up the characters labelled `space` at both
+ * ends (space < 0: none).  word_chars [wcap][2] int, indexed by the flat word index: (first, end) into the line's row; an empty range is
+ * (e, e).  One wave per line, 64 words per round; entries of words in no line are not written. */
+int ocrs_word_chars(const float* words, long wcap, const float* line_quads, const int* n_lines, long cap, const int* line_offsets, const int* word_order,
+                    const int* plan, long rows, int ld, const int* labels, const int* lens, const float* s0, const float* s1, int space, int* word_chars,
+                    hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

@@ -1,0 +1,35 @@
+// Crop frame: the one statement of the geometry rule (inference.py's docstring, "Crop frame"), used by the crop plan and the sampler
+// (ocr_infer.hip) and by the character boxes and word ranges (char_spans.hip), which turn positions along a crop back into page coordinates.
+#pragma once
+#include "common.h"
+
+struct CropFrame {
+    float ox, oy, ux, uy, lng, sht;  // origin corner, unit width axis u (v = (-uy, ux)), side lengths along u and v
+    int h, w;
+};
+__device__ __forceinline__ CropFrame crop_frame(const float* __restrict__ q) {
+    const float4 a = reinterpret_cast<const float4*>(q)[0], c = reinterpret_cast<const float4*>(q)[1];
+    const float xs[4] = {a.x, a.z, c.x, c.z}, ys[4] = {a.y, a.w, c.y, c.w};
+    const float e1x = xs[1] - xs[0], e1y = ys[1] - ys[0], e2x = xs[2] - xs[1], e2y = ys[2] - ys[1];
+    const float l1 = sqrtf(e1x * e1x + e1y * e1y), l2 = sqrtf(e2x * e2x + e2y * e2y);
+    const bool first = l1 > l2 || (l1 == l2 && fabsf(e1x) >= fabsf(e2x));  // the longer side; on a tie the one with the larger |x|
+    CropFrame f;
+    f.lng = first ? l1 : l2;
+    f.sht = first ? l2 : l1;
+    f.ux = 1.0f, f.uy = 0.0f;
+    if (f.lng > 0.0f) f.ux = (first ? e1x : e2x) / f.lng, f.uy = (first ? e1y : e2y) / f.lng;
+    if (f.ux < 0.0f || (f.ux == 0.0f && f.uy < 0.0f)) f.ux = -f.ux, f.uy = -f.uy;
+    // v = (-uy, ux); the origin is the corner that is first along u and along v, i.e. the smallest u + v projection
+    const float sx = f.ux - f.uy, sy = f.uy + f.ux;
+    int k = 0;
+    float best = xs[0] * sx + ys[0] * sy;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+        const float p = xs[j] * sx + ys[j] * sy;
+        if (p < best) best = p, k = j;
+    }
+    f.ox = xs[k], f.oy = ys[k];
+    f.w = (int)fminf(fmaxf(rintf(f.lng), 1.0f), 32768.0f);  // (fmaxf also turns a NaN length into 1)
+    f.h = (int)fminf(fmaxf(rintf(f.sht), 1.0f), 32768.0f);
+    return f;
+}

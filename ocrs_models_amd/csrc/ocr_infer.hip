@@ -14,6 +14,7 @@
 //                               crop_of_tile() and sample it with rectify_tile(), the one statement of the sampler
 //
 // All of them are small and byte-bound: no LDS tiles, no MFMA; coalesced 4..16-byte vector accesses; every count stays on the device.
+#include "crop_frame.h"
 #include "input_pipe.h"
 
 namespace {
@@ -154,37 +155,7 @@ __global__ __launch_bounds__(256) void k_gather_page_quads(const float* __restri
     page_of_word[base + r] = b;
 }
 
-// ---- crop frame: the one statement of the geometry rule, used by the plan and by the sampler ----------------------------------------
-struct CropFrame {
-    float ox, oy, ux, uy, lng, sht;  // origin corner, unit width axis u (v = (-uy, ux)), side lengths along u and v
-    int h, w;
-};
-__device__ __forceinline__ CropFrame crop_frame(const float* __restrict__ q) {
-    const float4 a = reinterpret_cast<const float4*>(q)[0], c = reinterpret_cast<const float4*>(q)[1];
-    const float xs[4] = {a.x, a.z, c.x, c.z}, ys[4] = {a.y, a.w, c.y, c.w};
-    const float e1x = xs[1] - xs[0], e1y = ys[1] - ys[0], e2x = xs[2] - xs[1], e2y = ys[2] - ys[1];
-    const float l1 = sqrtf(e1x * e1x + e1y * e1y), l2 = sqrtf(e2x * e2x + e2y * e2y);
-    const bool first = l1 > l2 || (l1 == l2 && fabsf(e1x) >= fabsf(e2x));  // the longer side; on a tie the one with the larger |x|
-    CropFrame f;
-    f.lng = first ? l1 : l2;
-    f.sht = first ? l2 : l1;
-    f.ux = 1.0f, f.uy = 0.0f;
-    if (f.lng > 0.0f) f.ux = (first ? e1x : e2x) / f.lng, f.uy = (first ? e1y : e2y) / f.lng;
-    if (f.ux < 0.0f || (f.ux == 0.0f && f.uy < 0.0f)) f.ux = -f.ux, f.uy = -f.uy;
-    // v = (-uy, ux); the origin is the corner that is first along u and along v, i.e. the smallest u + v projection
-    const float sx = f.ux - f.uy, sy = f.uy + f.ux;
-    int k = 0;
-    float best = xs[0] * sx + ys[0] * sy;
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-        const float p = xs[j] * sx + ys[j] * sy;
-        if (p < best) best = p, k = j;
-    }
-    f.ox = xs[k], f.oy = ys[k];
-    f.w = (int)fminf(fmaxf(rintf(f.lng), 1.0f), 32768.0f);  // (fmaxf also turns a NaN length into 1)
-    f.h = (int)fminf(fmaxf(rintf(f.sht), 1.0f), 32768.0f);
-    return f;
-}
+// ---- crop frame: CropFrame / crop_frame(), the one statement of the geometry rule, live in crop_frame.h (char_spans.hip uses them too) ------
 
 // hiertext.py:288-292 / input_pipeline.line_output_width, in the host's fp64 arithmetic
 __device__ __forceinline__ int line_output_width(int h, int w, int OH) {

@@ -59,7 +59,7 @@ constexpr long kWsBytesPerWord = 32 + 8 + 11 * 4;
 __device__ __forceinline__ int word_count(const int* __restrict__ count, long cap) { return (int)(count ? min((long)max(*count, 0), cap) : cap); }
 
 // ---- word frame ------------------------------------------------------------------------------------------------------------------
-// The same choice of axes as crop_frame() of ocr_infer.hip (longer side, tie -> larger |x|, sign so that u.x > 0 or u.x == 0 and u.y > 0),
+// The same choice of axes as crop_frame() of crop_frame.h (longer side, tie -> larger |x|, sign so that u.x > 0 or u.x == 0 and u.y > 0),
 // kept as this file's own text so that neither can change the other's bits.
 __global__ __launch_bounds__(256) void k_line_frames(const float* __restrict__ quads, const int* __restrict__ count, long cap, float* __restrict__ frames,
                                                      unsigned long long* __restrict__ accept, int* __restrict__ len_sorted, int* __restrict__ head_of_line) {

@@ -1,6 +1,6 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
-    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]]
+    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]] [--chars]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
@@ -8,7 +8,9 @@ on the page).  With ``--rec-model`` the words are recognised too (``inference.oc
 With ``--lines`` the words are grouped into text lines first (``inference.find_lines``): ``-text-lines.png`` shows the line quads, and with
 ``--rec-model`` every LINE is recognised (``inference.read_lines``) and printed as one JSON object with its quad, its text and its words' quads
 in reading order, instead of the words.  ``--lines --reading-order`` prints those objects in the page's reading order (column by column,
-``inference.reading_order``), each with ``"block"``, the number of its text block.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
+``inference.reading_order``), each with ``"block"``, the number of its text block.  ``--chars`` (with ``--rec-model``) adds to every object where each
+character of its text sits on the page and the recogniser's log-prob of it (``"char_quads"``, ``"char_log_probs"``), and to every line object the text and
+character range of each of its words (``"word_texts"``, ``"word_chars"``): ``inference.char_boxes`` / ``word_chars``.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -54,6 +56,8 @@ def main(argv=None):
                         "recognise and print one JSON object per line instead of per word")
     parser.add_argument("--reading-order", action="store_true", help="with --lines and --rec-model: print the lines in reading order, column by "
                         "column, each with the number of its block")
+    parser.add_argument("--chars", action="store_true", help="with --rec-model: add every character's quad and log-prob to the JSON objects and, with "
+                        "--lines, every word's text and character range")
     args = parser.parse_args(argv)
     if args.reading_order and not args.lines:
         parser.error("--reading-order needs --lines")
@@ -88,7 +92,7 @@ def main(argv=None):
         rec.eval()
     if args.lines:
         if rec is not None:
-            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order)
+            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars)
             for line in lines:
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]
@@ -99,9 +103,15 @@ def main(argv=None):
     elif rec is not None:
         plan = inference.crop_plan(det["quads"])
         packed = inference.rectify_crops(page, det["quads"], plan)
-        texts = inference.recognize_crops(rec, inference.crops_to_batches(packed, plan))
-        for quad, text in zip(quads, texts):
-            print(json.dumps({"quad": quad, "text": text}))
+        batches = inference.crops_to_batches(packed, plan)
+        if args.chars:
+            spans = inference.decode_crop_spans(rec, batches)
+            texts, chars, _ = inference.chars_to_host(spans, inference.char_boxes(det["quads"], plan, spans))
+            for quad, p in zip(quads, batches[2]):
+                print(json.dumps({"quad": quad, "text": texts[p], **chars[p]}))
+        else:
+            for quad, text in zip(quads, inference.recognize_crops(rec, batches)):
+                print(json.dumps({"quad": quad, "text": text}))
 
 
 if __name__ == "__main__":

@@ -42,6 +42,12 @@ order is top to bottom, so the columns of a page interleave.  ``reading_order`` 
 column by column, and marks where a new block starts, again without a host synchronisation; ``read_lines``, ``ocr_lines`` and ``ocr_pages`` take
 ``reading_order=True`` to return their lines that way, with the same three waits; ``page_text`` joins such a result into one string.
 
+Characters (csrc/char_spans.hip, C ABI section "characters"; restated for the tests in tests/chars_ref.py).  With ``chars=True``
+``recognize_crops``, ``ocr_page``, ``read_lines``, ``ocr_lines`` and ``ocr_pages`` keep what the greedy decode otherwise drops -- the time steps every
+character was collapsed from and its log-prob -- and return, next to the keys they always return, every character's quad on the page
+(``char_boxes``: time steps to crop columns to the page through the crop frame) and, for lines, the characters and the text of every word
+(``word_chars``: neighbouring words split the line half way between them; spaces at the ends of a range are dropped); the same three waits.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
@@ -55,7 +61,7 @@ import torch
 
 from ._lib import lib, ptr
 from .input_pipeline import _need_cuda, resize, transform_image
-from .text import DEFAULT_ALPHABET, decode_text, greedy_decode_batch_async, round_up
+from .text import DEFAULT_ALPHABET, decode_text, greedy_decode_batch_async, greedy_decode_spans_async, round_up, span_arrays
 
 MASK_SIZE = (800, 600)   # train_detection.py's mask_size: the size the detection model is trained and evaluated at
 SHRINK_DISTANCE = 3.0    # datasets/util.py: how far text polygons are shrunk when training masks are made
@@ -252,10 +258,131 @@ def crops_to_batches(packed: torch.Tensor, plan: CropPlan, max_batch: int = 256,
     return batches, image_widths, plan.host_perm()
 
 
-def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET) -> list[str]:
+@dataclass
+class CharSpans:
+    """What the recogniser's greedy decode keeps per character, on the device: one row per crop at a pitch of ``ld``
+    entries, rows in the crop plan's width-sorted order (row p is the crop of quad ``plan.table[p, 7]``).  Character k of row p has label
+    ``labels[p, k]``, was collapsed from the time steps ``t0[p, k] .. t1[p, k]`` and has the log-prob ``peak[p, k]``, the largest of its class
+    over those steps; ``lens[p]`` characters.  Entries of a row from ``lens[p]`` on are not written.  ``buf`` is the one int32 buffer all five
+    are views of (``text.span_arrays``): one copy brings them to the host."""
+    buf: torch.Tensor
+    labels: torch.Tensor  # (R,ld) int32
+    t0: torch.Tensor      # (R,ld) int32
+    t1: torch.Tensor      # (R,ld) int32
+    peak: torch.Tensor    # (R,ld) fp32
+    lens: torch.Tensor    # (R,) int32
+
+    def arrays(self):
+        return self.buf, self.labels, self.t0, self.t1, self.peak, self.lens
+
+
+@dataclass
+class CharBoxes:
+    """What ``char_boxes`` returns, on the device, rows and pitch as in ``CharSpans``: ``s0`` / ``s1`` (R,ld) fp32, where the character starts
+    and ends along its crop's width axis in page pixels, and ``quads`` (R,ld,4,2) fp32, its rectangle on the page."""
+    s0: torch.Tensor
+    s1: torch.Tensor
+    quads: torch.Tensor
+
+
+def _check_batches(rec_model, batches, who: str):
+    for b in batches[0]:
+        _need_cuda(b, who)
+    if rec_model.training:
+        raise RuntimeError(f"{who}: the model must be in eval mode (model.eval())")
+
+
+def decode_crop_spans(rec_model, batches) -> CharSpans:
+    """Eval forward of the recogniser per batch, as ``recognize_crops``, with the decode that keeps the spans: the chunks write their rows
+    into one set of arrays whose pitch is the longest chunk's number of time steps.  Every forward is queued before the first decode (the
+    pitch is known once the last forward has its shape); no synchronisation, nothing is copied."""
+    _check_batches(rec_model, batches, "decode_crop_spans")
+    imgs, image_widths, _ = batches
+    with torch.inference_mode():
+        lps = [rec_model(img) for img in imgs]
+    rows = sum(lp.shape[1] for lp in lps)
+    dev = lps[0].device if lps else torch.device("cuda", torch.cuda.current_device())
+    spans = CharSpans(*span_arrays(rows, max([lp.shape[0] for lp in lps], default=1), dev))
+    row = 0
+    for lp, iw in zip(lps, image_widths):
+        greedy_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), spans.arrays(), row)
+        row += lp.shape[1]
+    return spans
+
+
+def char_boxes(quads: torch.Tensor, plan: CropPlan, spans: CharSpans) -> CharBoxes:
+    """Where every character of every crop sits on the page (``ocrs_char_boxes``): ``quads`` (N,4,2) and ``plan`` are what
+    the crops were cut with, ``spans`` what ``decode_crop_spans`` wrote for them.  Time step t is centred on column 4 t of the resized crop; a
+    character reaches from two columns before its first step to two after its last, clamped to the crop, and that stretch of the crop's
+    width axis, over the crop's full height, is mapped to the page through the crop frame.  One launch, no synchronisation."""
+    q = _need_quads(quads, "char_boxes", plan=plan)
+    rows, ld = spans.labels.shape
+    if rows > q.shape[0]:
+        raise RuntimeError("char_boxes: more span rows than quads")
+    f32 = dict(dtype=torch.float32, device=q.device)
+    out = CharBoxes(torch.empty(rows, ld, **f32), torch.empty(rows, ld, **f32), torch.empty(rows, ld, 4, 2, **f32))
+    lib().char_boxes(ptr(q), ptr(plan.table), q.shape[0], rows, ld, ptr(spans.lens), ptr(spans.t0), ptr(spans.t1), ptr(out.s0), ptr(out.s1), ptr(out.quads))
+    return out
+
+
+def space_label(alphabet) -> int:
+    """the label of the space character (``alphabet.index(" ") + 1``), or -1 if the alphabet has none"""
+    alphabet = list(alphabet)
+    return alphabet.index(" ") + 1 if " " in alphabet else -1
+
+
+def word_chars(lines: TextLines, plan: CropPlan, spans: CharSpans, boxes: CharBoxes, alphabet=DEFAULT_ALPHABET) -> torch.Tensor:
+    """Which characters of its line every word lies over (``ocrs_word_chars``): ``lines`` from ``find_lines`` /
+    ``find_lines_pages``, ``plan`` made from ``lines.quads``, ``spans`` and ``boxes`` of those line crops -> (N,2) int32 on the device, indexed by
+    the flat word index: ``(first, end)`` into the characters of the word's line.  Neighbouring words split the line half way between the end
+    of one and the start of the next along the line's axis; spaces at either end of a range are dropped.  One launch, no synchronisation."""
+    who = "word_chars"
+    if not isinstance(lines, TextLines) or lines.words is None:
+        raise RuntimeError(f"{who}: expected the TextLines of find_lines or find_lines_pages")
+    words = _need_quads(lines.words, who)
+    _need_quads(lines.quads, who, plan=plan)
+    n = words.shape[0]
+    rows, ld = spans.labels.shape
+    if rows > n or tuple(boxes.s0.shape) != (rows, ld):
+        raise RuntimeError(f"{who}: spans and boxes must be those of the lines' crops")
+    out = torch.empty(n, 2, dtype=torch.int32, device=words.device)
+    lib().word_chars(ptr(words), n, ptr(lines.quads), ptr(lines.n_lines), n, ptr(lines.line_offsets), ptr(lines.word_order), ptr(plan.table), rows, ld,
+                     ptr(spans.labels), ptr(spans.lens), ptr(boxes.s0), ptr(boxes.s1), space_label(alphabet), ptr(out))
+    return out
+
+
+def chars_to_host(spans: CharSpans, boxes: CharBoxes, alphabet=DEFAULT_ALPHABET, ranges: torch.Tensor | None = None):
+    """The characters on the host, in the rows' (width-sorted) order: ``(texts, chars, ranges)`` with ``chars[p] = {"char_quads": [4x2 lists],
+    "char_log_probs": [floats]}``, one entry per character of ``texts[p]``, and ``ranges`` the (N,2) result of ``word_chars`` as a list (None
+    without it).  Three copies queued on the current stream and ONE wait for all of them."""
+    alphabet = list(alphabet)
+    sp_h, cq_h = _to_host_async(spans.buf), _to_host_async(boxes.quads)
+    rg_h = None if ranges is None else _to_host_async(ranges)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(spans.buf.device))
+    done.synchronize()
+    rows, ld = spans.labels.shape
+    labels, peak = sp_h[:rows * ld].view(rows, ld), sp_h[3 * rows * ld:4 * rows * ld].view(rows, ld).view(torch.float32)
+    lens = sp_h[4 * rows * ld:].tolist()
+    texts = [decode_text(labels[p, :n], alphabet) for p, n in enumerate(lens)]
+    chars = [{"char_quads": cq_h[p, :n].tolist(), "char_log_probs": peak[p, :n].tolist()} for p, n in enumerate(lens)]
+    return texts, chars, None if rg_h is None else rg_h.tolist()
+
+
+def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = False):
     """Eval forward of the recogniser per batch with ``input_lengths = image_width // 4`` (as ``train_rec.test``) and the device greedy
     decode.  ``batches`` is what ``crops_to_batches`` returned: ``(batch tensors, image widths, perm)``.  Returns the strings in quad order.
-    Every chunk's forward and decode are queued before the first label copy is waited for."""
+    Every chunk's forward and decode are queued before the first label copy is waited for.  ``chars=True``: ``(strings in quad order,
+    CharSpans)`` -- the same strings from the decode that keeps every character's time steps and log-prob (``decode_crop_spans``), whose
+    device arrays ``char_boxes`` and ``word_chars`` take; one wait, for the one copy of the span buffer."""
+    if chars:
+        spans = decode_crop_spans(rec_model, batches)
+        sp_h = _to_host_async(spans.buf)
+        torch.cuda.current_stream(spans.buf.device).synchronize()
+        rows, ld = spans.labels.shape
+        lens, alphabet = sp_h[4 * rows * ld:].tolist(), list(alphabet)
+        texts = [decode_text(row[:n], alphabet) for row, n in zip(sp_h[:rows * ld].view(rows, ld), lens)]
+        return [texts[p] for p in batches[2]], spans
     batches, image_widths, perm = batches
     for b in batches:
         _need_cuda(b, "recognize_crops")
@@ -271,23 +398,40 @@ def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET) -> list[str]:
 
 
 def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLines | None = None, n_lines: int = 0, order: ReadingOrder | None = None,
-                line_page_offs: list | None = None) -> list[dict]:
+                line_page_offs: list | None = None, chars_plan: CropPlan | None = None) -> list[dict]:
     """The tail of ``ocr_page``, ``read_lines`` and ``ocr_pages``: ``recognize_crops`` on ``batches``, then the flat result list -- one
     ``{"quad", "text"}`` per word, or with ``lines`` one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  With ``order``
     the list is in reading order -- position k holds line ``order.line_order[k]`` -- and every dict has ``"block"``, counted from 0 on every
     page (``line_page_offs``: the host offsets of the pages' lines; None: one page).  The word quads, the line tables and the reading order
-    travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of their own)."""
+    travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of their own).
+    ``chars_plan`` (the plan the crops were cut with; ``chars=True`` of the callers): every dict also has ``"char_quads"`` and
+    ``"char_log_probs"``, line dicts ``"word_chars"`` and ``"word_texts"`` too.  The boxes and word ranges are queued behind the
+    decodes and copied with the labels: still one wait here."""
     words_h = _to_host_async(words)
     if lines is not None:
         lq_h, order_h, offs_h = (_to_host_async(t) for t in (lines.quads, lines.word_order, lines.line_offsets))
     if order is not None:
         ro_h, nb_h = _to_host_async(order.line_order), _to_host_async(order.new_block)
-    texts = recognize_crops(rec_model, batches, alphabet)
+    if chars_plan is None:
+        texts = recognize_crops(rec_model, batches, alphabet)
+    else:
+        spans = decode_crop_spans(rec_model, batches)
+        boxes = char_boxes(words if lines is None else lines.quads, chars_plan, spans)
+        ranges = None if lines is None else word_chars(lines, chars_plan, spans, boxes, alphabet)
+        texts, chars, ranges = chars_to_host(spans, boxes, alphabet, ranges)
+        perm = batches[2]
+        texts, chars = [texts[p] for p in perm], [chars[p] for p in perm]
     wl = words_h.tolist()
     if lines is None:
+        if chars_plan is not None:
+            return [{"quad": q, "text": t, **c} for q, t, c in zip(wl, texts, chars)]
         return [{"quad": q, "text": t} for q, t in zip(wl, texts)]
     word_order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
     out = [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in word_order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+    if chars_plan is not None:
+        for l, d in enumerate(out):
+            rg = [ranges[i] for i in word_order[offs[l]:offs[l + 1]]]
+            d.update(chars[l], word_chars=rg, word_texts=[d["text"][a:b] for a, b in rg])
     if order is None:
         return out
     ro, nb, read = ro_h[:n_lines].tolist(), nb_h[:n_lines].tolist(), []
@@ -301,16 +445,18 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
 
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
-             output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET) -> list[dict]:
+             output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, chars: bool = False) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
-    A page without components returns ``[]`` without launching the recogniser."""
+    A page without components returns ``[]`` without launching the recogniser.  ``chars=True``: every dict also has ``"char_quads"``, the
+    rectangle of every character of ``"text"`` on the page, and ``"char_log_probs"``, the recogniser's log-prob of each; the
+    same three waits."""
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
     quads = det["quads"]
     plan = crop_plan(quads, output_height)
     packed = rectify_crops(page_u8, quads, plan)
-    return _read_crops(rec_model, crops_to_batches(packed, plan, max_batch, width_unit), alphabet, quads)
+    return _read_crops(rec_model, crops_to_batches(packed, plan, max_batch, width_unit), alphabet, quads, chars_plan=plan if chars else None)
 
 
 # ------------------------------------------------------------------ words -> lines -------------------------------------------------------
@@ -328,6 +474,7 @@ class TextLines:
     next_word: torch.Tensor     # (N,) int32
     line_page_offs: torch.Tensor | None = None  # (B+1,) int32, find_lines_pages only: the lines of page p are line_page_offs[p]:line_page_offs[p+1]
     page_of_line: torch.Tensor | None = None    # (N,) int32, find_lines_pages only: rows up to L
+    words: torch.Tensor | None = None           # (N,4,2) fp32: the word quads the lines were found in (what ``word_chars`` projects on a line's axis)
 
 
 def _empty_lines(n: int, device, pages: int | None = None) -> TextLines:
@@ -360,6 +507,7 @@ def find_lines(quads: torch.Tensor, count: torch.Tensor | None = None, max_gap: 
             _need_cuda(t, "find_lines")
             if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
                 raise RuntimeError(f"find_lines: out.{name} must be a contiguous {shape} {dtype} tensor")
+    out.words = q
     if n == 0:
         return out
     L = lib()
@@ -443,31 +591,36 @@ def page_text(result: list[dict]) -> str:
 
 
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
-               alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0) -> list[dict]:
+               alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0,
+               chars: bool = False) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
     ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
-    ``reading_order=True`` is queued behind the line stage and changes nothing about the crops (lines are cropped in line order)."""
+    ``reading_order=True`` is queued behind the line stage and changes nothing about the crops (lines are cropped in line order).
+    ``chars=True``: the characters' quads, log-probs and word ranges as ``ocr_lines`` describes them, queued behind the decodes; the same waits."""
     lines = find_lines(quads, None, max_gap, min_cos)
     order = _order_lines(lines, block_gap) if reading_order else None
     plan = crop_plan(lines.quads, output_height, lines.n_lines)
     packed = rectify_crops(page_u8, lines.quads, plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order)
+    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order, chars_plan=plan if chars else None)
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
-              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0) -> list[dict]:
+              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
     returns ``[]`` without launching the recogniser.  ``reading_order=True``: the same dicts in reading order (column by column
-    where line order interleaves the columns), each with ``"block"``, the number of its text block counted from 0; still three waits."""
+    where line order interleaves the columns), each with ``"block"``, the number of its text block counted from 0; still three waits.
+    ``chars=True``: every dict keeps those keys and gains ``"char_quads"`` (one 4x2 list per character of ``"text"``: where it
+    sits on the page), ``"char_log_probs"`` (the recogniser's log-prob of each), ``"word_chars"`` (parallel to ``"words"``: the ``[first, end]``
+    of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits."""
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
-    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap)
+    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars)
 
 
 # ------------------------------------------------------------------ page batches ---------------------------------------------------------
@@ -614,6 +767,7 @@ def find_lines_pages(quads: torch.Tensor, page_of_word: torch.Tensor, word_offs:
     B = word_offs.numel() - 1
     offs = word_offs.contiguous()
     out = _empty_lines(n, q.device, B)
+    out.words = q
     if n == 0:
         return out
     L = lib()
@@ -659,14 +813,15 @@ def split_by_page(items: list, offs: list) -> list[list]:
 
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
-              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0) -> list[list[dict]]:
+              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False) -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
     crop's chunk, and with it the padded width the recogniser sees, depends on the whole batch.  Three host synchronisations
     for the batch: the word offsets, the plan's totals (the line count and ``line_page_offs`` travel with them) and the labels.  A page
     without words yields ``[]``; a batch without words returns without launching the recogniser; ``pages == []`` launches nothing.
-    ``reading_order=True`` (with ``lines``): every page's list in reading order with ``"block"``, as ``ocr_lines`` returns it; the same waits."""
+    ``reading_order=True`` (with ``lines``): every page's list in reading order with ``"block"``, as ``ocr_lines`` returns it; the same waits.
+    ``chars=True``: the character keys of ``ocr_lines`` / ``ocr_page`` in every dict; the same waits."""
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
@@ -690,6 +845,6 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
         packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, words, det["page_of_word"], plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
     if not lines:
-        return split_by_page(_read_crops(rec_model, batches, alphabet, words), word_offs_h)
+        return split_by_page(_read_crops(rec_model, batches, alphabet, words, chars_plan=plan if chars else None), word_offs_h)
     n_lines, lpo = plan.host()[0], lpo_h.tolist()
-    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo), lpo)
+    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo, plan if chars else None), lpo)

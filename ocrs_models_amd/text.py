@@ -111,6 +111,77 @@ def greedy_decode_batch(log_probs: torch.Tensor, input_lengths):
     return h.result(), h.amax
 
 
+def span_arrays(rows: int, ld: int, device):
+    """The output arrays of ``ocrs_ctc_decode_spans`` for ``rows`` samples at a row pitch of ``ld``, as views of ONE int32 device buffer
+    ``labels | t0 | t1 | peak | lens`` (so that one copy brings all of them to the host) -> ``(buf, labels, t0, t1, peak, lens)``; ``peak`` is
+    the float32 view of its part.  Not initialised: entries of a row from its length on are never written."""
+    buf = torch.empty(4 * rows * ld + rows, dtype=torch.int32, device=device)
+    part = [buf[k * rows * ld:(k + 1) * rows * ld].view(rows, ld) for k in range(4)]
+    return buf, part[0], part[1], part[2], part[3].view(torch.float32), buf[4 * rows * ld:]
+
+
+class _DecodeSpans:
+    """Result handle of greedy_decode_spans_async: the span arrays on the device, and on their way into pinned host memory."""
+
+    def __init__(self, arrays, host, event, N, ld, amax):
+        (self.buf, self.labels, self.t0, self.t1, self.peak, self.lens), self.host, self.event, self.N, self.ld, self.amax = arrays, host, event, N, ld, amax
+
+    def result(self):
+        """list of N dicts ``labels``, ``t0``, ``t1`` (int lists) and ``peak`` (float list), one entry per character (waits for the copy only)"""
+        self.event.synchronize()
+        N, ld = self.N, self.ld
+        part = [self.host[k * N * ld:(k + 1) * N * ld].view(N, ld) for k in range(4)]
+        lens = self.host[4 * N * ld:].tolist()
+        labels, t0, t1, peak = part[0].tolist(), part[1].tolist(), part[2].tolist(), part[3].view(torch.float32).tolist()
+        return [{"labels": labels[i][:n], "t0": t0[i][:n], "t1": t1[i][:n], "peak": peak[i][:n]} for i, n in enumerate(lens)]
+
+
+def greedy_decode_spans_async(log_probs: torch.Tensor, input_lengths, out=None, row0: int = 0):
+    """``greedy_decode_batch_async`` that keeps where every character came from (``ocrs_ctc_decode_spans``): (T,N,C)
+    log-probs on the GPU -> per character its label, the first and last time step of the run it was collapsed from and the largest
+    log-prob of its class over that run.  Labels and lengths are exactly those of ``greedy_decode_batch_async``.
+
+    ``out=None``: new arrays (pitch T) and a handle whose ``result()`` waits for ONE non-blocking copy of all of them.  ``out`` = the tuple of
+    ``span_arrays`` shared by the chunks of a page: sample n writes row ``row0 + n``, nothing is copied and None is returned -- the caller
+    copies the buffer once, after its last chunk.  Runs on the current stream."""
+    lp = log_probs.contiguous().float()
+    if lp.dim() != 3 or not lp.is_cuda:
+        raise RuntimeError("greedy_decode_spans: expected (T,N,C) log-probs on the GPU (no CPU path)")
+    T, N, C = lp.shape
+    if T < 1 or C < 1:
+        raise RuntimeError("greedy_decode_spans: expected at least one time step and one class")
+    dev = lp.device
+    il = torch.as_tensor(input_lengths, dtype=torch.int64)
+    if not il.is_cuda:
+        il = il.pin_memory().to(dev, non_blocking=True) if il.numel() else il.to(dev)
+    il = il.contiguous()
+    if il.numel() != N:
+        raise RuntimeError(f"greedy_decode_spans: {il.numel()} input lengths for {N} samples")
+    own = out is None
+    if own:
+        out, row0 = span_arrays(N, T, dev), 0
+    _, labels, t0, t1, peak, lens = out
+    rows, ld = labels.shape
+    if ld < T or row0 < 0 or row0 + N > rows or lens.numel() != rows:
+        raise RuntimeError(f"greedy_decode_spans: rows {row0}..{row0 + N} of pitch {T} do not fit span arrays of {rows} rows of pitch {ld}")
+    amax = torch.empty(N, T, dtype=torch.int32, device=dev)
+    amax_lp = torch.empty(N, T, dtype=torch.float32, device=dev)
+    if N:
+        lib().ctc_decode_spans(ptr(lp), ptr(il), ptr(amax), ptr(amax_lp), T, N, C, int(row0), ld, ptr(labels), ptr(t0), ptr(t1), ptr(peak), ptr(lens))
+    if not own:
+        return None
+    host = torch.empty(out[0].numel(), dtype=torch.int32, pin_memory=True)
+    host.copy_(out[0], non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    return _DecodeSpans(out, host, ev, N, T, amax)
+
+
+def greedy_decode_spans(log_probs: torch.Tensor, input_lengths):
+    """(T,N,C) log-probs on the GPU -> list of N dicts ``labels``, ``t0``, ``t1``, ``peak``, one entry per character (one D2H copy)."""
+    return greedy_decode_spans_async(log_probs, input_lengths).result()
+
+
 def levenshtein(a, b) -> int:
     prev = list(range(len(b) + 1))
     for i, ca in enumerate(a, 1):
