@@ -23,6 +23,7 @@ from torch import nn
 
 from ._lib import lib, ptr
 from .models import _check_versions
+from .packs import EMPTY as EMPTY_PACKS, cached_table, dgrad_row, fwd_row
 
 D_MODEL, N_HEADS, D_FF, N_LAYERS, N_CLASSES = 256, 4, 1024, 6, 2
 LDL = 32  # row pitch of the padded classify output / gradient (the GEMM entry points want K % 32 == 0)
@@ -78,6 +79,8 @@ _ORDER = ["classify."] + [f"encode.layers.{i}.{part}" for i in reversed(range(N_
 
 
 class _LayoutRun:
+    packs = EMPTY_PACKS  # this step's weight-fragment packs (prepack)
+
     def __init__(self, mod, boxes, names, params, train, x3, p_drop, seed):
         self.L = lib()
         self.mod = mod
@@ -91,7 +94,7 @@ class _LayoutRun:
         self.R = self.N * self.W
         self.p = float(p_drop) if train else 0.0
         self.seed = seed
-        self.packs = {}
+        self.frag = (1, 2) if x3 else (0, 0)  # (fragment dtype, pack mode): pre-split hi / lo bf16 planes for the pipelined x3 GEMM, or exact fp32
 
     def empty(self, *shape):
         return torch.empty(shape, dtype=torch.float32, device=self.dev)
@@ -104,35 +107,21 @@ class _LayoutRun:
             out += [pre + "self_attn.in_proj_weight", pre + "self_attn.out_proj.weight", pre + "linear1.weight", pre + "linear2.weight"]
         return out
 
+    def pack_rows(self, need_dgrad):
+        """A[m][k] = W[m][k] for the forward, A[m][k] = W[k][m] for the input gradients (layer 0's in_proj has none: the embedding has no
+        parameters).  classify (2 x 256) is packed in parity mode only; in x3 mode it runs on ocrs_gemm_x3 from the master layout."""
+        rows = []
+        for n in self._linear_names() + ([] if self.x3 else ["classify.weight"]):
+            rows.append(fwd_row(self.P[n], *self.frag))
+            if need_dgrad and not n.startswith("encode.layers.0.self_attn.in_proj"):
+                rows.append(dgrad_row(self.P[n], *self.frag))
+        return rows
+
     def prepack(self, need_dgrad):
-        """All weight-fragment packs of the step in one launch: exact-fp32 fragments (parity mode) or pre-split hi / lo bf16 planes (pack mode 2,
-        the pipelined x3 GEMM).  A[m][k] = W[m][k] for the forward, A[m][k] = W[k][m] for the input gradients.  classify (2 x 256) is packed too
-        in parity mode; in x3 mode it runs on ocrs_gemm_x3 from the master layout.  The pointer table is cached while the parameters stay put."""
-        P, L = self.P, self.L
-        dt, mode = (1, 2) if self.x3 else (0, 0)
-        key = (dt, need_dgrad, tuple(p.data_ptr() for p in P.values()))
-        cache = getattr(self.mod, "_pack_cache", None)
-        if cache is None or cache[0] != key:
-            rows = []  # (src, K, M, K2, s1, s2, sm)
-            names = self._linear_names() + ([] if self.x3 else ["classify.weight"])
-            for n in names:
-                w = P[n]
-                M, K = w.shape
-                rows.append((w, K, M, K, 0, 1, K))
-                if need_dgrad and not n.startswith("encode.layers.0.self_attn.in_proj"):
-                    rows.append((w, M, K, M, 0, K, 1))
-            sizes = [L.pack_frags_bytes(r[1], r[2], dt) * (2 if mode == 2 else 1) for r in rows]
-            offs = [0]
-            for n in sizes:
-                offs.append(offs[-1] + (n + 255) // 256 * 256)
-            buf = torch.empty(offs[-1], dtype=torch.uint8, device=self.dev)
-            table = torch.tensor([[r[0].data_ptr(), buf.data_ptr() + o, mode, r[1], r[2], r[3], r[4], r[5], r[6]] for r, o in zip(rows, offs)],
-                                 dtype=torch.int64).to(self.dev)
-            maxthr = max(((r[1] + 31) // 32) * ((r[2] + 15) // 16) * 64 for r in rows)
-            views = {(r[0].data_ptr(), "f" if r[5] == 1 else "d"): buf[o:o + n] for r, o, n in zip(rows, offs, sizes)}
-            cache = self.mod._pack_cache = (key, table, len(rows), maxthr, dt, buf, views)
-        L.pack_frags_multi(ptr(cache[1]), cache[2], cache[3], cache[4])
-        self.packs = cache[6]
+        """All weight-fragment packs of the step in one launch (packs.py); the table is cached while the parameters stay put."""
+        key = (self.frag, need_dgrad, tuple(p.data_ptr() for p in self.P.values()))
+        self.packs = cached_table(self.mod, key, lambda: self.pack_rows(need_dgrad), self.dev)
+        self.packs.launch()
 
     def linear(self, x, ldx, w, bias, relu=False, ldo=None):
         """out [R][ldo] = x [R][K] @ w[M][K]^T + bias"""
@@ -140,15 +129,15 @@ class _LayoutRun:
         M, K = w.shape
         ldo = ldo or M
         out = self.empty(R, ldo)
+        row = fwd_row(w, *self.frag)
         if self.x3:
-            wpk = self.packs.get((w.data_ptr(), "f"))
+            wpk = self.packs.get(row)
             if wpk is not None and L.gemm_x3p_supported(ldx, K, ldo, M, R):
                 L.gemm_x3p(ptr(x), ldx, K, ptr(wpk), ptr(bias), ptr(out), ldo, M, R)
             else:
                 L.gemm_x3(ptr(x), ldx, K, ptr(w), K, 0, ptr(bias), ptr(out), ldo, M, R, 0)
             return out, False
-        L.conv_igemm(ptr(x), ldx, ptr(self.packs[(w.data_ptr(), "f")]), ptr(out), ldo, ptr(bias), 1 if relu else 0, None, K, M, 1, 1, R, 1, R, 1, 1,
-                     0, 0, 0)
+        L.conv_igemm(ptr(x), ldx, ptr(self.packs[row]), ptr(out), ldo, ptr(bias), 1 if relu else 0, None, K, M, 1, 1, R, 1, R, 1, 1, 0, 0, 0)
         return out, relu
 
     def linear_dgrad(self, g, ldg, w):
@@ -156,14 +145,15 @@ class _LayoutRun:
         L, R = self.L, self.R
         M, K = w.shape
         out = self.empty(R, K)
+        row = dgrad_row(w, *self.frag)
         if self.x3:
-            wpk = self.packs.get((w.data_ptr(), "d"))
+            wpk = self.packs.get(row)
             if wpk is not None and ldg == M and L.gemm_x3p_supported(ldg, M, K, K, R):
                 L.gemm_x3p(ptr(g), ldg, M, ptr(wpk), None, ptr(out), K, K, R)
             else:
                 L.gemm_x3(ptr(g), ldg, ldg, ptr(w), K, 1, None, ptr(out), K, K, R, M if M != ldg else 0)
             return out
-        L.conv_igemm(ptr(g), ldg, ptr(self.packs[(w.data_ptr(), "d")]), ptr(out), K, None, 0, None, ldg, K, 1, 1, R, 1, R, 1, 1, 0, 0, 0)
+        L.conv_igemm(ptr(g), ldg, ptr(self.packs[row]), ptr(out), K, None, 0, None, ldg, K, 1, 1, R, 1, R, 1, 1, 0, 0, 0)
         return out
 
     def wgrad(self, g, ldg, M, x, K, dW):

@@ -13,12 +13,12 @@ There is no CPU path: tensors must be on an MI355X.
 from __future__ import annotations
 
 import math
-from types import MappingProxyType
 
 import torch
 from torch import nn
 
 from ._lib import lib, ptr
+from .packs import EMPTY as EMPTY_PACKS, PackRow, cached_table, dgrad_row, fwd_row
 
 DEPTH_SCALE = [8, 16, 32, 32, 64, 128, 256]  # models.py:112
 _DT = {torch.float32: 0, torch.bfloat16: 1}
@@ -126,7 +126,7 @@ class _DetRun:
     use_mm = use_rs32 = fuse_bn_bwd = fold_fwd_fin = True
     c1_u = c1_noz = c1_fuse = head_gl = True
     # per-pass state, declared here with its value between passes (immutable defaults: a run the op tests assemble field by field reads them too):
-    packs = MappingProxyType({})  # this step's weight-fragment packs (prepack); empty outside a full forward
+    packs = EMPTY_PACKS  # this step's weight-fragment packs (prepack); empty outside a full forward
     _zpool, _zoff = None, 0  # the fp64 accumulator pool (zeros64)
     _flat, _folds, _defer_folds = None, (), False  # the flat gradient buffer of a backward and its deferred fp64 folds (fold64)
     _keep_ws, _deferring = None, False  # inside backward(): the workspaces the deferral window still reads (_hold)
@@ -209,45 +209,34 @@ class _DetRun:
 
     def pack(self, src, mode, K, M, K2, s1, s2, sm):
         """MFMA weight fragments of one layer: from this step's multi-pack buffer (prepack) or, outside a full forward, packed here."""
-        hit = self.packs.get((src.data_ptr(), mode, K, M, s2, sm))
-        if hit is not None:
-            return hit
-        nbytes = self.L.pack_frags_bytes(K, M, self.dt)
-        out = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        self.L.pack_frags(ptr(src), mode, K, M, K2, s1, s2, sm, ptr(out), self.dt)
-        return out
+        return self.packs.fetch(PackRow(src, self.dt, mode, K, M, K2, s1, s2, sm), self.dev)
+
+    def convt_row(self, w):
+        """ConvTranspose2d forward: the effective weight of W[Cup][Cout][3][3] (pack mode 1)"""
+        Cup, Cout = w.shape[0], w.shape[1]
+        return PackRow(w, self.dt, 1, 4 * Cup, 4 * Cout, Cup, 0, 0, 0)
+
+    def convt_dgrad_row(self, w):
+        """ConvTranspose2d input gradient: A[m = cup][k = (tap, cout)] = W[cup][cout][tap]"""
+        Cup, Cout = w.shape[0], w.shape[1]
+        return PackRow(w, self.dt, 0, 9 * Cout, Cup, Cout, 1, 9, 9 * Cout)
+
+    def pack_rows(self):
+        """The packs of a step: 25 forward + 24 backward pointwise, 6 + 6 ConvTranspose."""
+        P, rows = self.P, []
+        for name in self.names:
+            if name.endswith(".seq.1.weight") and P[name].dim() == 4 and P[name].shape[1] > 1:
+                rows += [fwd_row(P[name], self.dt), dgrad_row(P[name], self.dt)]  # W (K = Cin, M = Cout), W^T (K = Cout, M = Cin)
+        for i in range(6):
+            rows += [self.convt_row(P[f"up.{i}.up.weight"]), self.convt_dgrad_row(P[f"up.{i}.up.weight"])]
+        return rows
 
     def prepack(self):
-        """All weight-fragment packs of the step (25 forward + 24 backward pointwise, 6+6 ConvTranspose) in ONE launch.  The table of
-        (source pointer, layout) rows is built once per module / dtype and reused while the parameter storage stays in place."""
-        P, w = self.P, DEPTH_SCALE
-        cache = getattr(self.mod, "_pack_cache", None)
-        key = (self.dt, tuple(p.data_ptr() for p in P.values()))
-        if cache is None or cache[0] != key:
-            rows = []  # (src tensor, mode, K, M, K2, s1, s2, sm)
-            for name in self.names:
-                if name.endswith(".seq.1.weight") and P[name].dim() == 4 and P[name].shape[1] > 1:
-                    cout, cin = P[name].shape[0], P[name].shape[1]
-                    rows.append((P[name], 0, cin, cout, cin, 0, 1, cin))   # forward:  W   (K = Cin,  M = Cout)
-                    rows.append((P[name], 0, cout, cin, cout, 0, cin, 1))  # backward: W^T (K = Cout, M = Cin)
-            for i in range(6):
-                Cup, Cout = w[i + 1], w[i]
-                rows.append((P[f"up.{i}.up.weight"], 1, 4 * Cup, 4 * Cout, Cup, 0, 0, 0))
-                rows.append((P[f"up.{i}.up.weight"], 0, 9 * Cout, Cup, Cout, 1, 9, 9 * Cout))
-            sizes = [self.L.pack_frags_bytes(r[2], r[3], self.dt) for r in rows]
-            offs = [0]
-            for n in sizes:
-                offs.append(offs[-1] + ((n + 255) // 256) * 256)
-            buf = torch.empty(offs[-1], dtype=torch.uint8, device=self.dev)
-            table = torch.tensor([[r[0].data_ptr(), buf.data_ptr() + o, r[1], r[2], r[3], r[4], r[5], r[6], r[7]] for r, o in zip(rows, offs)],
-                                 dtype=torch.int64).to(self.dev)
-            views = {(r[0].data_ptr(), r[1], r[2], r[3], r[6], r[7]): buf[o:o + n] for r, o, n in zip(rows, offs, sizes)}
-            maxthr = max(((r[2] + 31) // 32) * ((r[3] + 15) // 16) * 64 for r in rows)
-            cache = (key, table, buf, views, len(rows), maxthr)
-            self.mod._pack_cache = cache
-        _, table, _, views, n, maxthr = cache
-        self.L.pack_frags_multi(ptr(table), n, maxthr, self.dt)
-        self.packs = views
+        """All weight-fragment packs of the step in ONE launch (packs.py); the table is built once per module / dtype and reused while the
+        parameter storage stays in place."""
+        key = (self.dt, tuple(p.data_ptr() for p in self.P.values()))
+        self.packs = cached_table(self.mod, key, self.pack_rows, self.dev)
+        self.packs.launch()
 
     def bn_tr(self, prefix, gstat, count, C, nparts=0):
         """gstat: fp64 [2][C] accumulated sums, or (nparts > 0) fp32 per-block partials [nparts][C][2] of the matrix-core forward"""
@@ -333,7 +322,7 @@ class _DetRun:
                 L.rs32_fwd(*common, None, 0, None, None, 0.0, 0.0, None, None, None, None, None, 0.0, Cout, N, H, W)
                 tr, saved = self.bn_tr(bnp, gstat, N * H * W, Cout)
         else:
-            wpk = self.pack(wpw, 0, Cin, Cout, Cin, 0, 1, Cin)
+            wpk = self.packs.fetch(fwd_row(wpw, self.dt), self.dev)
             gstat = self.zeros64(2 * Cout)
             if pool and L.dwpw_fwd_pool_supported(Cin, Cout):
                 pooled, gamma = self.empty(N, H // 2, W // 2, Cout), P[f"{bnp}.weight"]
@@ -407,7 +396,7 @@ class _DetRun:
         for i in reversed(range(6)):
             skip = skips[i]
             Cup, Cout = w[i + 1], w[i]
-            wpk = self.pack(P[f"up.{i}.up.weight"], 1, 4 * Cup, 4 * Cout, Cup, 0, 0, 0)
+            wpk = self.packs.fetch(self.convt_row(P[f"up.{i}.up.weight"]), self.dev)
             t = self.empty(N, skip.H, skip.W, Cout)
             up.other_use = True
             # fp32, wide levels: row-streaming over the input grid (csrc/det_rs32.hip)
@@ -458,7 +447,7 @@ class _DetRun:
             return None, None
         a, b = r.a, r.b
         Ca, Cb = a.C, (b.C if b is not None else 0)
-        wpk_d = self.pack(wpw, 0, C, r.Cin, C, 0, r.Cin, 1)
+        wpk_d = self.packs.fetch(dgrad_row(wpw, self.dt), self.dev)
 
         def stat_target(act):
             """(saved, gsum) of the block that produced `act` if this pass may produce its BatchNorm-backward sums."""
@@ -633,7 +622,7 @@ class _DetRun:
             skip_g[i].append(gxb)
             up_in, ta = self.convt[i]
             Cup, Cout = w[i + 1], w[i]
-            wpk_d = self.pack(P[f"up.{i}.up.weight"], 0, 9 * Cout, Cup, Cout, 1, 9, 9 * Cout)
+            wpk_d = self.packs.fetch(self.convt_dgrad_row(P[f"up.{i}.up.weight"]), self.dev)
             dx = self.empty(N, up_in.H, up_in.W, Cup)
             ws = self.empty(L.convt_bwd_ws_floats(Cup, Cout, N, up_in.H, up_in.W, self.dt), dtype=torch.float32)
             self._hold(ws)  # (the fp32 row-streaming weight-gradient kernel queues its second stage until the end of the backward)

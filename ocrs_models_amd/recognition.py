@@ -18,6 +18,7 @@ from torch import nn
 
 from ._lib import lib, ptr
 from .models import _DT, _check_versions, _identity_tr
+from .packs import EMPTY as EMPTY_PACKS, PackRow, cached_table, conv_dgrad_row, conv_row, dgrad_row, fwd_row
 
 _coef_cache: dict = {}
 
@@ -32,26 +33,41 @@ def _unit_coef(C, device):
     return t
 
 
+class _GruRec:
+    """What a GRU layer's backward needs from its forward (both directions stacked; x: the layer's input [T][N][I])."""
+
+    __slots__ = ("layer", "x", "I", "w_ih", "w_hh", "out", "saved")
+
+    def __init__(self, layer, x, I, w_ih, w_hh, out, saved):
+        self.layer, self.x, self.I, self.w_ih, self.w_hh, self.out, self.saved = layer, x, I, w_ih, w_hh, out, saved
+
+
 class _RecRun:
-    def __init__(self, mod, x, names, params, train, dtype):
+    """One forward (and later backward) pass of the recognition network on the current stream."""
+
+    # per-pass state, declared here with its value between passes (immutable defaults: a run the op tests drive stage by stage reads them too):
+    packs = EMPTY_PACKS  # this step's weight-fragment packs (prepack); empty outside a full forward
+    _arena, _arena_off = None, 0  # the fp64 accumulator arena (stat)
+    _side, _keep = None, ()  # inside backward(): the side stream (None: single stream) and the tensors its launches still read (on_side)
+    G = None  # inside backward(): gradient views by parameter name
+
+    def __init__(self, P, Bf, dev, dtype, N, H, W, train=True, mod=None, x=None):
+        """P / Bf: parameters / buffers by state-dict name (P in the module's parameter order); mod / x: the module and the input crops of a
+        whole-network pass (forward / backward need them; the op tests drive single stages without)."""
         self.L = lib()
-        self.mod = mod
-        self.P = dict(zip(names, params))
-        self.names = names
-        self.Bf = dict(mod.named_buffers())
-        self.train = train
-        self.dev = x.device
-        self.dtype = dtype
-        self.dt = _DT[self.dtype]
+        self.P, self.Bf, self.names = P, Bf, list(P)
+        self.dev, self.dtype, self.dt, self.N, self.H, self.W, self.train = dev, dtype, _DT[dtype], N, H, W, train
+        self.mod, self.x = mod, x
         # split-bf16 GEMMs for the fp32 GRU weight gradients in throughput mode, the projections on the pipelined kernel (rec_gemm.hip)
         self.x3 = os.environ.get("OCRS_GRU_X3", "1") != "0"
         # recurrence as one persistent launch per layer and pass (csrc/rec_gru_seq.hip) when all its workgroups can be resident; its matrix
         # products follow the projection GEMMs' arithmetic: exact fp32 MFMA in parity mode, split-bf16 x3 in throughput mode
-        self.gru_seq = bool(self.L.gru_seq_supported(x.shape[0])) and not _GRU_SEQ_OFF.get(x.device, False)
+        self.gru_seq = bool(self.L.gru_seq_supported(N)) and not _GRU_SEQ_OFF.get(dev, False)
         self.gru_exact = 0 if self.dt == 1 and self.x3 else 1
-        self.x = x
-        self.N, _, self.H, self.W = x.shape
-        self.ncls = self.P["output.0.weight"].shape[0]
+
+    @property
+    def ncls(self):
+        return self.P["output.0.weight"].shape[0]
 
     # ---- helpers -------------------------------------------------------------------------------
     def empty(self, *shape, dtype=None):
@@ -66,83 +82,62 @@ class _RecRun:
     def stat(self, C):
         """zeroed fp64 [2][C] accumulator (BatchNorm batch sums / their backward counterparts): a slice of ONE zero-filled arena per step"""
         n = 2 * C
-        arena = getattr(self, "_arena", None)
-        if arena is None or self._arena_off + n > arena.numel():
-            arena = self._arena = torch.zeros(2 * 2 * (64 + 3 * 128), dtype=torch.float64, device=self.dev)
+        if self._arena is None or self._arena_off + n > self._arena.numel():
+            self._arena = torch.zeros(2 * 2 * (64 + 3 * 128), dtype=torch.float64, device=self.dev)
             self._arena_off = 0
         self._arena_off += n
-        return arena[self._arena_off - n:self._arena_off]
+        return self._arena[self._arena_off - n:self._arena_off]
 
-    def pack(self, src, K, M, K2, s1, s2, sm, dt=None, offset=0):
-        dt = self.dt if dt is None else dt
-        hit = getattr(self, "packs", {}).get((src.data_ptr() + 4 * offset, dt, K, M, s1, s2, sm))
-        if hit is not None:
-            return hit
-        out = torch.empty(self.L.pack_frags_bytes(K, M, dt), dtype=torch.uint8, device=self.dev)
-        self.L.pack_frags(src.data_ptr() + 4 * offset, 0, K, M, K2, s1, s2, sm, ptr(out), dt)
+    def on_side(self, fn, *keep):
+        """fn() on the backward's side stream, behind what the caller's stream holds so far; `keep` (fn's operands) and the workspace fn may
+        return stay referenced until the caller's stream has waited for the side stream.  Single stream: just fn()."""
+        if self._side is None:
+            return fn()
+        self._side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self._side):
+            out = fn()
+        self._keep.extend(keep if out is None else (*keep, out))
         return out
 
-    def pack_conv(self, w):  # W[cout][cin][kh][kw] -> A[m=cout][k=(tap,cin)]
-        co, ci, kh, kw = w.shape
-        return self.pack(w, kh * kw * ci, co, ci, 1, kh * kw, ci * kh * kw)
-
-    def pack_conv_dgrad(self, w):  # A[m=cin][k=(tap',cout)] = W[cout][cin][ntaps-1-tap']
-        co, ci, kh, kw = w.shape
-        nt = kh * kw
-        return self.pack(w, nt * co, ci, co, -1, ci * nt, nt, offset=nt - 1)
+    def pack(self, src, K, M, K2, s1, s2, sm, dt=None, offset=0):
+        """MFMA weight fragments of one layout: from this step's multi-pack buffer (prepack) or, when the table does not hold it, packed here."""
+        return self.packs.fetch(PackRow(src, self.dt if dt is None else dt, 0, K, M, K2, s1, s2, sm, offset), self.dev)
 
     _CONVS = ("conv.3.weight", "conv.7.weight", "conv.9.weight", "conv.13.weight", "conv.15.weight", "conv.19.weight")
 
+    def pack_rows(self):
+        """The packs of a step: the conv layers (forward + input-gradient layouts) in the activation dtype, and the Linear layers of the mode."""
+        P, rows = self.P, []
+        for name in self._CONVS:
+            rows.append(conv_row(P[name], self.dt))
+            if self.train:
+                rows.append(conv_dgrad_row(P[name], self.dt))
+        wout = P["output.0.weight"]
+        if not self.use_x3(512, self.ncls, 0):
+            # parity mode: the output layer in both layouts, exact fp32 (the GRU projection weights are NOT here: linear() packs them with
+            # one ocrs_pack_frags each per step)
+            rows.append(fwd_row(wout, 0))
+            if self.train:
+                rows.append(dgrad_row(wout, 0))
+        else:
+            # throughput mode, pipelined split-bf16 GEMM (csrc/rec_gemm.hip): the GRU input-projection weights pre-split into hi / lo bf16
+            # fragment planes (pack mode 2), forward and -- training -- input-gradient layouts; the output layer's input gradient likewise
+            # (its forward has a ragged M = n_classes and stays on k_gemm_x3, straight from the master layout)
+            for layer in (0, 1):
+                w_ih = RecognitionModel._gru_stacked(layer, P)[0]
+                rows.append(fwd_row(w_ih, 1, 2))
+                if self.train:
+                    rows.append(dgrad_row(w_ih, 1, 2))
+            if self.train:
+                rows.append(dgrad_row(wout, 1, 2))
+        return rows
+
     def prepack(self):
-        """All weight-fragment packs of the step in one launch per dtype (conv layers: forward + input-gradient layouts; the output Linear: both
-        layouts, fp32).  The table of (source pointer, layout) rows is built once per module / dtype and reused while the parameter storage
-        stays in place (same scheme as models.py::_Run.prepack)."""
-        P = self.P
-        cache = getattr(self.mod, "_pack_cache", None)
-        key = (self.dt, self.train, self.x3, tuple(p.data_ptr() for p in P.values()))
-        if cache is None or cache[0] != key:
-            rows = []  # (src tensor, dtype code, K, M, K2, s1, s2, sm, element offset)
-            for name in self._CONVS:
-                co, ci, kh, kw = P[name].shape
-                nt = kh * kw
-                rows.append((P[name], self.dt, nt * ci, co, ci, 1, nt, ci * nt, 0))
-                if self.train:
-                    rows.append((P[name], self.dt, nt * co, ci, co, -1, ci * nt, nt, nt - 1))
-            C = self.ncls
-            if not self.use_x3(512, C, 0):  # (throughput mode: the output layer runs on the split-bf16 GEMM, straight from the master layout)
-                rows.append((P["output.0.weight"], 0, 512, C, 512, 0, 1, 512, 0))
-                if self.train:
-                    rows.append((P["output.0.weight"], 0, C, 512, C, 0, 512, 1, 0))
-            else:
-                # throughput mode, pipelined split-bf16 GEMM (csrc/rec_gemm.hip): the GRU input-projection weights pre-split into hi / lo bf16
-                # fragment planes (pack mode 2), forward A[m][k] = W_ih[m][k] and -- training -- input-gradient A[m][k] = W_ih[k][m] layouts;
-                # the output layer's input gradient likewise (its forward has a ragged M = n_classes and stays on k_gemm_x3)
-                for layer, I in ((0, 128), (1, 512)):
-                    w_ih = self.mod._gru_stacked(layer, P)[0]
-                    rows.append((w_ih, 1, I, 1536, I, 0, 1, I, 0, 2))
-                    if self.train:
-                        rows.append((w_ih, 1, 1536, I, 1536, 0, I, 1, 0, 2))
-                if self.train:
-                    rows.append((P["output.0.weight"], 1, C, 512, C, 0, 512, 1, 0, 2))
-            rows = [r if len(r) == 10 else r + (0,) for r in rows]  # (last field: pack mode)
-            sizes = [self.L.pack_frags_bytes(r[2], r[3], r[1]) * (2 if r[9] == 2 else 1) for r in rows]
-            offs = [0]
-            for n in sizes:
-                offs.append(offs[-1] + ((n + 255) // 256) * 256)
-            buf = torch.empty(offs[-1], dtype=torch.uint8, device=self.dev)
-            views, tables = {}, []
-            for dt in sorted({r[1] for r in rows}):
-                sel = [(r, o) for r, o in zip(rows, offs) if r[1] == dt]
-                table = torch.tensor([[r[0].data_ptr() + 4 * r[8], buf.data_ptr() + o, r[9], r[2], r[3], r[4], r[5], r[6], r[7]] for r, o in sel],
-                                     dtype=torch.int64).to(self.dev)
-                tables.append((table, len(sel), max(((r[2] + 31) // 32) * ((r[3] + 15) // 16) * 64 for r, _ in sel), dt))
-            for r, o, n in zip(rows, offs, sizes):
-                views[(r[0].data_ptr() + 4 * r[8], r[1], r[2], r[3], r[5], r[6], r[7]) + ((r[9],) if r[9] else ())] = buf[o:o + n]
-            cache = (key, tables, buf, views)
-            self.mod._pack_cache = cache
-        for table, n, maxthr, dt in cache[1]:
-            self.L.pack_frags_multi(ptr(table), n, maxthr, dt)
-        self.packs = cache[3]
+        """All weight-fragment packs of the step in one launch per fragment dtype (packs.py); the table is built once per module / mode and
+        reused while the parameter storage stays in place."""
+        key = (self.dt, self.train, self.x3, tuple(p.data_ptr() for p in self.P.values()))
+        self.packs = cached_table(self.mod, key, self.pack_rows, self.dev)
+        self.packs.launch()
 
     def bn(self, prefix, gstat, count, C, lo):
         P, Bf = self.P, self.Bf
@@ -163,22 +158,10 @@ class _RecRun:
         Ho, Wo = Ho or Hi, Wo or Wi
         out = self.empty(self.N, Ho, Wo, co)
         gstat = self.stat(co) if stats else None
-        self.L.conv_igemm(ptr(x), ci, ptr(self.pack_conv(w)), ptr(out), co, ptr(bias), 1 if relu else 0, ptr(gstat), ci, co, self.N, Hi, Wi, Ho, Wo,
-                          kh, kw, pad, pad, self.dt)
+        wpk = self.packs.fetch(conv_row(w, self.dt), self.dev)
+        self.L.conv_igemm(ptr(x), ci, ptr(wpk), ptr(out), co, ptr(bias), 1 if relu else 0, ptr(gstat), ci, co, self.N, Hi, Wi, Ho, Wo, kh, kw, pad, pad,
+                          self.dt)
         return out, gstat
-
-    def gemm_x3(self, x, ldx, K, w, ldw, km, bias, M, ldo, rows, kw=0):
-        """Throughput-mode fp32 GEMM as split-bf16 (see csrc/rec_conv.hip::k_gemm_x3): W straight from the master layout."""
-        out = self.empty(rows, ldo, dtype=torch.float32)
-        if M % 128 == 0:
-            # pre-split weights of this step's prepack (mode 2): A[m][k] = W[m][k] (km = 0: s2 = 1, sm = ldw) or W[k][m] (km = 1: s2 = ldw, sm = 1)
-            Kw = kw or K
-            wpk = self.packs.get((w.data_ptr(), 1, Kw, M, 0, ldw if km else 1, 1 if km else ldw, 2))
-            if wpk is not None and self.L.gemm_x3p_supported(ldx, K, ldo, M, rows):
-                self.L.gemm_x3p(ptr(x), ldx, K, ptr(wpk), ptr(bias), ptr(out), ldo, M, rows)
-                return out
-        self.L.gemm_x3(ptr(x), ldx, K, ptr(w), ldw, km, ptr(bias), ptr(out), ldo, M, rows, kw)
-        return out
 
     def use_x3(self, K, M, km=1):
         return self.dt == 1 and self.x3 and K % 32 == 0 and (M % 4 == 0 or not km)
@@ -187,6 +170,24 @@ class _RecRun:
         """fp32 GEMM: out[rows][ldo] = x[rows][K] @ W^T (+bias), W given as packed fragments (K, M)."""
         out = self.empty(rows, ldo, dtype=torch.float32)
         self.L.conv_igemm(ptr(x), ldx, ptr(wpk), ptr(out), ldo, ptr(bias), 0, None, K, M, 1, 1, rows, 1, rows, 1, 1, 0, 0, 0)
+        return out
+
+    def linear(self, x, ldx, K, w, ldw, km, bias, M, ldo, rows, kw=0):
+        """fp32 out[rows][ldo] = x[rows][K] @ A^T (+ bias) with A[m][k] = w[m][k] (km = 0) or w[k][m] (km = 1), w's row pitch ldw; kw (0: K):
+        the k extent w really has -- x's columns [kw, K) are zero.  w is the whole matrix: its shape says the same as (M, kw or K, ldw).  The one place that picks the kernel: throughput mode runs split-bf16
+        (csrc/rec_conv.hip::k_gemm_x3), on the pipelined kernel where this step's prepack pre-split the weight and the shape is taken, else
+        straight from the master layout; parity mode runs exact fp32 on packed fragments."""
+        L = self.L
+        assert (M, kw or K, ldw) == ((w.shape[1], w.shape[0]) if km else tuple(w.shape)) + (w.shape[1],)  # (the packed routes read w.shape)
+        row_of = dgrad_row if km else fwd_row
+        if not self.use_x3(K, M, km):
+            return self.gemm(x, ldx, K, self.packs.fetch(row_of(w, 0), self.dev), bias, M, ldo, rows)
+        out = self.empty(rows, ldo, dtype=torch.float32)
+        wpk = self.packs.get(row_of(w, 1, 2))
+        if wpk is not None and L.gemm_x3p_supported(ldx, K, ldo, M, rows):
+            L.gemm_x3p(ptr(x), ldx, K, ptr(wpk), ptr(bias), ptr(out), ldo, M, rows)
+        else:
+            L.gemm_x3(ptr(x), ldx, K, ptr(w), ldw, km, ptr(bias), ptr(out), ldo, M, rows, kw)
         return out
 
     # ---- forward -------------------------------------------------------------------------------
@@ -228,11 +229,8 @@ class _RecRun:
         S.gru = []
         xin, I = S.seq, 128
         for layer in (0, 1):
-            w_ih, w_hh, b_ih, b_hh = self.mod._gru_stacked(layer, P)  # (1536, I), (2, 768, 256), (1536,), (1536,): both directions
-            if self.use_x3(I, 1536):
-                gi = self.gemm_x3(xin, I, I, w_ih, I, 0, b_ih, 1536, 1536, rows)  # W_ih [1536][I]
-            else:
-                gi = self.gemm(xin, I, I, self.pack(w_ih, I, 1536, I, 0, 1, I, dt=0), b_ih, 1536, 1536, rows)
+            w_ih, w_hh, b_ih, b_hh = RecognitionModel._gru_stacked(layer, P)  # (1536, I), (2, 768, 256), (1536,), (1536,): both directions
+            gi = self.linear(xin, I, I, w_ih, I, 0, b_ih, 1536, 1536, rows)  # W_ih [1536][I]
             out = self.empty(T, N, 512, dtype=torch.float32)
             saved = self.empty(T, N, 2, 4, 256, dtype=torch.float32) if self.train else None
             if self.gru_seq:
@@ -244,16 +242,12 @@ class _RecRun:
                 for d in (0, 1):
                     L.pack_frags(w_hh.data_ptr() + 4 * d * 768 * 256, 0, 256, 768, 256, 0, 1, 256, whh_pk.data_ptr() + 4 * d * nfl, 0)
                 L.gru_layer_fwd(ptr(gi), ptr(whh_pk), ptr(b_hh), ptr(out), ptr(saved), T, N)
-            S.gru.append({"x": xin, "I": I, "w_ih": w_ih, "w_hh": w_hh, "out": out, "saved": saved})
+            S.gru.append(_GruRec(layer, xin, I, w_ih, w_hh, out, saved))
             xin, I = out, 512
         # ---- Linear + LogSoftmax (fp32) ----
         C = self.ncls
         S.ldl = (C + 31) // 32 * 32
-        wout = P["output.0.weight"]
-        if self.use_x3(512, C, 0):
-            logits = self.gemm_x3(xin, 512, 512, wout, 512, 0, P["output.0.bias"], C, S.ldl, rows)
-        else:
-            logits = self.gemm(xin, 512, 512, self.pack(wout, 512, C, 512, 0, 1, 512, dt=0), P["output.0.bias"], C, S.ldl, rows)
+        logits = self.linear(xin, 512, 512, P["output.0.weight"], 512, 0, P["output.0.bias"], C, S.ldl, rows)
         S.lp = self.empty(T, N, C, dtype=torch.float32)
         L.log_softmax_fwd(ptr(logits), ptr(S.lp), rows, C, S.ldl, 0)
         return S.lp
@@ -271,22 +265,16 @@ class _RecRun:
                 return ws
             self.wgrad(dz, co, co, xin, ci, ci, self.G[name], self.N, Hz, Wz, Hx, Wx, pad, pad, kh, kw, self.dt)
             return None
-        side = getattr(self, "_side", None)
-        if side is not None and need_dx:
-            # The weight gradient hangs off dz and nothing downstream in the backward reads it: it runs on a side stream next to the dgrad and the
-            # HBM-bound BatchNorm / pooling backward kernels of the next layer (matrix-core work next to streaming work).  Its operands stay
-            # referenced until the main stream has waited for the side stream (end of the backward, or the DDP stage report).
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                ws = wgrad_now()
-            self._keep.extend((dz, xin, ws))
-        else:
-            wgrad_now()
         if not need_dx:
+            wgrad_now()
             return None
+        # The weight gradient hangs off dz and nothing downstream in the backward reads it: it runs on the side stream next to the dgrad and the
+        # HBM-bound BatchNorm / pooling backward kernels of the next layer (matrix-core work next to streaming work).  Its operands and workspace
+        # stay referenced until the main stream has waited for the side stream (end of the backward, or the DDP stage report).
+        self.on_side(wgrad_now, dz, xin)
         dx = self.empty(self.N, Hx, Wx, ci)
-        L.conv_igemm(ptr(dz), co, ptr(self.pack_conv_dgrad(w)), ptr(dx), ci, None, 0, None, co, ci, self.N, Hz, Wz, Hx, Wx, kh, kw, kh - 1 - pad,
-                     kw - 1 - pad, self.dt)
+        L.conv_igemm(ptr(dz), co, ptr(self.packs.fetch(conv_dgrad_row(w, self.dt), self.dev)), ptr(dx), ci, None, 0, None, co, ci, self.N, Hz, Wz, Hx, Wx, kh, kw,
+                     kh - 1 - pad, kw - 1 - pad, self.dt)
         return dx
 
     def wgrad(self, A, ldA, CA, B, ldB, CB, dW, N, hA, wA, HB, WB, padh, padw, KH, KW, dt):
@@ -311,6 +299,15 @@ class _RecRun:
             return
         ws = self.empty(L.wgrad_gather_ws_floats(CA, CB, KH * KW, N * hA * wA, dt), dtype=torch.float32)
         L.wgrad_gather(a_ptr, ldA, CA, None, b_ptr, ldB, CB, ptr(dW), ptr(ws), N, hA, wA, HB, WB, 1, padh, padw, KH, KW, dt)
+
+    def gru_wgrads(self, gl, dgi, dgh):
+        """dW_ih += dgi^T x and, per direction, dW_hh += dgh^T h_{t -+ 1} of GRU layer gl (both directions' W_ih gradients are one stacked view:
+        adjacent in the flat buffer, see `order` in _backward)"""
+        T, N, G = self.T, self.N, self.G
+        self.wgrad(dgi, 1536, 1536, gl.x, gl.I, gl.I, G[f"gru.weight_ih_l{gl.layer}"], 1, 1, T * N, 1, T * N, 0, 0, 1, 1, 0)
+        for d, sfx in enumerate((f"_l{gl.layer}", f"_l{gl.layer}_reverse")):
+            self.wgrad(dgh.data_ptr() + 4 * d * 768, 1536, 768, gl.out.data_ptr() + 4 * d * 256, 512, 256, G["gru.weight_hh" + sfx], 1, T, N, T, N,
+                       1 if d == 0 else -1, 0, 1, 1, 0)
 
     def bn_pool_bwd(self, prefix, g, z, tr, saved, C, H, W, PH, PW):
         L = self.L
@@ -358,8 +355,7 @@ class _RecRun:
         done = [0]
 
         main = torch.cuda.current_stream()
-        self._side = _rec_side_stream(self.dev) if _REC_OVERLAP else None
-        self._keep = []
+        self._side, self._keep = (_rec_side_stream(self.dev) if _REC_OVERLAP else None), []
         # Deferred second stage (ocrs_bwd_defer_begin / _flush, round 5): the launches that used to end in cross-block float atomics (bias column sums,
         # the first layer's weight gradient, the GRU bias sums) write per-block partials into the library's workspace and queue a fixed-order column
         # sum; ONE launch at the end of the backward runs them all -- the step's gradients are bit-reproducible.  Not with a gradient bucketer (a
@@ -383,62 +379,45 @@ class _RecRun:
         g_lp = g_lp.contiguous().float()
         dlog = self.empty(rows, S.ldl, dtype=torch.float32)
         L.log_softmax_bwd(ptr(S.lp), ptr(g_lp), ptr(dlog), rows, C, S.ldl, 0)
-        top = S.gru[1]["out"]
+        top = S.gru[1].out
         self.wgrad(dlog, S.ldl, C, top, 512, 512, G["output.0.weight"], 1, 1, rows, 1, rows, 0, 0, 1, 1, 0)
         L.col_sum(ptr(dlog), S.ldl, C, ptr(G["output.0.bias"]), rows, 0)
-        if self.use_x3(S.ldl, 512):  # dlog's columns [C, ldl) are zero and meet no weights (kw = C)
-            dout = self.gemm_x3(dlog, S.ldl, S.ldl, P["output.0.weight"], 512, 1, None, 512, 512, rows, kw=C)
-        else:
-            dout = self.gemm(dlog, S.ldl, S.ldl, self.pack(P["output.0.weight"], C, 512, C, 0, 512, 1, dt=0), None, 512, 512, rows)
+        dout = self.linear(dlog, S.ldl, S.ldl, P["output.0.weight"], 512, 1, None, 512, 512, rows, kw=C)  # dlog's columns [C, ldl) are zero
         stage_done("output.")
         dhz = self.empty(2, 2, N, 256, dtype=torch.float32)
-        deferred_l1 = None
+        held = []
         for layer in (1, 0):
             gl = S.gru[layer]
-            I = gl["I"]
+            I = gl.I
             dgi = self.empty(rows, 1536, dtype=torch.float32)
             dgh = self.empty(rows, 1536, dtype=torch.float32)
             if self.gru_seq:
                 sync, xws = self.seq_sync()
-                L.gru_seq_bwd(ptr(dout), ptr(gl["saved"]), ptr(gl["out"]), ptr(gl["w_hh"]), ptr(dgi), ptr(dgh), T, N, ptr(sync),
+                L.gru_seq_bwd(ptr(dout), ptr(gl.saved), ptr(gl.out), ptr(gl.w_hh), ptr(dgi), ptr(dgh), T, N, ptr(sync),
                               ptr(_gru_err(self.dev)), ptr(xws), self.gru_exact, ptr(G[f"gru.bias_ih_l{layer}"]), ptr(G[f"gru.bias_hh_l{layer}"]))
             else:
                 nfl = 24 * 16 * 64 * 8
                 whhT = torch.empty(2 * nfl, dtype=torch.float32, device=self.dev)
                 for d in (0, 1):
-                    L.pack_frags(gl["w_hh"].data_ptr() + 4 * d * 768 * 256, 0, 768, 256, 768, 0, 256, 1, whhT.data_ptr() + 4 * d * nfl, 0)
-                L.gru_layer_bwd(ptr(dout), ptr(gl["saved"]), ptr(gl["out"]), ptr(whhT), ptr(dgi), ptr(dgh), ptr(dhz), T, N)
-            sfx = [f"_l{layer}", f"_l{layer}_reverse"]
-            # stacked views: [w_ih, w_ih_reverse] etc. are adjacent in the flat buffer (see `order`)
-            gw_ih = G["gru.weight_ih" + sfx[0]]
-
-            def gru_wgrads(dgi=dgi, dgh=dgh, gl=gl, I=I, gw_ih=gw_ih, sfx=sfx):  # (bound now: layer 1's call may run during layer 0's iteration)
-                self.wgrad(dgi, 1536, 1536, gl["x"], I, I, gw_ih, 1, 1, rows, 1, rows, 0, 0, 1, 1, 0)
-                for d in (0, 1):
-                    self.wgrad(dgh.data_ptr() + 4 * d * 768, 1536, 768, gl["out"].data_ptr() + 4 * d * 256, 512, 256, G["gru.weight_hh" + sfx[d]], 1,
-                               T, N, T, N, 1 if d == 0 else -1, 0, 1, 1, 0)
-            if self._side is not None and layer == 1 and bucketer is None:
-                # layer 1's weight gradients must not run under layer 0's persistent recurrence (its hand-offs suffer from streaming neighbours:
-                # measured slower in round 2): they are queued on the side stream BEHIND that recurrence, together with layer 0's
-                deferred_l1 = gru_wgrads
-                self._keep.extend((dgi, dgh, gl["x"], gl["out"]))
-            elif layer == 0 and self._side is not None:
-                # layer 0's weight gradients next to the conv backward that follows
-                self._side.wait_stream(main)
-                with torch.cuda.stream(self._side):
-                    if deferred_l1 is not None:
-                        deferred_l1()
-                    gru_wgrads()
-                self._keep.extend((dgi, dgh, gl["x"], gl["out"]))
+                    L.pack_frags(gl.w_hh.data_ptr() + 4 * d * 768 * 256, 0, 768, 256, 768, 0, 256, 1, whhT.data_ptr() + 4 * d * nfl, 0)
+                L.gru_layer_bwd(ptr(dout), ptr(gl.saved), ptr(gl.out), ptr(whhT), ptr(dgi), ptr(dgh), ptr(dhz), T, N)
+            # The weight gradients.  With a side stream, layer 0's run there next to the conv backward that follows.  Layer 1's must not run under
+            # layer 0's persistent recurrence (its hand-offs suffer from streaming neighbours: measured slower): they are queued on the side
+            # stream BEHIND that recurrence, together with layer 0's -- except with a bucketer, which reports layer 1's stage before layer 0 runs.
+            if layer == 1 and self._side is not None and bucketer is None:
+                held.append((gl, dgi, dgh))
+                self._keep.extend((dgi, dgh, gl.x, gl.out))
+            elif layer == 1:
+                self.gru_wgrads(gl, dgi, dgh)
             else:
-                gru_wgrads()
+                def wgrads_now():
+                    for args in held + [(gl, dgi, dgh)]:
+                        self.gru_wgrads(*args)
+                self.on_side(wgrads_now, dgi, dgh, gl.x, gl.out)
             if not self.gru_seq:  # (the persistent launch accumulates the bias gradients itself)
-                L.col_sum(ptr(dgi), 1536, 1536, ptr(G["gru.bias_ih" + sfx[0]]), rows, 0)
-                L.col_sum(ptr(dgh), 1536, 1536, ptr(G["gru.bias_hh" + sfx[0]]), rows, 0)
-            if self.use_x3(1536, I):
-                dout = self.gemm_x3(dgi, 1536, 1536, gl["w_ih"], I, 1, None, I, I, rows)  # dx = dgi W_ih: W(m, k) = W_ih[k][m]
-            else:
-                dout = self.gemm(dgi, 1536, 1536, self.pack(gl["w_ih"], 1536, I, 1536, 0, I, 1, dt=0), None, I, I, rows)
+                L.col_sum(ptr(dgi), 1536, 1536, ptr(G[f"gru.bias_ih_l{layer}"]), rows, 0)
+                L.col_sum(ptr(dgh), 1536, 1536, ptr(G[f"gru.bias_hh_l{layer}"]), rows, 0)
+            dout = self.linear(dgi, 1536, 1536, gl.w_ih, I, 1, None, I, I, rows)  # dx = dgi W_ih: W(m, k) = W_ih[k][m]
             stage_done(f"gru.bias_hh_l{layer}")
         dseq = dout  # [T][N][128] fp32
         # ---- conv.20 (BN, no ReLU) + AvgPool ----
@@ -468,7 +447,7 @@ class _RecRun:
         L.conv0_bwd(ptr(self.x), ptr(P["conv.0.weight"]), ptr(P["conv.0.bias"]), ptr(g0), ptr(G["conv.0.weight"]), ptr(G["conv.0.bias"]), N, self.H,
                     W, self.dt)
         join_side()
-        self._side = None
+        self._side, self._keep = None, ()
         if deferring:
             L.bwd_defer_flush()  # (behind the join: partials written on the side stream are complete in main-stream order)
         stage_done("conv.0.")
@@ -528,11 +507,15 @@ def _gru_err_poll(dev):
         ent[1].copy_(ent[0], non_blocking=True)
 
 
+def _new_run(mod, x, names, params, dtype):
+    P = dict(zip(names, (p.detach() for p in params)))
+    return _RecRun(P, dict(mod.named_buffers()), x.device, dtype, x.shape[0], x.shape[2], x.shape[3], mod.training, mod, x)
+
+
 class _RecFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, names, dtype, *params):
-        run = _RecRun(mod, x, names, [p.detach() for p in params], mod.training, dtype)
-        ctx.run = run
+        run = ctx.run = _new_run(mod, x, names, params, dtype)
         ctx.params = params
         ctx.versions = [p._version for p in params]
         out = run.forward()
@@ -630,13 +613,13 @@ class RecognitionModel(nn.Module):
         with torch.autocast("cuda", enabled=False):
             if torch.is_grad_enabled() and any(p.requires_grad for p in params):
                 return _RecFn.apply(x, self, names, dtype, *params)
-            run = _RecRun(self, x, names, [p.detach() for p in params], self.training, dtype)
+            run = _new_run(self, x, names, params, dtype)
             out = run.forward()
             if run.gru_seq and not self._gru_seq_ok(run):
                 # inference / validation: a timed-out persistent launch left `out` incomplete -- one synchronous check per call is cheap here;
                 # repeat this forward on the per-step kernels instead of returning wrong log-probabilities
                 _gru_err_reset(x.device)
-                out = _RecRun(self, x, names, [p.detach() for p in params], self.training, dtype).forward()
+                out = _new_run(self, x, names, params, dtype).forward()
             return out
 
     @staticmethod

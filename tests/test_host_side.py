@@ -251,3 +251,70 @@ def test_gru_direction_pairs_are_rehomed_once_and_keep_the_state_dict():
     m._gru_flatten()
     m._gru_stacked(0, {n: p.detach() for n, p in m.named_parameters()})
     assert all(torch.equal(v, before[k]) for k, v in m.state_dict().items())
+
+
+def test_pack_table_layout_lookup_and_cache():
+    """ocrs_models_amd/packs.py on the CPU (fragment sizes injected): buffer layout, the per-dtype int64 tables ocrs_pack_frags_multi reads,
+    lookups by row, and the module-level cache."""
+    from ocrs_models_amd.packs import PackRow, PackTable, cached_table, conv_dgrad_row, dgrad_row, fwd_row
+
+    def frag_bytes(K, M, dt):
+        return K * M * 2
+
+    w, v, c = torch.zeros(24, 40), torch.zeros(7, 33), torch.zeros(5, 3, 2, 2)
+    rows = [fwd_row(w, 1), dgrad_row(w, 1),   # two layouts of one tensor
+            conv_dgrad_row(c, 0),             # a non-zero offset (the last tap)
+            fwd_row(v, 1, 2),                 # pre-split planes: twice the bytes
+            fwd_row(v, 0), PackRow(w, 0, 1, 8, 16, 2, 0, 0, 0)]
+    assert rows[2].offset == 3 and rows[2][1:] == (0, 0, 4 * 5, 3, 5, -1, 3 * 4, 4, 3)
+    t = PackTable(rows, "cpu", frag_bytes)
+    base = t.buf.data_ptr()
+    views = [t.get(r) for r in rows]
+    sizes = [frag_bytes(r.K, r.M, r.dt) * (2 if r.mode == 2 else 1) for r in rows]
+    offs = [x.data_ptr() - base for x in views]
+    assert [x.numel() for x in views] == sizes and views[3].numel() == 2 * frag_bytes(33, 7, 1)
+    assert all(o % 256 == 0 for o in offs) and offs[0] == 0
+    assert all(offs[i] + sizes[i] <= offs[i + 1] < offs[i] + sizes[i] + 256 for i in range(len(rows) - 1))  # ascending, disjoint, packed tight
+    assert offs[-1] + sizes[-1] <= t.buf.numel()
+    assert [dt for _, _, _, dt in t.tables] == [0, 1]
+    for table, n, max_frag_threads, dt in t.tables:
+        sel = [(r, o) for r, o in zip(rows, offs) if r.dt == dt]
+        assert n == len(sel) and table.dtype == torch.int64
+        assert table.tolist() == [[r.src.data_ptr() + 4 * r.offset, base + o, r.mode, r.K, r.M, r.K2, r.s1, r.s2, r.sm] for r, o in sel]
+        assert max_frag_threads == max(-(-r.K // 32) * -(-r.M // 16) * 64 for r, _ in sel)
+    # a row that differs in any one field is another pack
+    r0 = rows[2]
+    for i in range(1, len(r0)):
+        other = r0._replace(**{r0._fields[i]: r0[i] + 1})
+        assert t.get(other) is None, r0._fields[i]
+    assert t.get(r0._replace(src=torch.zeros(60))) is None
+    with pytest.raises(KeyError):
+        t[rows[0]._replace(mode=2)]
+    assert t[rows[0]].data_ptr() == views[0].data_ptr()
+
+    class Mod:
+        pass
+
+    mod, built = Mod(), []
+
+    def build_rows():
+        built.append(1)
+        return rows
+
+    key = (1, tuple(x.data_ptr() for x in (w, v, c)))
+    a = cached_table(mod, key, build_rows, "cpu", frag_bytes)
+    assert cached_table(mod, key, build_rows, "cpu", frag_bytes) is a and built == [1]
+    moved = (1, tuple(x.data_ptr() for x in (w, v.clone(), c)))
+    b = cached_table(mod, moved, build_rows, "cpu", frag_bytes)
+    assert b is not a and built == [1, 1] and cached_table(mod, moved, build_rows, "cpu", frag_bytes) is b
+    # a module that carries a cached table still deep-copies and pickles (EMA / averaged copies, torch.save of a model after a forward)
+    import copy
+    import pickle
+
+    lin = torch.nn.Linear(40, 24)
+    row = fwd_row(lin.weight.detach(), 0)
+    t = cached_table(lin, (0, lin.weight.data_ptr()), lambda: [row], "cpu", frag_bytes)
+    for clone in (copy.deepcopy(lin), pickle.loads(pickle.dumps(lin))):
+        assert torch.equal(clone.weight, lin.weight)
+        key, tc = clone._pack_cache
+        assert key == (0, lin.weight.data_ptr()) and tc is not t and tc.get(row).numel() == t.get(row).numel()

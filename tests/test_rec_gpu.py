@@ -29,12 +29,10 @@ TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2}
 
 
 def _run(dev, dtype, N, H=64, W=64):
-    from ocrs_models_amd._lib import lib
-    from ocrs_models_amd.models import _DT
     from ocrs_models_amd.recognition import _RecRun
 
-    r = _RecRun.__new__(_RecRun)
-    r.L, r.dev, r.dtype, r.dt, r.N, r.H, r.W, r.P, r.G = lib(), dev, dtype, _DT[dtype], N, H, W, {}, {}
+    r = _RecRun({}, {}, dev, dtype, N, H, W)
+    r.G = {}
     return r
 
 
@@ -674,3 +672,41 @@ def test_ctc_side_by_side_recursions_are_bit_identical(dev, monkeypatch):
             out[mode] = (loss.detach().clone(), x.grad.clone())
         assert torch.equal(out[False][0], out[True][0]) or (torch.isinf(out[False][0]) and torch.isinf(out[True][0])), (T, N, Lmax)
         assert torch.equal(torch.nan_to_num(out[False][1]), torch.nan_to_num(out[True][1])), (T, N, Lmax)
+
+
+def test_throughput_mode_linear_layers_take_their_routes(dev, monkeypatch):
+    """One bf16-autocast training step at N = 2, W = 32 (T = 9: 18 GEMM rows; ocrs_gemm_x3p_supported takes any positive row count, asserted
+    below, so N = 2 is the smallest batch needed): the pipelined split-bf16 GEMM must run both GRU input projections, the output layer's input
+    gradient and both GRU input gradients from the pre-split packs of the step's table; the logits (ragged M = n_classes) run on ocrs_gemm_x3
+    from the master layout; no Linear layer runs as packed exact fp32.  A lookup that misses the table would silently move a layer to
+    ocrs_gemm_x3 -- same numbers, so only this pins it."""
+    import ocrs_models_amd as oa
+    from ocrs_models_amd._lib import lib
+
+    monkeypatch.setenv("OCRS_GRU_X3", "1")
+    N, W = 2, 32
+    rows = (W // 4 + 1) * N
+    L = lib()
+    for ldx, K, ldo, M in ((128, 128, 1536, 1536), (512, 512, 1536, 1536), (128, 128, 512, 512), (1536, 1536, 512, 512), (1536, 1536, 128, 128)):
+        assert L.gemm_x3p_supported(ldx, K, ldo, M, rows)
+    torch.manual_seed(3)
+    m = oa.RecognitionModel(oa.text.DEFAULT_ALPHABET).to(dev)
+    m.train()
+    C = m.output[0].weight.shape[0]
+    x = torch.rand(N, 1, 64, W, device=dev)
+    text = torch.randint(1, 90, (N, 3), dtype=torch.int32)
+    il, tl = torch.full((N,), W // 4, dtype=torch.int64), torch.full((N,), 3, dtype=torch.int64)
+    rec = {"gemm_x3p": [], "gemm_x3": [], "conv_igemm": []}
+    monkeypatch.setattr(L, "timing", rec)
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        lp = m(x)
+        loss = oa.CTCLoss()(lp, text.to(dev), il, tl)
+    loss.backward()
+    torch.cuda.synchronize()
+    # ocrs_gemm_x3p(X, ldx, K, wpk, bias, out, ldo, M, P): (K, M, P) in launch order
+    assert [(a[2], a[7], a[8]) for _, _, a in rec["gemm_x3p"]] == [(128, 1536, rows), (512, 1536, rows), (128, 512, rows), (1536, 512, rows),
+                                                                    (1536, 128, rows)]
+    # ocrs_gemm_x3(X, ldx, K, Wm, ldw, km, bias, out, ldo, M, P, Kw)
+    assert [(a[2], a[5], a[9], a[10]) for _, _, a in rec["gemm_x3"]] == [(512, 0, C, rows)]
+    # ocrs_conv_igemm: the six conv layers forward and their six input gradients, in bf16 (last argument) -- and nothing else
+    assert len(rec["conv_igemm"]) == 12 and all(a[-1] == 1 for _, _, a in rec["conv_igemm"])
