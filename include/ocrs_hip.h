@@ -155,6 +155,9 @@ int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
 int ocrs_pw_bwd_fin(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
                     int pooled, const void* z, const float* bn, float* coef, const double* gsum, const float* gamma, const float* saved, float* dgamma,
                     float* dbeta, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N, int H, int W, int dtype, hipStream_t st);
+/* the kernel ocrs_pw_bwd_fin runs for a block shape when given a workspace: 1 = k_pwb (det_pwb.hip), 2 = k_pw_bwd2 (det_pw2.hip), 3 = k_pw_bwd2
+   once per source of a 32 | 32 concat, 4 = the generic k_pw_bwd, 0 = none (the call answers OCRS_ERR_ARG) */
+long ocrs_pw_bwd_kernel(int Ca, int Cb, int Cout, int dtype);
 /* autograd of the depthwise 3x3 conv (dL/dx~ split at channel Ca into gxa|gxb; dwdw [C][1][3][3] accumulated). */
 /*   ws: ocrs_dw_bwd_ws_floats() floats of workspace (per-block partials, two-stage reduction) or NULL (float atomics). */
 long ocrs_dw_bwd_ws_floats(int C, int N, int H, int W);
@@ -270,6 +273,8 @@ int ocrs_fold64_multi(const int* table, int nrows, float* dst, const double* src
  * step); the same holds for gsum of ocrs_rec_bn_reduce / ocrs_avgpool_bn_reduce. */
 int ocrs_conv_igemm(const void* x, int ldx, const void* wpk, void* out, int ldo, const float* bias, int relu, double* gstat, int Cin, int M, int N,
                     int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw, int dtype, hipStream_t st);
+/* the kernel ocrs_conv_igemm runs for these arguments: 1 = k_conv3x3_tile, 2 = k_conv3x3_rows, 3 = k_conv3x3_c128, 0 = the generic k_conv_igemm */
+long ocrs_conv_igemm_kernel(int ldx, int ldo, int Cin, int M, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw, int dtype);
 /* weight gradients of Conv2d / Linear / GRU (autograd of the calls above). */
 /* Split-bf16 (bf16x3) weight-gradient GEMM for fp32 operands: dW [CA][CB] += A^T B over P rows (throughput mode of the GRU / Linear
  * weight gradients, train_rec.py:140 backward of models.py:264-268); <= ~1.1e-5 relative error per product, fp32 accumulation.

@@ -1606,6 +1606,21 @@ int ocrs_pw_bwd_fin(const void* xa, const void* xb, int Ca, int Cb, const float*
     return ocrs_pw_bwd(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, dtype, st);
 }
 
+// The kernel ocrs_pw_bwd_fin runs for a block shape when it is given a workspace (the dispatch above and in ocrs_pw_bwd, restated for callers
+// that must know what they exercised): 1 = k_pwb (det_pwb.hip), 2 = k_pw_bwd2 (det_pw2.hip), 3 = k_pw_bwd2 once per source of a 32 | 32 concat,
+// 4 = the generic k_pw_bwd, 0 = none (OCRS_ERR_ARG).
+long ocrs_pw_bwd_kernel(int Ca, int Cb, int Cout, int dtype) {
+    const int Cin = Ca + Cb;
+    if (det_pwb_supported(Cin, Cout, dtype)) return 1;
+    if (det_pw2_supported(Cin, Cout, dtype)) return 2;
+    if (pw2_split_ok(Ca, Cb, Cout, dtype)) return 3;
+#define X(CI, CO) \
+    if (Cin == CI && Cout == CO) return 4;
+    PW_BWD_COMBOS(X)
+#undef X
+    return 0;
+}
+
 // Depthwise-conv backward: gxa/gxb (either may be null) receive dL/dx~ split at channel Ca; dwdw accumulated in master layout [C][1][3][3].
 static void dw_bwd_grid(int C, int N, int H, int W, int& gx, int& gy, int& cg) {
     cg = C / 8 < 4 ? C / 8 : 4;  // channel groups (of 8) per block: 4 -> 8x4-pixel tiles, 2 -> 8x8, 1 -> 8x16

@@ -1345,6 +1345,15 @@ __global__ __launch_bounds__(256) void k_gemm_x3(const float* __restrict__ X, in
 
 extern "C" {
 
+// The kernel ocrs_conv_igemm runs for these arguments (its dispatch below, restated for callers that must know what they exercised):
+// 1 = k_conv3x3_tile (rec_conv4.hip), 2 = k_conv3x3_rows (rec_conv3.hip), 3 = k_conv3x3_c128 (rec_conv2.hip), 0 = the generic k_conv_igemm.
+long ocrs_conv_igemm_kernel(int ldx, int ldo, int Cin, int M, int Hi, int Wi, int Ho, int Wo, int KH, int KW, int padh, int padw, int dtype) {
+    if (conv3x3_tile_supported(ldx, ldo, Cin, M, Hi, Wi, Ho, Wo, KH, KW, padh, padw, dtype)) return 1;
+    if (conv3x3_rows_supported(ldx, ldo, Cin, M, Hi, Wi, Ho, Wo, KH, KW, padh, padw, dtype)) return 2;
+    if (conv3x3_c128_supported(ldx, ldo, Cin, M, Hi, Wi, Ho, Wo, KH, KW, padh, padw, dtype)) return 3;
+    return 0;
+}
+
 // Implicit-GEMM convolution / GEMM:  out[n][ho][wo][m] = sum_{ky,kx,c} W[m][(ky,kx,c)] * x[n][ho+ky-padh][wo+kx-padw][c]  (+bias, ReLU)
 //   nn.Conv2d forward (models.py:189-240), its dgrad (flipped packed weights), GRU input projections and nn.Linear (KH=KW=1, Hi=Ho=1).
 //   x [N][Hi][Wi][ldx] (Cin % 32 == 0, ldx >= Cin); wpk = ocrs_pack_frags(K = KH*KW*Cin ordered (tap, c), M); out [N][Ho][Wo][ldo];

@@ -1,0 +1,446 @@
+"""Integer-valued test inputs and float64 references for the bit-exact kernel tests (tests/test_exact_host.py, tests/test_exact_gpu.py).
+
+CPU only: nothing here imports the GPU package.
+
+The idea: the convolutions, the ConvTranspose and the GEMMs compute sums of products.  With small-integer (or half-integer) inputs and
+weights in {-1, 0, 1} every product and every partial sum is a multiple of 0.5 far below 2^24, so the result is the same in ANY summation
+order and ANY of the precisions the kernels use (fp32 MFMA accumulation, split-bf16, fp64 atomics, per-block partials, bf16 storage): a
+kernel must equal the float64 reference BIT FOR BIT.  The same inputs give many exact ties at a pooling maximum (equal small integers,
+and a constant plateau in the middle of the image with equal receptive fields), which fp32 noise never produces: the rule "the gradient
+goes to the FIRST maximum of the window in row-major order, and only if it is positive" becomes testable.
+
+Every reference asserts the conditions it relies on (`storable`, `summable`): a case that breaks one is a bug in the test, not a pass.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+
+BN_EPS = 1e-5
+# a BatchNorm pre-activation closer to zero than this could change its ReLU decision between fp32 and float64 arithmetic: cases keep clear of it
+SIGN_MARGIN = 2e-5
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# conditions
+# ---------------------------------------------------------------------------------------------------------------------------------
+def storable(t, what=""):
+    """every value a kernel stores in bf16: an integer or a multiple of 0.5, |v| < 256, and unchanged by a bf16 rounding"""
+    t = t.detach().double()
+    assert bool((t * 2 == torch.round(t * 2)).all()), f"{what}: not a multiple of 0.5"
+    assert float(t.abs().max()) < 256, f"{what}: |v| >= 256"
+    assert torch.equal(t.float().bfloat16().double(), t), f"{what}: not bf16-representable"
+    return t
+
+
+def summable(t, dims=None, what=""):
+    """every accumulated sum over `dims` (all if None) stays below 2^24 even if all terms had one sign"""
+    a = t.detach().double().abs()
+    s = a.sum() if dims is None else a.sum(dims)
+    assert float(s.max()) < 2 ** 24, f"{what}: sum of magnitudes {float(s.max())} >= 2^24"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# generators (torch.Generator on the CPU; everything returned is fp32 NCHW / fp32 parameters)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def gen(seed):
+    return torch.Generator().manual_seed(int(seed))
+
+
+def ints(g, shape, lo, hi):
+    return torch.randint(lo, hi + 1, tuple(shape), generator=g).float()
+
+
+def int_act(g, N, C, H, W):
+    """integers in [-2, 2] with a rectangular plateau of one constant value over the middle of the image"""
+    x = ints(g, (N, C, H, W), -2, 2)
+    x[:, :, H // 3: 2 * H // 3, W // 4: 3 * W // 4] = 2.0
+    return x
+
+
+def int_tr(g, C):
+    """load transform [scale | shift | floor]: scale from {1, -1, 0.5} (every fifth channel negative), integer shift in [-1, 1], floor 0"""
+    tr = torch.zeros(3, C)
+    tr[0] = torch.where(torch.rand(C, generator=g) < 0.5, 1.0, 0.5)
+    tr[0, ::5] = -1.0
+    tr[1] = ints(g, (C,), -1, 1)
+    return tr
+
+
+def apply_tr(x, tr):
+    tr = tr.to(x.dtype)
+    return torch.maximum(x * tr[0].view(1, -1, 1, 1) + tr[1].view(1, -1, 1, 1), tr[2].view(1, -1, 1, 1))
+
+
+def tern(g, shape):
+    """weights in {-1, 0, 1}"""
+    return ints(g, shape, -1, 1)
+
+
+def sparse_pm1(g, rows, cols, nnz=4):
+    """[rows, cols] with at most `nnz` non-zeros of +-1 per row"""
+    w = torch.zeros(rows, cols)
+    k = min(nnz, cols)
+    for r in range(rows):
+        idx = torch.randperm(cols, generator=g)[:k]
+        w[r, idx] = (torch.randint(0, 2, (k,), generator=g) * 2 - 1).float()
+    return w
+
+
+def block_params(g, pfx, Cin, Cout, neg=1):
+    """DepthwiseConv block parameters: ternary depthwise weights, <= 4 non-zeros of +-1 per pointwise output row, float gamma / beta (they act
+    behind the exact part) with gamma[neg] negative"""
+    P = {
+        f"{pfx}.seq.0.weight": tern(g, (Cin, 1, 3, 3)),
+        f"{pfx}.seq.1.weight": sparse_pm1(g, Cout, Cin).view(Cout, Cin, 1, 1),
+        f"{pfx}.seq.2.weight": 1 + 0.1 * torch.randn(Cout, generator=g),
+        f"{pfx}.seq.2.bias": 0.1 * torch.randn(Cout, generator=g),
+    }
+    P[f"{pfx}.seq.2.weight"][neg] *= -1
+    return P
+
+
+def convt_weight(g, Cup, Cout):
+    """ConvTranspose2d weight [Cup][Cout][3][3]: at most 4 non-zeros of +-1 per (output channel, tap) column"""
+    return sparse_pm1(g, Cout * 9, Cup).view(Cout, 3, 3, Cup).permute(3, 0, 1, 2).contiguous()
+
+
+def conv_weight(g, co, ci, k):
+    """Conv2d weight [co][ci][k][k]: at most 4 non-zeros of +-1 per (output channel, tap)"""
+    return sparse_pm1(g, co * k * k, ci).view(co, k, k, ci).permute(0, 3, 1, 2).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# pooling with an explicit tie rule
+# ---------------------------------------------------------------------------------------------------------------------------------
+def windows(y, ph=2, pw=2):
+    """[N, C, H, W] -> [N, C, H//ph, W//pw, ph*pw], window elements in row-major order (floor mode)"""
+    N, C, H, W = y.shape
+    hp, wp = H // ph, W // pw
+    return y[:, :, : hp * ph, : wp * pw].reshape(N, C, hp, ph, wp, pw).permute(0, 1, 2, 4, 3, 5).reshape(N, C, hp, wp, ph * pw)
+
+
+def pool_index(y, ph=2, pw=2, last=False):
+    """index (row-major within the window) of the FIRST maximum -- the rule of every kernel and of torch's max_pool2d -- or of the LAST one"""
+    win = windows(y.detach(), ph, pw)
+    k = win.shape[-1]
+    rank = torch.arange(1, k + 1) if last else torch.arange(k, 0, -1)  # distinct weights on the maxima: no reliance on argmax's own tie order
+    return ((win == win.max(-1, keepdim=True).values) * rank).argmax(-1)
+
+
+def pool(y, ph=2, pw=2, last=False):
+    """differentiable max-pool whose gradient goes to pool_index's element"""
+    return windows(y, ph, pw).gather(-1, pool_index(y, ph, pw, last).unsqueeze(-1)).squeeze(-1)
+
+
+def tied_share(y, ph=2, pw=2):
+    """share of ALL windows whose maximum is positive and attained more than once"""
+    win = windows(y.detach(), ph, pw)
+    m = win.max(-1).values
+    tied = (m > 0) & ((win == m.unsqueeze(-1)).sum(-1) > 1)
+    return float(tied.double().mean())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the DepthwiseConv block (depthwise 3x3 -> pointwise 1x1 -> BatchNorm -> ReLU [-> MaxPool2d(2)])
+# ---------------------------------------------------------------------------------------------------------------------------------
+def block_case(seed, Ca, Cb, Cout, N, H, W, neg=1, pfx="blk"):
+    g = gen(seed)
+    case = {"pfx": pfx, "Ca": Ca, "Cb": Cb, "Cout": Cout, "shape": (N, H, W),
+            "xa": int_act(g, N, Ca, H, W), "tra": int_tr(g, Ca),
+            "xb": int_act(g, N, Cb, H, W) if Cb else None, "trb": int_tr(g, Cb) if Cb else None,
+            "P": block_params(g, pfx, Ca + Cb, Cout, neg)}
+    case["g_full"] = [ints(g, (N, Cout, H, W), -2, 2) for _ in range(2)]
+    case["g_pool"] = [ints(g, (N, Cout, H // 2, W // 2), -2, 2) for _ in range(2)]
+    return case
+
+
+def first_block_case(seed, N, H, W, pfx="blk"):
+    """Cin = 1: integer image, ternary depthwise weight, pointwise weights +-1 (one input channel)"""
+    g = gen(seed)
+    P = block_params(g, pfx, 1, 8)
+    return {"pfx": pfx, "shape": (N, H, W), "img": int_act(g, N, 1, H, W), "P": P}
+
+
+def block_linear(case, mode="f64"):
+    """-> (x~ [the concatenated, load-transformed input], u, z): the exact part of the block, evaluated in float64 ("f64"), in fp32 ("f32") or
+    in fp32 with u and z rounded to bf16 where the kernels store / stage them ("bf16").  All three must be identical."""
+    dt = torch.float64 if mode == "f64" else torch.float32
+    rnd = (lambda t: t.bfloat16().to(dt)) if mode == "bf16" else (lambda t: t)
+    P, pfx = case["P"], case["pfx"]
+    if "img" in case:
+        xt = case["img"].to(dt)
+    else:
+        xs = [apply_tr(case["xa"].to(dt), case["tra"])] + ([apply_tr(case["xb"].to(dt), case["trb"])] if case["Cb"] else [])
+        xt = rnd(torch.cat(xs, 1))
+    cin = xt.shape[1]
+    u = rnd(F.conv2d(xt, P[f"{pfx}.seq.0.weight"].to(dt), None, 1, 1, 1, cin))
+    z = rnd(F.conv2d(u, P[f"{pfx}.seq.1.weight"].to(dt)))
+    return xt, u, z
+
+
+def bn_relu(z, gamma, beta):
+    """training-mode BatchNorm + ReLU in float64 -> (activation, pre-activation, mean, biased variance)"""
+    mean = z.mean((0, 2, 3))
+    var = z.var((0, 2, 3), unbiased=False)
+    pre = (z - mean.view(1, -1, 1, 1)) * (gamma / torch.sqrt(var + BN_EPS)).view(1, -1, 1, 1) + beta.view(1, -1, 1, 1)
+    return torch.relu(pre), pre, mean, var
+
+
+def block_reference(case, pooled=False, last=False, with_grads=True):
+    """float64 reference of the block: z, batch statistics, the (pooled) activation and, by autograd through pool(relu(batch_norm(z))),
+    dL/dx~ and the four parameter gradients for the upstream gradient g1 + g2.  `last`: route through the LAST maximum instead (sensitivity)."""
+    pfx = case["pfx"]
+    xt, u, z = block_linear(case, "f64")
+    storable(xt, "x~"), storable(u, "u"), storable(z, "z")
+    summable(z, (0, 2, 3), "sum z"), summable(z * z, (0, 2, 3), "sum z^2")
+    Pr = {k: v.double().clone().requires_grad_(True) for k, v in case["P"].items()}
+    xt = xt.clone().requires_grad_(True)
+    cin = xt.shape[1]
+    zz = F.conv2d(F.conv2d(xt, Pr[f"{pfx}.seq.0.weight"], None, 1, 1, 1, cin), Pr[f"{pfx}.seq.1.weight"])
+    assert torch.equal(zz.detach(), z)
+    y, pre, mean, var = bn_relu(zz, Pr[f"{pfx}.seq.2.weight"], Pr[f"{pfx}.seq.2.bias"])
+    assert float(pre.detach().abs().min()) > SIGN_MARGIN, "a BatchNorm pre-activation too close to the ReLU threshold: choose another seed"
+    res = {"xt": xt.detach(), "u": u, "z": z, "y": y.detach(), "mean": mean.detach(), "var": var.detach()}
+    if pooled:
+        out = pool(y, last=last)
+        res["pooled"] = out.detach()
+        res["index"] = pool_index(y, last=last)
+        res["tied"] = tied_share(y)
+    else:
+        out = y
+    if with_grads:
+        gs = case["g_pool" if pooled else "g_full"]
+        gsum = (gs[0] + gs[1]).double()
+        names = list(Pr)
+        grads = torch.autograd.grad(out, [xt] + [Pr[k] for k in names], grad_outputs=gsum)
+        res["dx"], res["grads"] = grads[0], dict(zip(names, grads[1:]))
+    return res
+
+
+def rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).norm() / (b.norm() + 1e-30))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# ConvTranspose2d(k3, s2, bias) + crop
+# ---------------------------------------------------------------------------------------------------------------------------------
+def convt_case(seed, Cup, Cout, h, w, H, W, N=2):
+    g = gen(seed)
+    return {"dims": (Cup, Cout, h, w, H, W, N), "x": int_act(g, N, Cup, h, w), "tr": int_tr(g, Cup), "W": convt_weight(g, Cup, Cout),
+            "b": ints(g, (Cout,), -2, 2), "gy": ints(g, (N, Cout, H, W), -2, 2)}
+
+
+def convt_reference(case, mode="f64"):
+    """-> output, dL/dx~, dW, db.  Everything is linear in integers: exact in every mode."""
+    dt = torch.float64 if mode == "f64" else torch.float32
+    rnd = (lambda t: t.bfloat16().to(dt)) if mode == "bf16" else (lambda t: t)
+    Cup, Cout, h, w, H, W, N = case["dims"]
+    xt = rnd(apply_tr(case["x"].to(dt), case["tr"])).requires_grad_(True)
+    Wr, br = case["W"].to(dt).requires_grad_(True), case["b"].to(dt).requires_grad_(True)
+    out = F.conv_transpose2d(xt, Wr, br, stride=2)[:, :, :H, :W]
+    dx, dW, db = torch.autograd.grad(out, [xt, Wr, br], grad_outputs=case["gy"].to(dt))
+    out, dx = rnd(out.detach()), rnd(dx)
+    if mode == "f64":
+        storable(xt, "x~"), storable(out, "out"), storable(dx, "dx")
+        # every partial sum of dW / db is bounded by max|x~| max|gy| times the number of positions
+        assert 3 * 2 * N * H * W < 2 ** 24 and float(xt.detach().abs().max()) <= 3
+    return {"xt": xt.detach(), "out": out, "dx": dx, "dW": dW, "db": db}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# recognition convolutions: Conv2d(k, pad) + bias + ReLU, dgrad, wgrad
+# ---------------------------------------------------------------------------------------------------------------------------------
+def conv_case(seed, ci, co, k, pad, H, W, N):
+    g = gen(seed)
+    Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
+    return {"dims": (ci, co, k, pad, H, W, N), "x": int_act(g, N, ci, H, W), "w": conv_weight(g, co, ci, k), "b": ints(g, (co,), -2, 2),
+            "dz": ints(g, (N, co, Ho, Wo), -2, 2)}
+
+
+def conv_reference(case, mode="f64"):
+    """-> relu(conv + bias), its per-channel sums (sum, sum of squares), dL/dx and dW of the PRE-activation for the upstream gradient dz"""
+    dt = torch.float64 if mode == "f64" else torch.float32
+    rnd = (lambda t: t.bfloat16().to(dt)) if mode == "bf16" else (lambda t: t)
+    ci, co, k, pad, H, W, N = case["dims"]
+    x = case["x"].to(dt).requires_grad_(True)
+    w = case["w"].to(dt).requires_grad_(True)
+    pre = F.conv2d(x, w, None, padding=pad)
+    out = rnd(torch.relu(pre.detach() + case["b"].to(dt).view(1, -1, 1, 1)))
+    dx, dW = torch.autograd.grad(pre, [x, w], grad_outputs=case["dz"].to(dt))
+    dx = rnd(dx)
+    s1, s2 = out.sum((0, 2, 3)), (out * out).sum((0, 2, 3))
+    if mode == "f64":
+        storable(out, "out"), storable(dx, "dx")
+        summable(dW, None, "dW")
+        # dW's partial sums: bounded by the sum of |x| |dz| over all positions
+        assert float(case["x"].abs().max() * case["dz"].abs().max()) * N * H * W < 2 ** 24
+    return {"out": out, "dx": dx, "dW": dW, "s1": s1, "s2": s2, "sums_exact": bool(float(s2.max()) < 2 ** 24)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# conv0: Conv2d(1 -> 32, k3, pad 1) + bias + ReLU + MaxPool2d(2), weight / bias gradient
+# ---------------------------------------------------------------------------------------------------------------------------------
+def conv0_case(seed, N, H, W):
+    g = gen(seed)
+    return {"shape": (N, H, W), "img": int_act(g, N, 1, H, W), "w": tern(g, (32, 1, 3, 3)), "b": ints(g, (32,), -1, 1),
+            "gy": ints(g, (N, 32, H // 2, W // 2), -2, 2)}
+
+
+def conv0_reference(case, mode="f64", last=False):
+    dt = torch.float64 if mode == "f64" else torch.float32
+    rnd = (lambda t: t.bfloat16().to(dt)) if mode == "bf16" else (lambda t: t)
+    w, b = case["w"].to(dt).requires_grad_(True), case["b"].to(dt).requires_grad_(True)
+    y = torch.relu(F.conv2d(case["img"].to(dt), w, b, padding=1))
+    out = pool(y, last=last)
+    dW, db = torch.autograd.grad(out, [w, b], grad_outputs=case["gy"].to(dt))
+    if mode == "f64":
+        storable(out, "pooled")
+        N, H, W = case["shape"]
+        assert 2 * 2 * N * H * W < 2 ** 24  # |img| <= 2, |gy| <= 2: every partial sum of dW / db
+        if not last:
+            assert torch.equal(out.detach(), F.max_pool2d(y.detach(), 2))
+    return {"out": rnd(out.detach()), "dW": dW, "db": db, "tied": tied_share(y)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# BatchNorm + ReLU + MaxPool2d((PH, PW)) forward and the pieces of its backward, with dyadic caller-supplied coefficients
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pool_pieces_case(seed, N, H, W, C, PH, PW):
+    g = gen(seed)
+    pow2 = lambda n, lo, hi: torch.pow(2.0, ints(g, (n,), lo, hi))  # noqa: E731
+    sc = pow2(C, -1, 1)
+    sc[3] *= -1  # one negative scale channel
+    tr = torch.stack([sc, ints(g, (C,), -1, 1), torch.zeros(C)])
+    saved = torch.stack([ints(g, (C,), -1, 1), pow2(C, -1, 1)])  # [mean | rstd]
+    coef = torch.stack([pow2(C, -1, 1) * (ints(g, (C,), 0, 1) * 2 - 1), pow2(C, -2, 0) * (ints(g, (C,), 0, 1) * 2 - 1), ints(g, (C,), -1, 1)])
+    return {"dims": (N, H, W, C, PH, PW), "z": int_act(g, N, C, H, W), "tr": tr, "saved": saved, "coef": coef,
+            "gy": ints(g, (N, C, H // PH, W // PW), -2, 2)}
+
+
+def pool_pieces_reference(case, mode="f64", last=False):
+    """-> pooled activation, gsum = [sum ghat | sum ghat zhat], dz = coef0 ghat + coef1 z + coef2, dsum = column sums of dz; ghat = the pooled
+    gradient routed to each window's first maximum, through the ReLU (NOT through the scale)"""
+    dt = torch.float64 if mode == "f64" else torch.float32
+    rnd = (lambda t: t.bfloat16().to(dt)) if mode == "bf16" else (lambda t: t)
+    N, H, W, C, PH, PW = case["dims"]
+    v = lambda t: t.to(dt).view(1, C, 1, 1)  # noqa: E731
+    z = case["z"].to(dt)
+    tr, saved, coef = case["tr"], case["saved"], case["coef"]
+    a = (z * v(tr[0]) + v(tr[1])).requires_grad_(True)
+    y = torch.relu(a)
+    out = pool(y, PH, PW, last=last)
+    ghat, = torch.autograd.grad(out, [a], grad_outputs=case["gy"].to(dt))
+    zhat = (z - v(saved[0])) * v(saved[1])
+    gsum = torch.cat([ghat.sum((0, 2, 3)), (ghat * zhat).sum((0, 2, 3))])
+    dz = rnd(v(coef[0]) * ghat + v(coef[1]) * z + v(coef[2]))
+    res = {"out": rnd(out.detach()), "ghat": ghat, "gsum": gsum, "dz": dz, "dsum": dz.sum((0, 2, 3)), "tied": tied_share(y.detach(), PH, PW)}
+    if mode == "f64":
+        storable(res["out"], "pooled"), storable(dz * 2, "2 dz")  # dz: multiples of 0.25 (bf16-exact below 64)
+        assert torch.equal(dz.float().bfloat16().double(), dz) and float((ghat * zhat * 4 - torch.round(ghat * zhat * 4)).abs().max()) == 0
+        summable(ghat * zhat, (0, 2, 3), "gsum"), summable(dz, (0, 2, 3), "dsum")
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GEMMs
+# ---------------------------------------------------------------------------------------------------------------------------------
+def gemm_operands(seed, P, K, M):
+    """integer operands with |v| <= 4 -> (X [P, K], W [K, M], bias [M]); every partial sum is an integer of magnitude <= 16 K + 4"""
+    assert 16 * max(P, K) + 4 < 2 ** 24
+    g = gen(seed)
+    return ints(g, (P, K), -4, 4), ints(g, (K, M), -4, 4), ints(g, (M,), -4, 4)
+
+
+def wgrad_gemm_operands(P, CA, ldA, CB, ldB):
+    """-> (A [P, ldA], B [P, ldB], dW0 [CA, CB]): dW = dW0 + A[:, :CA]^T B[:, :CB], every partial sum an integer of magnitude <= 16 P + 4"""
+    assert 16 * P + 4 < 2 ** 24
+    g = gen(seed_of(10, P, CA, CB))
+    return ints(g, (P, ldA), -4, 4), ints(g, (P, ldB), -4, 4), ints(g, (CA, CB), -4, 4)
+
+
+def wgrad_gather_operands(N, CA, CB, H, W, K, pad):
+    """-> (x [N, CB, H, W], dz [N, CA, Ho, Wo], dW0 [CA, CB, K, K]) of a stride-1 Conv2d weight gradient accumulated into dW0"""
+    Ho, Wo = H + 2 * pad - K + 1, W + 2 * pad - K + 1
+    assert 16 * N * Ho * Wo + 4 < 2 ** 24
+    g = gen(seed_of(11, N, CA, CB, K))
+    return ints(g, (N, CB, H, W), -4, 4), ints(g, (N, CA, Ho, Wo), -4, 4), ints(g, (CA, CB, K, K), -4, 4)
+
+
+def wgrad_gather_reference(x, dz, dW0, pad, dt=torch.float64):
+    wr = torch.zeros(dW0.shape, dtype=dt, requires_grad=True)
+    F.conv2d(x.to(dt), wr, padding=pad).backward(dz.to(dt))
+    return dW0.to(dt) + wr.grad
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the cases (one table for the host checks and the GPU tests)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _block_shapes(Ca, Cb, small_only=False):
+    big = Ca + Cb >= 128
+    return [(2, 9, 13) if big else (2, 21, 37), (2, 2, 3)] + ([] if (big or small_only) else [(2, 32, 96)])
+
+
+# (route, dtype name, (Ca, Cb, Cout)) of the block forward
+FWD_CHANNELS = ([("mm", "bf16", c) for c in [(8, 0, 8), (8, 8, 8), (16, 0, 32), (32, 32, 32)]]
+                + [("rs32", "fp32", c) for c in [(8, 0, 16), (16, 16, 16)]]
+                + [("tile", d, c) for d in ("fp32", "bf16") for c in [(64, 0, 128), (128, 128, 128), (128, 0, 256)]])
+FWD_CASES = [(route, d, c, s) for route, d, c in FWD_CHANNELS for s in _block_shapes(c[0], c[1], small_only=route == "tile")]
+FIRST_BLOCK_SHAPES = [(2, 19, 23), (1, 2, 192)]
+
+# (forward route, backward route, the kernel that routes the pooled gradient, dtype name, (Ca, Cb, Cout)) of the pooled block backward:
+# test_block_bwd_through_maxpool's four routings in both dtypes; k_rs32_bwdp at its other channel shapes, 8 -> 16 and 16 -> 8
+# (test_rs32_block_backward_through_maxpool's); the fp32 concat input 8 | 8 -> 16, whose pooled backward has no row-streaming instantiation and runs
+# tiled behind a row-streaming forward; and k_pw_bwd2 (det_pw2.hip), which takes the matrix-core shapes and runs with those kernels off: 16 -> 16
+# and the two-launch split of the 32 | 32 concat
+BWD_POOLED_CHANNELS = ([("rs32", "rs32", "k_rs32_bwdp", "fp32", (16, 0, 16)), ("mm", "mm", "k_mm_bwd", "bf16", (16, 0, 16))]
+                       + [("tile", "tile", k, d, (C, 0, Co)) for d, k in (("fp32", "k_pw_bwd"), ("bf16", "k_pwb")) for C, Co in [(64, 64), (32, 64), (128, 128)]]
+                       + [("rs32", "rs32", "k_rs32_bwdp", "fp32", (8, 0, 16)), ("rs32", "rs32", "k_rs32_bwdp", "fp32", (16, 0, 8)),
+                          ("rs32", "tile", "k_pw_bwd", "fp32", (8, 8, 16)),
+                          ("tile", "tile", "k_pw_bwd2", "bf16", (16, 0, 16)), ("tile", "tile", "k_pw_bwd2 x2", "bf16", (32, 32, 32))])
+BWD_SHAPES = [(2, 11, 15), (2, 2, 3)]
+BWD_POOLED_CASES = [(fr, br, k, d, c, s) for fr, br, k, d, c in BWD_POOLED_CHANNELS for s in BWD_SHAPES]
+# unpooled backward with two gradient tensors: one case per kernel family
+BWD_FULL_CASES = [("mm", "k_mm_bwd", "bf16", (16, 0, 16), (2, 11, 15)), ("rs32", "k_rs32_bwd", "fp32", (16, 0, 16), (2, 11, 15)),
+                  ("tile", "k_pw_bwd", "fp32", (64, 0, 64), (2, 11, 15)), ("tile", "k_pwb", "bf16", (64, 0, 64), (2, 11, 15)),
+                  ("tile", "k_pw_bwd2", "bf16", (16, 0, 16), (2, 11, 15))]
+
+CONVT_CASES = [(16, 8, 6, 9, 12, 19), (32, 16, 5, 7, 11, 14), (32, 32, 4, 4, 9, 9), (64, 32, 3, 5, 6, 10), (128, 64, 3, 3, 7, 6), (256, 128, 2, 3, 4, 7),
+               (16, 8, 40, 37, 81, 75), (32, 16, 35, 20, 70, 41), (32, 32, 33, 17, 67, 34)]
+CONV_CASES = [(32, 64, 3, 1, 12, 20, 3), (64, 128, 3, 1, 9, 17, 3), (128, 128, 3, 1, 8, 33, 3), (128, 128, 2, 1, 4, 19, 3), (128, 128, 3, 1, 21, 16, 3),
+              (128, 64, 3, 1, 16, 37, 3), (32, 64, 3, 1, 32, 77, 3),
+              # the smallest shape that reaches k_conv3x3_c128 (bf16 forward: 128 outputs, a row of a whole number of 16-pixel tiles longer than 64) and,
+              # with its input gradient, the generic k_conv_igemm in bf16
+              (64, 128, 3, 1, 8, 80, 2)]
+CONV0_SHAPES = [(2, 64, 24), (2, 32, 66), (5, 8, 130), (2, 16, 37)]
+GEMM_CASES = [(77, 128, 36, 40), (777, 1536, 512, 516)]                      # (P, K, M, ldo) of the exact-fp32 packed GEMM
+GEMM_X3_CASES = [(77, 128, 36, 0, 0), (777, 1536, 512, 1, 0), (333, 64, 5, 0, 60)]  # (P, K, M, km, kw) of ocrs_gemm_x3 (and _x3p where it takes the shape)
+WGRAD_GEMM_CASES = [(4001, 768, 1536, 256, 512), (77, 100, 128, 36, 40)]  # (P, CA, ldA, CB, ldB) of ocrs_wgrad_gemm_x3
+WGRAD_GATHER_CASES = [(3, 40, 24, 7, 9, 3, 1), (1, 8, 8, 3, 3, 3, 1)]     # (N, CA, CB, H, W, K, pad) of ocrs_wgrad_gather
+POOL_PIECES_CASES = [(2, 8, 12, 64, 2, 2), (2, 9, 13, 64, 2, 2), (3, 8, 7, 128, 2, 1), (2, 7, 5, 128, 2, 1), (2, 5, 9, 128, 1, 1)]
+
+
+def seed_of(*key):
+    s = 17
+    for k in key:
+        for v in (k if isinstance(k, (tuple, list)) else (k,)):
+            s = (s * 131 + int(v)) % 1000003
+    return s
+
+
+# Seeds are chosen, not drawn: a case must keep the tied-window floor and the ReLU margin (tests/test_exact_host.py asserts both for every
+# case).  At the minimum shape (2, 2, 3) a case has ONE window per image and channel, so the share is a coarse count and most seeds of the
+# plain recipe land at 6-9 %; the salts below are the first ones (searched upwards from 0) at which every host check holds.
+FWD_SALT = {((128, 0, 256), (2, 2, 3)): 1, ((128, 128, 128), (2, 2, 3)): 1, ((16, 16, 16), (2, 2, 3)): 1, ((8, 0, 16), (2, 2, 3)): 6}
+BWD_SALT = {((16, 0, 16), (2, 11, 15)): 2, ((16, 0, 16), (2, 2, 3)): 2, ((32, 0, 64), (2, 2, 3)): 1, ((8, 8, 16), (2, 11, 15)): 1, ((8, 8, 16), (2, 2, 3)): 4, ((8, 0, 16), (2, 2, 3)): 3, ((32, 32, 32), (2, 2, 3)): 1}
+
+
+def fwd_block_case(chans, shape, salt=None):
+    salt = FWD_SALT.get((tuple(chans), tuple(shape)), 0) if salt is None else salt
+    return block_case(seed_of(1, chans, shape, salt), *chans, *shape, neg=1)
+
+
+def bwd_block_case(chans, shape, salt=None):
+    salt = BWD_SALT.get((tuple(chans), tuple(shape)), 0) if salt is None else salt
+    return block_case(seed_of(2, chans, shape, salt), *chans, *shape, neg=3)
