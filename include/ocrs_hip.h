@@ -586,6 +586,34 @@ int ocrs_word_chars(const float* words, long wcap, const float* line_quads, cons
                     const int* plan, long rows, int ld, const int* labels, const int* lens, const float* s0, const float* s1, int space, int* word_chars,
                     hipStream_t st);
 
+/* ------------------------------------------------------------------ beam search -------------- */
+/* CTC prefix beam search and forced alignment by the rule of DESIGN.md §18 (csrc/ctc_beam.hip; Python: text.beam_decode_spans,
+ * text.ctc_align_spans; restated in tests/beam_ref.py).  Both generalise ctc_greedy_decode_text (datasets/util.py:147-177), the greedy rule:
+ * it returns the labelling of the single most probable alignment, the beam the most probable labelling among the prefixes it kept.  lp
+ * [T][N][C] fp32 log-probs, class 0 = blank, in_len [N] (clamped to 0..T); sample n reads / writes row row0 + n of the span arrays (pitch
+ * ld >= T), as ocrs_ctc_decode_spans does.  One launch each, nothing synchronises, integer LDS atomics only: equal input gives equal bytes.
+ *
+ * Workspace sizes (host only, no GPU needed; 0 = shape not supported).  Beam: the prefix tree, (T W + 1) nodes of 8 bytes per sample.
+ * Align: two 64-bit back-pointer words per step and 64 states, for labellings of up to min(Lmax, T) labels. */
+long ocrs_ctc_beam_ws_bytes(int T, int N, int W);
+long ocrs_ctc_align_ws_bytes(int T, int N, int Lmax);
+/* Stands in for ctc_greedy_decode_text (datasets/util.py:147-177) with a beam of W prefixes, 1 <= W <= 64, 2 <= C <= 256 (anything else:
+ * error 1, nothing launched).  Per step every prefix stays (blank, a repeat of its last label, and the mass of its parent prefix extending
+ * into it) and extends by every label 1..C-1; the W largest totals survive, ties by (slot, stay before extend, label) ascending; no label
+ * pruning.  labels / lens: the labelling of the best prefix after the last step; score [rows] fp32: its log-mass (in_len 0: empty, 0.0; no
+ * candidate of finite mass left: empty, -inf).  Entries of a row from lens on are not written.  ws: 8-byte aligned,
+ * ocrs_ctc_beam_ws_bytes(T, N, W) bytes.  One workgroup per sample. */
+int ocrs_ctc_beam_decode(const float* lp, const long long* in_len, int T, int N, int C, int W, long row0, int ld, int* labels, int* lens, float* score, void* ws,
+                         long ws_bytes, hipStream_t st);
+/* The t0 / t1 / peak that ocrs_ctc_decode_spans derives from ctc_greedy_decode_text's runs (datasets/util.py:147-177), for a GIVEN labelling:
+ * Viterbi over blank | l1 | blank | ... | lL | blank (ties: stay, then one state back, then two; the final blank wins a tied end).  Reads
+ * labels / lens of rows row0 .. row0 + N - 1; character k gets the first / last step the path spends in its state and peak = the largest
+ * lp[t][n][l_k] over them, a bit copy.  lens = -1 where no alignment has a finite score (more labels than steps, no room for the blank between
+ * equal neighbours, a label outside 1..C-1, more labels than ws was sized for, or more than 3199); rows with lens < 0 are skipped.  ws:
+ * 8-byte aligned, at least the size for Lmax = 0.  One wave per sample. */
+int ocrs_ctc_align_spans(const float* lp, const long long* in_len, int T, int N, int C, long row0, int ld, const int* labels, int* lens, int* t0, int* t1,
+                         float* peak, void* ws, long ws_bytes, hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

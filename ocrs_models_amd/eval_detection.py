@@ -1,6 +1,6 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
-    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]] [--chars]
+    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]] [--chars] [--beam-width N]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
@@ -10,7 +10,9 @@ With ``--lines`` the words are grouped into text lines first (``inference.find_l
 in reading order, instead of the words.  ``--lines --reading-order`` prints those objects in the page's reading order (column by column,
 ``inference.reading_order``), each with ``"block"``, the number of its text block.  ``--chars`` (with ``--rec-model``) adds to every object where each
 character of its text sits on the page and the recogniser's log-prob of it (``"char_quads"``, ``"char_log_probs"``), and to every line object the text and
-character range of each of its words (``"word_texts"``, ``"word_chars"``): ``inference.char_boxes`` / ``word_chars``.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
+character range of each of its words (``"word_texts"``, ``"word_chars"``): ``inference.char_boxes`` / ``word_chars``.  ``--beam-width N`` (with
+``--rec-model``) decodes by CTC prefix beam search with N prefixes instead of greedily and adds ``"log_prob"``, the log-mass of the text, to every
+object.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -58,9 +60,15 @@ def main(argv=None):
                         "column, each with the number of its block")
     parser.add_argument("--chars", action="store_true", help="with --rec-model: add every character's quad and log-prob to the JSON objects and, with "
                         "--lines, every word's text and character range")
+    parser.add_argument("--beam-width", type=int, default=None, metavar="N", help="with --rec-model: decode by CTC prefix beam search with N prefixes "
+                        "(1..64) instead of greedily and add the text's log-prob to the JSON objects")
     args = parser.parse_args(argv)
     if args.reading_order and not args.lines:
         parser.error("--reading-order needs --lines")
+    if args.beam_width is not None and not args.rec_model:
+        parser.error("--beam-width needs --rec-model")
+    if args.beam_width is not None and not 1 <= args.beam_width <= 64:
+        parser.error("--beam-width must be in 1..64")
 
     device = torch.device("cuda:0")
     model = DetectionModel().to(device)
@@ -92,7 +100,7 @@ def main(argv=None):
         rec.eval()
     if args.lines:
         if rec is not None:
-            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars)
+            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width)
             for line in lines:
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]
@@ -105,10 +113,13 @@ def main(argv=None):
         packed = inference.rectify_crops(page, det["quads"], plan)
         batches = inference.crops_to_batches(packed, plan)
         if args.chars:
-            spans = inference.decode_crop_spans(rec, batches)
+            spans = inference.decode_crop_spans(rec, batches, args.beam_width)
             texts, chars, _ = inference.chars_to_host(spans, inference.char_boxes(det["quads"], plan, spans))
             for quad, p in zip(quads, batches[2]):
                 print(json.dumps({"quad": quad, "text": texts[p], **chars[p]}))
+        elif args.beam_width is not None:
+            for quad, text, score in zip(quads, *inference.recognize_crops(rec, batches, beam_width=args.beam_width)):
+                print(json.dumps({"quad": quad, "text": text, "log_prob": score}))
         else:
             for quad, text in zip(quads, inference.recognize_crops(rec, batches)):
                 print(json.dumps({"quad": quad, "text": text}))

@@ -48,6 +48,12 @@ character was collapsed from and its log-prob -- and return, next to the keys th
 (``char_boxes``: time steps to crop columns to the page through the crop frame) and, for lines, the characters and the text of every word
 (``word_chars``: neighbouring words split the line half way between them; spaces at the ends of a range are dropped); the same three waits.
 
+Beam search (csrc/ctc_beam.hip, C ABI section "beam search"; restated for the tests in tests/beam_ref.py).  With ``beam_width=W``
+the same functions decode every crop by CTC prefix beam search -- the most probable labelling among the W prefixes kept per step, where the
+greedy decode returns the labelling of the single most probable alignment -- and add ``"log_prob"``, the labelling's log-mass, to every
+dict; the spans that ``chars=True`` needs come from a forced alignment of the chosen labelling.  None, the default, is the greedy path
+unchanged; the same three waits either way.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
@@ -61,7 +67,8 @@ import torch
 
 from ._lib import lib, ptr
 from .input_pipeline import _need_cuda, resize, transform_image
-from .text import DEFAULT_ALPHABET, decode_text, greedy_decode_batch_async, greedy_decode_spans_async, round_up, span_arrays
+from .text import (DEFAULT_ALPHABET, _check_beam_width, beam_decode_spans_async, decode_text, greedy_decode_batch_async, greedy_decode_spans_async, round_up,
+                   span_arrays)
 
 MASK_SIZE = (800, 600)   # train_detection.py's mask_size: the size the detection model is trained and evaluated at
 SHRINK_DISTANCE = 3.0    # datasets/util.py: how far text polygons are shrunk when training masks are made
@@ -264,13 +271,15 @@ class CharSpans:
     entries, rows in the crop plan's width-sorted order (row p is the crop of quad ``plan.table[p, 7]``).  Character k of row p has label
     ``labels[p, k]``, was collapsed from the time steps ``t0[p, k] .. t1[p, k]`` and has the log-prob ``peak[p, k]``, the largest of its class
     over those steps; ``lens[p]`` characters.  Entries of a row from ``lens[p]`` on are not written.  ``buf`` is the one int32 buffer all five
-    are views of (``text.span_arrays``): one copy brings them to the host."""
+    are views of (``text.span_arrays``): one copy brings them to the host.  ``scores`` (R,) fp32, beam decodes only: the
+    log-mass of every row's labelling; None for the greedy decode."""
     buf: torch.Tensor
     labels: torch.Tensor  # (R,ld) int32
     t0: torch.Tensor      # (R,ld) int32
     t1: torch.Tensor      # (R,ld) int32
     peak: torch.Tensor    # (R,ld) fp32
     lens: torch.Tensor    # (R,) int32
+    scores: torch.Tensor | None = None  # (R,) fp32
 
     def arrays(self):
         return self.buf, self.labels, self.t0, self.t1, self.peak, self.lens
@@ -292,20 +301,29 @@ def _check_batches(rec_model, batches, who: str):
         raise RuntimeError(f"{who}: the model must be in eval mode (model.eval())")
 
 
-def decode_crop_spans(rec_model, batches) -> CharSpans:
+def decode_crop_spans(rec_model, batches, beam_width: int | None = None) -> CharSpans:
     """Eval forward of the recogniser per batch, as ``recognize_crops``, with the decode that keeps the spans: the chunks write their rows
     into one set of arrays whose pitch is the longest chunk's number of time steps.  Every forward is queued before the first decode (the
-    pitch is known once the last forward has its shape); no synchronisation, nothing is copied."""
+    pitch is known once the last forward has its shape); no synchronisation, nothing is copied.  ``beam_width``: None = the greedy decode;
+    a width = prefix beam search and forced alignment (``text.beam_decode_spans_async``) into the same arrays, with
+    ``scores`` set."""
     _check_batches(rec_model, batches, "decode_crop_spans")
+    if beam_width is not None:
+        _check_beam_width("decode_crop_spans", beam_width)
     imgs, image_widths, _ = batches
     with torch.inference_mode():
         lps = [rec_model(img) for img in imgs]
     rows = sum(lp.shape[1] for lp in lps)
     dev = lps[0].device if lps else torch.device("cuda", torch.cuda.current_device())
     spans = CharSpans(*span_arrays(rows, max([lp.shape[0] for lp in lps], default=1), dev))
+    if beam_width is not None:
+        spans.scores = torch.empty(rows, dtype=torch.float32, device=dev)
     row = 0
     for lp, iw in zip(lps, image_widths):
-        greedy_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), spans.arrays(), row)
+        if beam_width is None:
+            greedy_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), spans.arrays(), row)
+        else:
+            beam_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), beam_width, spans.arrays(), row, spans.scores)
         row += lp.shape[1]
     return spans
 
@@ -354,27 +372,51 @@ def word_chars(lines: TextLines, plan: CropPlan, spans: CharSpans, boxes: CharBo
 def chars_to_host(spans: CharSpans, boxes: CharBoxes, alphabet=DEFAULT_ALPHABET, ranges: torch.Tensor | None = None):
     """The characters on the host, in the rows' (width-sorted) order: ``(texts, chars, ranges)`` with ``chars[p] = {"char_quads": [4x2 lists],
     "char_log_probs": [floats]}``, one entry per character of ``texts[p]``, and ``ranges`` the (N,2) result of ``word_chars`` as a list (None
-    without it).  Three copies queued on the current stream and ONE wait for all of them."""
+    without it).  Spans of a beam decode (``spans.scores``) add ``"log_prob"`` to every ``chars[p]``.  The copies are queued on the current
+    stream and there is ONE wait for all of them."""
     alphabet = list(alphabet)
     sp_h, cq_h = _to_host_async(spans.buf), _to_host_async(boxes.quads)
     rg_h = None if ranges is None else _to_host_async(ranges)
+    sc_h = None if spans.scores is None else _to_host_async(spans.scores)
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(spans.buf.device))
     done.synchronize()
     rows, ld = spans.labels.shape
     labels, peak = sp_h[:rows * ld].view(rows, ld), sp_h[3 * rows * ld:4 * rows * ld].view(rows, ld).view(torch.float32)
-    lens = sp_h[4 * rows * ld:].tolist()
+    lens = [max(n, 0) for n in sp_h[4 * rows * ld:].tolist()]  # (-1: a beam row without any labelling of finite mass)
     texts = [decode_text(labels[p, :n], alphabet) for p, n in enumerate(lens)]
     chars = [{"char_quads": cq_h[p, :n].tolist(), "char_log_probs": peak[p, :n].tolist()} for p, n in enumerate(lens)]
+    if sc_h is not None:  # a beam decode: the labelling's log-mass travels with the characters
+        for d, sc in zip(chars, sc_h.tolist()):
+            d["log_prob"] = sc
     return texts, chars, None if rg_h is None else rg_h.tolist()
 
 
-def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = False):
+def _beam_texts_to_host(spans: CharSpans, alphabet):
+    """texts and scores of a beam decode's span rows on the host, in the rows' order: two copies and ONE wait, for the event behind them"""
+    sp_h, sc_h = _to_host_async(spans.buf), _to_host_async(spans.scores)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(spans.buf.device))
+    done.synchronize()
+    rows, ld = spans.labels.shape
+    lens, alphabet = [max(n, 0) for n in sp_h[4 * rows * ld:].tolist()], list(alphabet)  # (-1: a row without any labelling of finite mass)
+    texts = [decode_text(row[:n], alphabet) for row, n in zip(sp_h[:rows * ld].view(rows, ld), lens)]
+    return texts, sc_h.tolist()
+
+
+def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = False, beam_width: int | None = None):
     """Eval forward of the recogniser per batch with ``input_lengths = image_width // 4`` (as ``train_rec.test``) and the device greedy
     decode.  ``batches`` is what ``crops_to_batches`` returned: ``(batch tensors, image widths, perm)``.  Returns the strings in quad order.
     Every chunk's forward and decode are queued before the first label copy is waited for.  ``chars=True``: ``(strings in quad order,
     CharSpans)`` -- the same strings from the decode that keeps every character's time steps and log-prob (``decode_crop_spans``), whose
-    device arrays ``char_boxes`` and ``word_chars`` take; one wait, for the one copy of the span buffer."""
+    device arrays ``char_boxes`` and ``word_chars`` take; one wait, for the one copy of the span buffer.  ``beam_width``: the
+    strings of prefix beam search instead -- ``(strings, log-probs of the strings)``, with ``chars=True`` ``(strings, CharSpans, log-probs)``;
+    both forms decode into one span buffer and wait once."""
+    if beam_width is not None:
+        spans = decode_crop_spans(rec_model, batches, beam_width)
+        texts, scores = _beam_texts_to_host(spans, alphabet)
+        texts, scores = [texts[p] for p in batches[2]], [scores[p] for p in batches[2]]
+        return (texts, spans, scores) if chars else (texts, scores)
     if chars:
         spans = decode_crop_spans(rec_model, batches)
         sp_h = _to_host_async(spans.buf)
@@ -398,7 +440,7 @@ def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool =
 
 
 def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLines | None = None, n_lines: int = 0, order: ReadingOrder | None = None,
-                line_page_offs: list | None = None, chars_plan: CropPlan | None = None) -> list[dict]:
+                line_page_offs: list | None = None, chars_plan: CropPlan | None = None, beam_width: int | None = None) -> list[dict]:
     """The tail of ``ocr_page``, ``read_lines`` and ``ocr_pages``: ``recognize_crops`` on ``batches``, then the flat result list -- one
     ``{"quad", "text"}`` per word, or with ``lines`` one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  With ``order``
     the list is in reading order -- position k holds line ``order.line_order[k]`` -- and every dict has ``"block"``, counted from 0 on every
@@ -406,16 +448,20 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
     travel to the host ahead of the recogniser on the same stream: they have arrived when the labels have (no wait of their own).
     ``chars_plan`` (the plan the crops were cut with; ``chars=True`` of the callers): every dict also has ``"char_quads"`` and
     ``"char_log_probs"``, line dicts ``"word_chars"`` and ``"word_texts"`` too.  The boxes and word ranges are queued behind the
-    decodes and copied with the labels: still one wait here."""
+    decodes and copied with the labels: still one wait here.  ``beam_width``: the texts of prefix beam search and
+    ``"log_prob"`` in every dict; still one wait."""
     words_h = _to_host_async(words)
     if lines is not None:
         lq_h, order_h, offs_h = (_to_host_async(t) for t in (lines.quads, lines.word_order, lines.line_offsets))
     if order is not None:
         ro_h, nb_h = _to_host_async(order.line_order), _to_host_async(order.new_block)
-    if chars_plan is None:
+    scores = None
+    if chars_plan is None and beam_width is not None:
+        texts, scores = recognize_crops(rec_model, batches, alphabet, beam_width=beam_width)
+    elif chars_plan is None:
         texts = recognize_crops(rec_model, batches, alphabet)
     else:
-        spans = decode_crop_spans(rec_model, batches)
+        spans = decode_crop_spans(rec_model, batches, beam_width)
         boxes = char_boxes(words if lines is None else lines.quads, chars_plan, spans)
         ranges = None if lines is None else word_chars(lines, chars_plan, spans, boxes, alphabet)
         texts, chars, ranges = chars_to_host(spans, boxes, alphabet, ranges)
@@ -425,9 +471,14 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
     if lines is None:
         if chars_plan is not None:
             return [{"quad": q, "text": t, **c} for q, t, c in zip(wl, texts, chars)]
+        if scores is not None:
+            return [{"quad": q, "text": t, "log_prob": sc} for q, t, sc in zip(wl, texts, scores)]
         return [{"quad": q, "text": t} for q, t in zip(wl, texts)]
     word_order, offs, lq = order_h.tolist(), offs_h[:n_lines + 1].tolist(), lq_h[:n_lines].tolist()
     out = [{"quad": lq[l], "text": texts[l], "words": [wl[i] for i in word_order[offs[l]:offs[l + 1]]]} for l in range(n_lines)]
+    if scores is not None:
+        for l, d in enumerate(out):
+            d["log_prob"] = scores[l]
     if chars_plan is not None:
         for l, d in enumerate(out):
             rg = [ranges[i] for i in word_order[offs[l]:offs[l + 1]]]
@@ -445,18 +496,22 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
 
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
-             output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, chars: bool = False) -> list[dict]:
+             output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, chars: bool = False,
+             beam_width: int | None = None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
     A page without components returns ``[]`` without launching the recogniser.  ``chars=True``: every dict also has ``"char_quads"``, the
     rectangle of every character of ``"text"`` on the page, and ``"char_log_probs"``, the recogniser's log-prob of each; the
-    same three waits."""
+    same three waits.
+    ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
+    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits."""
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
     quads = det["quads"]
     plan = crop_plan(quads, output_height)
     packed = rectify_crops(page_u8, quads, plan)
-    return _read_crops(rec_model, crops_to_batches(packed, plan, max_batch, width_unit), alphabet, quads, chars_plan=plan if chars else None)
+    return _read_crops(rec_model, crops_to_batches(packed, plan, max_batch, width_unit), alphabet, quads, chars_plan=plan if chars else None,
+                       beam_width=beam_width)
 
 
 # ------------------------------------------------------------------ words -> lines -------------------------------------------------------
@@ -592,23 +647,26 @@ def page_text(result: list[dict]) -> str:
 
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
                alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0,
-               chars: bool = False) -> list[dict]:
+               chars: bool = False, beam_width: int | None = None) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
     ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
     ``reading_order=True`` is queued behind the line stage and changes nothing about the crops (lines are cropped in line order).
-    ``chars=True``: the characters' quads, log-probs and word ranges as ``ocr_lines`` describes them, queued behind the decodes; the same waits."""
+    ``chars=True``: the characters' quads, log-probs and word ranges as ``ocr_lines`` describes them, queued behind the decodes; the same waits.
+    ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
+    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits."""
     lines = find_lines(quads, None, max_gap, min_cos)
     order = _order_lines(lines, block_gap) if reading_order else None
     plan = crop_plan(lines.quads, output_height, lines.n_lines)
     packed = rectify_crops(page_u8, lines.quads, plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order, chars_plan=plan if chars else None)
+    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order, chars_plan=plan if chars else None, beam_width=beam_width)
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
-              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False) -> list[dict]:
+              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
+              beam_width: int | None = None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
@@ -616,11 +674,13 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thres
     where line order interleaves the columns), each with ``"block"``, the number of its text block counted from 0; still three waits.
     ``chars=True``: every dict keeps those keys and gains ``"char_quads"`` (one 4x2 list per character of ``"text"``: where it
     sits on the page), ``"char_log_probs"`` (the recogniser's log-prob of each), ``"word_chars"`` (parallel to ``"words"``: the ``[first, end]``
-    of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits."""
+    of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits.  ``beam_width``: as in
+    ``read_lines``."""
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
-    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars)
+    return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars,
+                      beam_width)
 
 
 # ------------------------------------------------------------------ page batches ---------------------------------------------------------
@@ -813,7 +873,8 @@ def split_by_page(items: list, offs: list) -> list[list]:
 
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
-              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False) -> list[list[dict]]:
+              min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
+              beam_width: int | None = None) -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
@@ -821,7 +882,9 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
     for the batch: the word offsets, the plan's totals (the line count and ``line_page_offs`` travel with them) and the labels.  A page
     without words yields ``[]``; a batch without words returns without launching the recogniser; ``pages == []`` launches nothing.
     ``reading_order=True`` (with ``lines``): every page's list in reading order with ``"block"``, as ``ocr_lines`` returns it; the same waits.
-    ``chars=True``: the character keys of ``ocr_lines`` / ``ocr_page`` in every dict; the same waits."""
+    ``chars=True``: the character keys of ``ocr_lines`` / ``ocr_page`` in every dict; the same waits.
+    ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
+    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits."""
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
@@ -845,6 +908,6 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
         packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, words, det["page_of_word"], plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
     if not lines:
-        return split_by_page(_read_crops(rec_model, batches, alphabet, words, chars_plan=plan if chars else None), word_offs_h)
+        return split_by_page(_read_crops(rec_model, batches, alphabet, words, chars_plan=plan if chars else None, beam_width=beam_width), word_offs_h)
     n_lines, lpo = plan.host()[0], lpo_h.tolist()
-    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo, plan if chars else None), lpo)
+    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo, plan if chars else None, beam_width), lpo)

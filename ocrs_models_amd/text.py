@@ -7,6 +7,9 @@
 * ``DeviceRecognitionAccuracyStats``, ``edit_distance_device``                       the same stats with nothing left on the host
   (``ocrs_ctc_cer_update`` / ``ocrs_edit_distance``, csrc/rec_cer.hip): edit distances and both sums on the GPU, one host sync per read.
 * ``transform_image``                                                              (datasets/util.py:27-35)
+* ``beam_decode_spans``, ``ctc_align_spans``                                         CTC prefix beam search next to the greedy rule of
+  datasets/util.py:147-177, and the forced alignment that gives its labelling spans (``ocrs_ctc_beam_decode`` / ``ocrs_ctc_align_spans``,
+  csrc/ctc_beam.hip)
 """
 from __future__ import annotations
 
@@ -131,7 +134,7 @@ class _DecodeSpans:
         self.event.synchronize()
         N, ld = self.N, self.ld
         part = [self.host[k * N * ld:(k + 1) * N * ld].view(N, ld) for k in range(4)]
-        lens = self.host[4 * N * ld:].tolist()
+        lens = [max(n, 0) for n in self.host[4 * N * ld:].tolist()]  # (-1: a beam row without any labelling of finite mass)
         labels, t0, t1, peak = part[0].tolist(), part[1].tolist(), part[2].tolist(), part[3].view(torch.float32).tolist()
         return [{"labels": labels[i][:n], "t0": t0[i][:n], "t1": t1[i][:n], "peak": peak[i][:n]} for i, n in enumerate(lens)]
 
@@ -180,6 +183,117 @@ def greedy_decode_spans_async(log_probs: torch.Tensor, input_lengths, out=None, 
 def greedy_decode_spans(log_probs: torch.Tensor, input_lengths):
     """(T,N,C) log-probs on the GPU -> list of N dicts ``labels``, ``t0``, ``t1``, ``peak``, one entry per character (one D2H copy)."""
     return greedy_decode_spans_async(log_probs, input_lengths).result()
+
+
+BEAM_MAX_WIDTH, BEAM_MAX_CLASSES = 64, 256  # what ocrs_ctc_beam_decode supports (csrc/ctc_beam.hip)
+
+
+class _BeamSpans(_DecodeSpans):
+    """Result handle of beam_decode_spans_async: the span arrays and the scores on the device, and on their way into pinned host memory."""
+
+    def __init__(self, arrays, host, event, N, ld, scores, scores_host):
+        super().__init__(arrays, host, event, N, ld, None)
+        self.scores, self.scores_host = scores, scores_host
+
+    def result(self):
+        """list of N dicts ``labels``, ``t0``, ``t1``, ``peak`` as ``greedy_decode_spans`` returns them, plus ``score``, the log-mass of the
+        labelling (waits for the copies only)"""
+        out = super().result()
+        for d, s in zip(out, self.scores_host.tolist()):
+            d["score"] = s
+        return out
+
+
+def _span_args(who: str, log_probs, input_lengths):
+    """the argument checks shared by the decoders that fill span arrays -> (lp, il, T, N, C, dev)"""
+    if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or not log_probs.is_cuda:
+        raise RuntimeError(f"{who}: expected (T,N,C) log-probs on the GPU (no CPU path)")
+    lp = log_probs.contiguous().float()
+    T, N, C = lp.shape
+    if T < 1 or C < 1:
+        raise RuntimeError(f"{who}: expected at least one time step and one class")
+    dev = lp.device
+    il = torch.as_tensor(input_lengths, dtype=torch.int64)
+    if not il.is_cuda:
+        il = il.pin_memory().to(dev, non_blocking=True) if il.numel() else il.to(dev)
+    il = il.contiguous()
+    if il.numel() != N:
+        raise RuntimeError(f"{who}: {il.numel()} input lengths for {N} samples")
+    return lp, il, T, N, C, dev
+
+
+def _check_beam_width(who: str, beam_width):
+    if isinstance(beam_width, bool) or not isinstance(beam_width, int) or not 1 <= beam_width <= BEAM_MAX_WIDTH:
+        raise RuntimeError(f"{who}: beam_width must be an integer in 1..{BEAM_MAX_WIDTH}, got {beam_width!r}")
+
+
+def _align_into(lp, il, T, N, C, row0, ld, labels, lens, t0, t1, peak):
+    """one ocrs_ctc_align_spans launch over rows row0 .. row0 + N of the span arrays"""
+    ws = torch.empty(lib().ctc_align_ws_bytes(T, N, min(ld, T)), dtype=torch.uint8, device=lp.device)
+    lib().ctc_align_spans(ptr(lp), ptr(il), T, N, C, int(row0), ld, ptr(labels), ptr(lens), ptr(t0), ptr(t1), ptr(peak), ptr(ws), ws.numel())
+
+
+def beam_decode_spans_async(log_probs: torch.Tensor, input_lengths, beam_width: int, out=None, row0: int = 0, scores: torch.Tensor | None = None):
+    """``greedy_decode_spans_async`` for the best labelling under CTC prefix beam search with ``beam_width`` prefixes (DESIGN.md §18,
+    ``ocrs_ctc_beam_decode``) and the spans of its forced alignment (``ocrs_ctc_align_spans``): the same span arrays, the same ``out`` /
+    ``row0`` contract.  ``scores``: float32 device tensor with one entry per row of ``out`` that receives the labelling's log-mass at
+    ``row0 + n`` (required with ``out``; without it a new one is made and copied with the arrays).  One beam launch and one align launch on
+    the current stream."""
+    who = "beam_decode_spans"
+    _check_beam_width(who, beam_width)
+    if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3:
+        raise RuntimeError(f"{who}: expected (T,N,C) log-probs on the GPU (no CPU path)")
+    if not 2 <= log_probs.shape[2] <= BEAM_MAX_CLASSES:
+        raise RuntimeError(f"{who}: {log_probs.shape[2]} classes, supported are 2..{BEAM_MAX_CLASSES}")
+    lp, il, T, N, C, dev = _span_args(who, log_probs, input_lengths)
+    own = out is None
+    if own:
+        out, row0 = span_arrays(N, T, dev), 0
+        scores = torch.empty(N, dtype=torch.float32, device=dev)
+    _, labels, t0, t1, peak, lens = out
+    rows, ld = labels.shape
+    if ld < T or row0 < 0 or row0 + N > rows or lens.numel() != rows:
+        raise RuntimeError(f"{who}: rows {row0}..{row0 + N} of pitch {T} do not fit span arrays of {rows} rows of pitch {ld}")
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == rows):
+        raise RuntimeError(f"{who}: scores must be a contiguous float32 device tensor with one entry per row ({rows})")
+    if N:
+        ws = torch.empty(lib().ctc_beam_ws_bytes(T, N, beam_width), dtype=torch.uint8, device=dev)
+        lib().ctc_beam_decode(ptr(lp), ptr(il), T, N, C, beam_width, int(row0), ld, ptr(labels), ptr(lens), ptr(scores), ptr(ws), ws.numel())
+        _align_into(lp, il, T, N, C, row0, ld, labels, lens, t0, t1, peak)
+    if not own:
+        return None
+    host = torch.empty(out[0].numel(), dtype=torch.int32, pin_memory=True)
+    host.copy_(out[0], non_blocking=True)
+    scores_host = torch.empty(N, dtype=torch.float32, pin_memory=True)
+    scores_host.copy_(scores, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dev))
+    return _BeamSpans(out, host, ev, N, T, scores, scores_host)
+
+
+def beam_decode_spans(log_probs: torch.Tensor, input_lengths, beam_width: int):
+    """(T,N,C) log-probs on the GPU -> list of N dicts ``labels``, ``t0``, ``t1``, ``peak`` (one entry per character) and ``score``."""
+    return beam_decode_spans_async(log_probs, input_lengths, beam_width).result()
+
+
+def ctc_align_spans(log_probs: torch.Tensor, input_lengths, labels, label_lengths):
+    """Forced alignment of given labellings (``ocrs_ctc_align_spans``): ``labels`` (N, L) label rows and ``label_lengths``
+    (N,) -> the tuple of ``span_arrays`` (pitch max(T, L)) with ``t0`` / ``t1`` / ``peak`` of every character on the best alignment path;
+    ``lens`` is -1 where the labelling has no alignment of finite score.  One launch, no synchronisation."""
+    who = "ctc_align_spans"
+    lp, il, T, N, C, dev = _span_args(who, log_probs, input_lengths)
+    lab = _labels_to_device(dev, labels)
+    ll, = _lengths_to_device(dev, label_lengths)
+    if lab.shape[0] != N or ll.numel() != N:
+        raise RuntimeError(f"{who}: {lab.shape[0]} label rows and {ll.numel()} label lengths for {N} samples")
+    L = lab.shape[1]
+    out = span_arrays(N, max(T, L), dev)
+    _, o_labels, t0, t1, peak, lens = out
+    o_labels[:, :L] = lab
+    lens.copy_(ll.clamp(max=L).to(torch.int32))
+    if N:
+        _align_into(lp, il, T, N, C, 0, max(T, L), o_labels, lens, t0, t1, peak)
+    return out
 
 
 def levenshtein(a, b) -> int:
