@@ -305,7 +305,9 @@ int ocrs_conv3x3_wgrad(const void* dz, int Cout, const void* x, int Cin, float* 
 int ocrs_conv0_fwd(const float* img, const float* w, const float* bias, void* out, int N, int H, int W, int dtype, hipStream_t st);
 int ocrs_conv0_bwd(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype,
                    hipStream_t st);
-/* BatchNorm2d + ReLU + MaxPool2d((2,2)|(2,1)) (models.py:197-199, 214-216, 231-233) forward and the pieces of its backward. */
+/* BatchNorm2d + ReLU + MaxPool2d((2,2)|(2,1)) (models.py:197-199, 214-216, 231-233) forward and the pieces of its backward.
+ * Windows (PH, PW) = (2,2), (2,1) or (1,1) (no pooling), floor mode: a last row / column that H % PH or W % PW leaves over is in no window
+ * (ocrs_dz_apply gives its pixels coefB*z + coefC).  C / 8 must be a power of two <= 256.  Anything else returns 1 and launches nothing. */
 int ocrs_act_pool_fwd(const void* z, const float* tr, void* out, int C, int N, int H, int W, int PH, int PW, int dtype, hipStream_t st);
 int ocrs_rec_bn_reduce(const void* g, const void* z, const float* bn, const float* saved, double* gsum, int C, int N, int H, int W, int PH, int PW,
                        int dtype, hipStream_t st);

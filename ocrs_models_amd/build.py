@@ -36,6 +36,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers.append(os.path.join(os.path.dirname(HERE), "include", "ocrs_hip.h"))  # common.h includes the ABI header: every definition is checked against it
     jobs = []
     for src in sources():
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src + ".o")

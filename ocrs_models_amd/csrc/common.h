@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/ocrs_hip.h"  // every definition of an ocrs_* entry point is compiled against its declaration
 
 #define OCRS_OK 0
 #include <hip/hip_ext.h>
@@ -405,6 +406,12 @@ struct DevOnce {
     bool need() const { return !(mask.load(std::memory_order_relaxed) & bit()); }
     void done() { mask.fetch_or(bit(), std::memory_order_relaxed); }
 };
+// The ABI's dtype (0 = fp32, 1 = bf16) as a type: f(T{}) with T = float or bf16, for launchers whose two branches differ in nothing else
+//   with_dtype(dtype, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(k<T>, ..., (const T*)x, ...); });
+template <class F>
+static inline auto with_dtype(int dtype, F&& f) {
+    return dtype == 1 ? f(bf16{}) : f(float{});
+}
 // Per-launch timestamps from the dispatch packet (csrc/prof.hip): OCRS_LAUNCH_T == hipLaunchKernelGGL unless ocrs_prof_enable(1)
 struct OcrsProf {
     int on, used, cap;

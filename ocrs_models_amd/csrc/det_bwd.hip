@@ -1149,7 +1149,7 @@ __global__ __launch_bounds__(256) void k_convt_dgrad(const T* __restrict__ g, co
     }
 }
 
-// ConvTranspose2d wgrad (dW[c,o,ky,kx] = sum_{n,i,j} x~[n,i,j,c] * g[n,2i+ky,2j+kx,o]) runs on the generic k_wgrad_gather (rec_conv.hip)
+// ConvTranspose2d wgrad (dW[c,o,ky,kx] = sum_{n,i,j} x~[n,i,j,c] * g[n,2i+ky,2j+kx,o]) runs on the generic k_wgrad_gather (rec_wgrad.hip)
 // with A = x~ (load transform applied), B = g gathered at stride 2.
 
 // per-channel sum over pixels (ConvTranspose2d bias gradient)
@@ -1363,7 +1363,7 @@ struct DeferState {
     long cap = 0, used = 0;
     int nblocks = 0;
     RedJobs jobs;
-    // workspace for per-block partials of launches whose entry points take none (the CRNN's bias / first-layer sums: rec_conv.hip, rec_conv0.hip,
+    // workspace for per-block partials of launches whose entry points take none (the CRNN's bias / first-layer sums: rec_pool.hip, rec_conv0.hip,
     // rec_gru_seq.hip): a per-device buffer (allocated on that device at first use), bump-allocated between _begin and _flush; null outside that
     // window, when it is used up, or when the allocation is refused (e.g. inside a stream capture: callers then take their atomic path)
     float* ws = nullptr;

@@ -24,7 +24,6 @@
 // (numpy's dot / 2-term matmul go through BLAS, whose kernels use fma) the same fma is written out, and np.hypot is glibc's correction
 // kernel.  Integer work (labelling, hull construction) is exact.
 #include "common.h"
-#include "../../include/ocrs_hip.h"
 
 #pragma clang fp contract(off)
 

@@ -14,7 +14,6 @@
 // A single page is B = 1 with line_page_offs == NULL: its lines are 0 .. L.  All decision arithmetic is fp32 with one rounding per operation
 // (no fused multiply-add), so the restatement follows it operation by operation.  No atomics at all.
 #include "common.h"
-#include "../../include/ocrs_hip.h"
 
 #pragma clang fp contract(off)
 

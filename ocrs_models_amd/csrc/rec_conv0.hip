@@ -1,5 +1,8 @@
-// Backward of the CRNN's fused first layer, Conv2d(1, 32, 3, padding=1) + ReLU + MaxPool2d(2) (ocrs_models/models.py:181-187), on the matrix cores
-// (round 5; bf16 gradient, gfx950).  Same contract as k_conv0_bwd (rec_conv.hip): dW [32][9], db [32] accumulated from img [N][H][W] fp32 and the
+// The CRNN's fused first layer, Conv2d(1, 32, 3, padding=1) + ReLU + MaxPool2d(2) (ocrs_models/models.py:181-187), gfx950:
+//   k_conv0_fwd      forward, one thread per (pooled pixel, 8 output channels)
+//   k_conv0_bwd      backward on the VALU with window recompute (fp32 gradients, odd sizes)
+//   k_conv0_bwd_mm   backward on the matrix cores (round 5; bf16 gradient, even H and W)
+// Contract of both backward kernels: dW [32][9], db [32] accumulated from img [N][H][W] fp32 and the
 // gradient g [N][H/2][W/2][32] w.r.t. the pooled output; nothing of the forward is stored, the layer is recomputed.
 //
 // k_conv0_bwd does that on the VALU: per (pooled pixel, channel) 36 FMAs of recompute, a 4-way arg-max, 27 selects to pick the winner's patch and
@@ -13,7 +16,7 @@
 //       written to wave-private LDS in their natural [K][column] order and read back through the LDS transpose read (lds_tr8).
 // A wave owns steps of 32 consecutive pooled pixels of one output row; its LDS (image rows, a, patches) is private: LDS operations of one wave
 // execute in order, so there is no workgroup barrier in the loop.  The next step's image rows and gradient vectors are register-prefetched.
-#include "det_common.h"
+#include "rec_internal.h"
 
 namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -227,8 +230,135 @@ __global__ __launch_bounds__(256, 3) void k_conv0_bwd_mm(const float* __restrict
     }
 }
 
-// launcher for ocrs_conv0_bwd (rec_conv.hip): 1 if this kernel took the call (bf16 gradient, even H and W)
-extern "C" int conv0_bwd_mm_launch(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype, hipStream_t st) {
+// ---------------------------------------------------------------------------------------------------------------------
+// first layer: Conv2d(1,32,3,pad 1,bias) + ReLU + MaxPool2d(2) (models.py:180-187).  One thread per (pooled pixel, 8 out channels).
+template <class T>
+__global__ __launch_bounds__(256) void k_conv0_fwd(const float* __restrict__ img, const float* __restrict__ w /*[32][9]*/,
+                                                   const float* __restrict__ bias, T* __restrict__ out /*[N][H/2][W/2][32]*/, int N, int H, int W) {
+    const int Hp = H >> 1, Wp = W >> 1;
+    // a thread keeps its group of 8 output channels (the grid's thread count is a multiple of 4): their 72 weights + 8 biases live in registers
+    // (re-loading them per pixel made 20 of the kernel's 37 load instructions per store)
+    const long gtid = (long)blockIdx.x * 256 + threadIdx.x, nthr = (long)gridDim.x * 256;
+    const int c0 = (int)(gtid & 3) * 8;
+    float wk[8][9], bs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        bs[i] = bias[c0 + i];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[i][k] = w[(c0 + i) * 9 + k];
+    }
+    const long Pp = (long)N * Hp * Wp;
+    for (long pp = gtid >> 2; pp < Pp; pp += nthr >> 2) {
+        const PixIdx q = decode_pixel(pp, Hp, Wp);
+        float patch[4][4];
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 4; ++dx) {
+                const int h = 2 * q.h + dy - 1, ww = 2 * q.w + dx - 1;
+                const bool ok = h >= 0 && h < H && ww >= 0 && ww < W;
+                const float v = img[ok ? ((long)q.n * H + h) * W + ww : 0];  // (unconditional load, selected address)
+                patch[dy][dx] = ok ? v : 0.f;
+            }
+        float m[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float best = 0.f;  // ReLU floor: max(relu(a), relu(b), ...) = max(0, a, b, ...)
+#pragma unroll
+            for (int oy = 0; oy < 2; ++oy)
+#pragma unroll
+                for (int ox = 0; ox < 2; ++ox) {
+                    float s = bs[i];
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) s = fmaf(wk[i][k], patch[oy + k / 3][ox + k % 3], s);
+                    best = fmaxf(best, s);
+                }
+            m[i] = best;
+        }
+        store8(out + pp * 32 + c0, m);
+    }
+}
+
+// backward of the fused first layer: dW [32][9], db [32] accumulated.  g = gradient w.r.t. the pooled output [N][H/2][W/2][32].
+template <class T>
+__global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   const T* __restrict__ g, float* __restrict__ dW, float* __restrict__ db, int N, int H, int W) {
+    __shared__ float s_acc[32 * 10];
+    for (int i = threadIdx.x; i < 320; i += 256) s_acc[i] = 0.f;
+    __syncthreads();
+    const int Hp = H >> 1, Wp = W >> 1;
+    const long gtid = (long)blockIdx.x * 256 + threadIdx.x, nthr = (long)gridDim.x * 256;
+    const int c0 = (int)(gtid & 3) * 8;
+    float acc[8][10];
+    float wk[8][9], bs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        bs[i] = bias[c0 + i];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[i][k] = w[(c0 + i) * 9 + k];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) acc[i][k] = 0.f;
+    }
+    const long Pp = (long)N * Hp * Wp;
+    for (long pp = gtid >> 2; pp < Pp; pp += nthr >> 2) {
+        const PixIdx q = decode_pixel(pp, Hp, Wp);
+        float patch[4][4];
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 4; ++dx) {
+                const int h = 2 * q.h + dy - 1, ww = 2 * q.w + dx - 1;
+                patch[dy][dx] = (h >= 0 && h < H && ww >= 0 && ww < W) ? img[((long)q.n * H + h) * W + ww] : 0.f;
+            }
+        float gv[8];
+        load8(g + pp * 32 + c0, gv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float best = 0.f;
+            int bo = -1;  // -1: every candidate <= 0 -> ReLU kills the gradient
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                float s = bs[i];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) s = fmaf(wk[i][k], patch[(o >> 1) + k / 3][(o & 1) + k % 3], s);
+                if (s > best) {
+                    best = s;
+                    bo = o;
+                }
+            }
+            const float gi = bo >= 0 ? gv[i] : 0.f;
+            const int oy = bo >= 0 ? (bo >> 1) : 0, ox = bo >= 0 ? (bo & 1) : 0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                // select the patch element of the winning position without dynamic register indexing
+                float pv = patch[k / 3][k % 3];
+                pv = (oy == 0 && ox == 1) ? patch[k / 3][1 + k % 3] : pv;
+                pv = (oy == 1 && ox == 0) ? patch[1 + k / 3][k % 3] : pv;
+                pv = (oy == 1 && ox == 1) ? patch[1 + k / 3][1 + k % 3] : pv;
+                acc[i][k] = fmaf(gi, pv, acc[i][k]);
+            }
+            acc[i][9] += gi;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int k = 0; k < 10; ++k) {
+            const float v = lane_class_sum<4>(acc[i][k]);
+            if ((threadIdx.x & 63) < 4) atomicAdd(&s_acc[(c0 + i) * 10 + k], v);
+        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 320; i += 256) {
+        const int c = i / 10, k = i - c * 10;
+        if (k < 9)
+            atomicAdd(&dW[c * 9 + k], s_acc[i]);
+        else
+            atomicAdd(&db[c], s_acc[i]);
+    }
+}
+
+// k_conv0_bwd_mm's launcher for ocrs_conv0_bwd: 1 if this kernel took the call (bf16 gradient, even H and W)
+static int conv0_bwd_mm_launch(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype, hipStream_t st) {
     if (dtype != 1 || (H & 1) || (W & 1) || H < 2 || W < 2 || (long)N * (H / 2) * (((W / 2) + 31) / 32) >= (1L << 30)) return 0;
     static DevOnce attr;
     if (attr.need()) {
@@ -244,3 +374,34 @@ extern "C" int conv0_bwd_mm_launch(const float* img, const float* w, const float
     hipLaunchKernelGGL(k_conv0_bwd_mm, dim3((int)grid), dim3(256), C0_SMEM, st, img, w, bias, (const bf16*)g, dW, db, N, H, W, ws);
     return 1;
 }
+
+extern "C" {
+
+// Conv2d(1,32,3,p1)+ReLU+MaxPool2d(2) fused (models.py:180-187): img fp32 (N,1,H,W) -> out [N][H/2][W/2][32].
+int ocrs_conv0_fwd(const float* img, const float* w, const float* bias, void* out, int N, int H, int W, int dtype, hipStream_t st) {
+    OCRS_CHECK_ARG(img && w && bias && out && H >= 2 && W >= 2);  // (odd sizes: floor-mode pooling, the last row / column is in no window)
+    const int grid = ew_grid((long)N * (H / 2) * (W / 2) * 4);
+    if (dtype == 1)
+        hipLaunchKernelGGL(k_conv0_fwd<bf16>, dim3(grid), dim3(256), 0, st, img, w, bias, (bf16*)out, N, H, W);
+    else
+        hipLaunchKernelGGL(k_conv0_fwd<float>, dim3(grid), dim3(256), 0, st, img, w, bias, (float*)out, N, H, W);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+int ocrs_conv0_bwd(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype,
+                   hipStream_t st) {
+    OCRS_CHECK_ARG(img && w && bias && g && dW && db);
+    if (conv0_bwd_mm_launch(img, w, bias, g, dW, db, N, H, W, dtype, st)) {
+        OCRS_LAUNCH_CHECK();
+        return OCRS_OK;
+    }
+    const int grid = ew_grid((long)N * (H / 2) * (W / 2) * 4);
+    if (dtype == 1)
+        hipLaunchKernelGGL(k_conv0_bwd<bf16>, dim3(grid), dim3(256), 0, st, img, w, bias, (const bf16*)g, dW, db, N, H, W);
+    else
+        hipLaunchKernelGGL(k_conv0_bwd<float>, dim3(grid), dim3(256), 0, st, img, w, bias, (const float*)g, dW, db, N, H, W);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 //   LDS buffers at the end of step g + 1 -- two steps of MFMA work cover the L2 / HBM round trip; ONE barrier per step.
 // Tile = 16 rows x 16 pixels: one image at H >= 16, or two images x 8 rows (H = 8) -- a 16-pixel row is one MFMA N tile.
 // Waves: 2 (M halves) x 2 (row halves).  Two blocks per CU (73 KB of LDS, <= 256 registers).
-#include "det_common.h"
+#include "rec_internal.h"
 
 namespace {
 constexpr int C2_UNROLL = 1;  // tap loop unroll factor

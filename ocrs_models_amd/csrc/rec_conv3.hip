@@ -26,7 +26,7 @@
 //   * the epilogue regroups an N tile through 2 KB of LDS per wave and stores 16 bytes per lane (the CUs reach their epilogues together: the
 //     layer's output is written in bursts, and 8-byte pieces of 32-byte segments made those bursts 40 % longer).
 // 2 x 2 kernels and padding 0 / 1 (the CRNN's last conv and its dgrad) run through the same code with 4 steps per chunk.
-#include "det_common.h"
+#include "rec_internal.h"
 
 namespace {
 constexpr int R3_HPMAX = 1024;   // staged halo pixels per plane (<= 64 KB per 32-channel chunk, two chunks)

@@ -13,7 +13,7 @@
 //     ONE barrier per chunk at tap 8); B fragments are refilled in place one step ahead; the epilogue regroups a tile through LDS and
 //     stores 16 bytes per lane.
 // 8 waves = 8 pixel groups (WM = 1): a wave holds MH x NTW accumulator tiles (4 x 4 or 2 x 4).
-#include "det_common.h"
+#include "rec_internal.h"
 
 namespace {
 __device__ uint4 g4_zero64[4];  // 64 zero bytes: source of the padding lanes' DMA

@@ -24,8 +24,7 @@
 //     z * dh carry of the backward stay in registers.
 // EXACT = true: v_mfma_f32_16x16x4_f32 (the reference's fp32 arithmetic); false: split-bf16 x3 (hi*hi + hi*lo + lo*hi on the bf16 MFMA, fp32
 // accumulation: fp32-class, ~2^-17 relative per product, 5x fewer MFMA cycles) -- the same switch as the projection GEMMs (OCRS_GRU_X3).
-#include "common.h"
-float* rec_defer_partials(int nb, int n, float* out);  // rec_conv.hip (deferred, fixed-order second stage: det_common.h)
+#include "rec_internal.h"  // rec_defer_partials (rec_pool.hip): the deferred, fixed-order second stage of the bias sums
 
 namespace {
 constexpr int SH = 256, S3 = 768;  // hidden size, 3 gates

@@ -26,7 +26,6 @@
 // All decision arithmetic is fp32 with one rounding per operation (no fused multiply-add), so the restatement follows it operation by
 // operation.  No float atomics: the only atomic is an integer minimum whose result does not depend on the order of arrival.
 #include "common.h"
-#include "../../include/ocrs_hip.h"
 
 #pragma clang fp contract(off)
 

@@ -175,7 +175,7 @@ class _RecRun:
     def linear(self, x, ldx, K, w, ldw, km, bias, M, ldo, rows, kw=0):
         """fp32 out[rows][ldo] = x[rows][K] @ A^T (+ bias) with A[m][k] = w[m][k] (km = 0) or w[k][m] (km = 1), w's row pitch ldw; kw (0: K):
         the k extent w really has -- x's columns [kw, K) are zero.  w is the whole matrix: its shape says the same as (M, kw or K, ldw).  The one place that picks the kernel: throughput mode runs split-bf16
-        (csrc/rec_conv.hip::k_gemm_x3), on the pipelined kernel where this step's prepack pre-split the weight and the shape is taken, else
+        (csrc/rec_gemm.hip::k_gemm_x3), on the pipelined kernel where this step's prepack pre-split the weight and the shape is taken, else
         straight from the master layout; parity mode runs exact fp32 on packed fragments."""
         L = self.L
         assert (M, kw or K, ldw) == ((w.shape[1], w.shape[0]) if km else tuple(w.shape)) + (w.shape[1],)  # (the packed routes read w.shape)

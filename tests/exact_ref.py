@@ -418,7 +418,8 @@ GEMM_CASES = [(77, 128, 36, 40), (777, 1536, 512, 516)]                      # (
 GEMM_X3_CASES = [(77, 128, 36, 0, 0), (777, 1536, 512, 1, 0), (333, 64, 5, 0, 60)]  # (P, K, M, km, kw) of ocrs_gemm_x3 (and _x3p where it takes the shape)
 WGRAD_GEMM_CASES = [(4001, 768, 1536, 256, 512), (77, 100, 128, 36, 40)]  # (P, CA, ldA, CB, ldB) of ocrs_wgrad_gemm_x3
 WGRAD_GATHER_CASES = [(3, 40, 24, 7, 9, 3, 1), (1, 8, 8, 3, 3, 3, 1)]     # (N, CA, CB, H, W, K, pad) of ocrs_wgrad_gather
-POOL_PIECES_CASES = [(2, 8, 12, 64, 2, 2), (2, 9, 13, 64, 2, 2), (3, 8, 7, 128, 2, 1), (2, 7, 5, 128, 2, 1), (2, 5, 9, 128, 1, 1)]
+POOL_PIECES_CASES = [(2, 8, 12, 64, 2, 2), (2, 9, 13, 64, 2, 2), (3, 8, 7, 128, 2, 1), (2, 7, 5, 128, 2, 1), (2, 5, 9, 128, 1, 1),
+                     (2, 9, 12, 64, 2, 2), (2, 8, 13, 64, 2, 2)]  # (the last two: only a partial last row / only a partial last column)
 
 
 def seed_of(*key):

@@ -378,9 +378,9 @@ def test_conv0_bit_exact_with_tied_maxima(dev, dname, shape):
 @pytest.mark.parametrize("dname", ["fp32", "bf16"])
 @pytest.mark.parametrize("dims", X.POOL_PIECES_CASES, ids=_ids)
 def test_bn_relu_pool_pieces_bit_exact(dev, dname, dims):
-    """the five cases of test_bn_relu_pool_forward_and_backward_pieces (compile-time windows and the generic floor-mode kernels, 2x2 / 2x1 / no
-    pooling) with dyadic tr / saved / coef (one negative-scale channel): pooled output, gsum, dz and dsum EQUAL to float64, with 19-44 % of the
-    windows tied at a positive maximum."""
+    """the cases of test_bn_relu_pool_forward_and_backward_pieces (2x2 / 2x1 / no pooling; windows that tile the tensor exactly and floor mode
+    with a partial last row, a partial last column or both: k_dz_apply's EDGE form) with dyadic tr / saved / coef (one negative-scale channel):
+    pooled output, gsum, dz and dsum EQUAL to float64, with 19-44 % of the windows tied at a positive maximum."""
     from ocrs_models_amd._lib import lib, ptr
     from ocrs_models_amd.models import _DT
 
@@ -393,10 +393,10 @@ def test_bn_relu_pool_pieces_bit_exact(dev, dname, dims):
     tr, saved, coef = case["tr"].contiguous().to(dev), case["saved"].contiguous().to(dev), case["coef"].contiguous().to(dev)
     if PH * PW > 1:
         assert ref["tied"] >= TIE_FLOOR
-        out = torch.empty(N, H // PH, W // PW, C, dtype=dtype, device=dev)
-        L.act_pool_fwd(ptr(z), ptr(tr), ptr(out), C, N, H, W, PH, PW, dt)
-        torch.cuda.synchronize()
-        assert same(host(out), ref["out"]), "pooled output"
+    out = torch.empty(N, H // PH, W // PW, C, dtype=dtype, device=dev)
+    L.act_pool_fwd(ptr(z), ptr(tr), ptr(out), C, N, H, W, PH, PW, dt)
+    torch.cuda.synchronize()
+    assert same(host(out), ref["out"]), "pooled output"
     gsum = torch.zeros(2 * C, dtype=torch.float64, device=dev)
     L.rec_bn_reduce(ptr(gy), ptr(z), ptr(tr), ptr(saved), ptr(gsum), C, N, H, W, PH, PW, dt)
     dz = torch.empty_like(z)

@@ -308,11 +308,12 @@ def test_recognition_bf16_step_is_bit_stable(dev):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("N,H,W,C,PH,PW", [(2, 8, 12, 64, 2, 2), (2, 9, 13, 64, 2, 2), (3, 8, 7, 128, 2, 1), (2, 7, 5, 128, 2, 1), (2, 5, 9, 128, 1, 1)])
+@pytest.mark.parametrize("N,H,W,C,PH,PW", [(2, 8, 12, 64, 2, 2), (2, 9, 13, 64, 2, 2), (3, 8, 7, 128, 2, 1), (2, 7, 5, 128, 2, 1), (2, 5, 9, 128, 1, 1),
+                                          (2, 9, 12, 64, 2, 2), (2, 8, 13, 64, 2, 2)])
 def test_bn_relu_pool_forward_and_backward_pieces(dev, dtype, N, H, W, C, PH, PW):
     """BatchNorm2d + ReLU + MaxPool2d((PH,PW)) forward (ocrs_act_pool_fwd) and the pieces of its backward (ocrs_rec_bn_reduce, ocrs_dz_apply) vs
-    torch autograd through the same operators -- window shapes of models.py:197-199 / 214-216 on tensors the windows tile exactly (the
-    compile-time-window kernels) and on tensors with a partial last row / column (floor mode: the generic kernels)."""
+    torch autograd through the same operators -- window shapes of models.py:197-199 / 214-216 and no pooling, on tensors the windows tile
+    exactly and on tensors with a partial last row, a partial last column or both (floor mode: k_dz_apply's EDGE form)."""
     from ocrs_models_amd._lib import lib, ptr
     from ocrs_models_amd.models import _DT
 
@@ -323,12 +324,10 @@ def test_bn_relu_pool_forward_and_backward_pieces(dev, dtype, N, H, W, C, PH, PW
     tr = torch.stack([sc, sh, torch.zeros(C, device=dev)]).contiguous()
     Hp, Wp = H // PH, W // PW
     out = torch.empty(N, Hp, Wp, C, dtype=dtype, device=dev)
-    if PH * PW > 1:
-        L.act_pool_fwd(ptr(z), ptr(tr), ptr(out), C, N, H, W, PH, PW, dt)
+    L.act_pool_fwd(ptr(z), ptr(tr), ptr(out), C, N, H, W, PH, PW, dt)
     zr = nchw(z).cpu().requires_grad_(True)  # (torch reference on the CPU)
     y = F.max_pool2d(torch.relu(zr * sc.cpu().view(1, C, 1, 1) + sh.cpu().view(1, C, 1, 1)), (PH, PW))
-    if PH * PW > 1:
-        assert rel(nchw(out), y) < TOL[dtype]
+    assert rel(nchw(out), y) < TOL[dtype]
     gy = nhwc(torch.randn(N, C, Hp, Wp, generator=g).to(dev), dtype)
     y.backward(nchw(gy).cpu())
     ghat = (zr.grad / sc.cpu().view(1, C, 1, 1)).to(dev)  # the pooled gradient routed to each window's first maximum, through the ReLU
@@ -346,6 +345,29 @@ def test_bn_relu_pool_forward_and_backward_pieces(dev, dtype, N, H, W, C, PH, PW
     want = coef[0].view(1, C, 1, 1) * ghat + coef[1].view(1, C, 1, 1) * nchw(z) + coef[2].view(1, C, 1, 1)
     assert rel(nchw(dz), want) < TOL[dtype]
     assert rel(dsum - 0.25, nchw(dz).sum((0, 2, 3))) < 1e-5  # the column sums of the STORED dz, accumulated into the caller's buffer
+
+
+@pytest.mark.parametrize("C,PH,PW", [(64, 1, 2), (24, 2, 2)])
+def test_window_entry_points_refuse_what_they_are_not_built_for(dev, C, PH, PW):
+    """ocrs_act_pool_fwd, ocrs_rec_bn_reduce and ocrs_dz_apply take the windows (2,2), (2,1), (1,1) and a C / 8 that is a power of two: a (1,2)
+    window and C = 24 are OCRS_ERR_ARG, nothing is launched and the output buffers keep their sentinel."""
+    from ocrs_models_amd._lib import lib, ptr
+
+    L = lib()
+    N, H, W = 2, 4, 6
+    z, gy = torch.randn(N, H, W, C, device=dev), torch.randn(N, H // PH, W // PW, C, device=dev)
+    tr = torch.stack([torch.ones(C), torch.zeros(C), torch.zeros(C)]).to(dev)
+    out, dz, dsum = torch.full_like(gy, 7.0), torch.full_like(z, 7.0), torch.full((C,), 7.0, device=dev)
+    gsum = torch.full((2 * C,), 7.0, dtype=torch.float64, device=dev)
+    with pytest.raises(RuntimeError, match="bad argument"):
+        L.act_pool_fwd(ptr(z), ptr(tr), ptr(out), C, N, H, W, PH, PW, 0)
+    with pytest.raises(RuntimeError, match="bad argument"):
+        L.rec_bn_reduce(ptr(gy), ptr(z), ptr(tr), ptr(tr), ptr(gsum), C, N, H, W, PH, PW, 0)
+    with pytest.raises(RuntimeError, match="bad argument"):
+        L.dz_apply(ptr(gy), ptr(z), ptr(tr), ptr(tr), ptr(dz), C, N, H, W, PH, PW, 0, ptr(dsum))
+    torch.cuda.synchronize()
+    for t in (out, gsum, dz, dsum):
+        assert bool((t == 7.0).all())
 
 
 @pytest.mark.parametrize("N,CA,CB,H,W,K,pad", [(3, 40, 24, 7, 9, 3, 1), (2, 128, 128, 4, 19, 2, 1), (5, 136, 64, 5, 6, 1, 0), (1, 8, 8, 3, 3, 3, 1)])
