@@ -313,7 +313,9 @@ int ocrs_rec_bn_reduce(const void* g, const void* z, const float* bn, const floa
                        int dtype, hipStream_t st);
 int ocrs_dz_apply(const void* g, const void* z, const float* bn, const float* coef, void* dz, int C, int N, int H, int W, int PH, int PW, int dtype,
                   float* dsum /* nullable [C]: += column sums of dz (the bias gradient of a biased conv, models.py:201, 218) */, hipStream_t st);
-/* BatchNorm2d + AvgPool2d((4,1)) + permute/reshape to (W, N, C*H) (models.py:241-242, 259-262). */
+/* BatchNorm2d + AvgPool2d((4,1)) + permute/reshape to (W, N, C*H) (models.py:241-242, 259-262).  ONE pooled row, from rows 0..3 of z [N][H][W][C];
+   rows 4.. lie in no window (dz there = coef[1] z + coef[2]).  All three: C % 8 == 0 and 4 <= H <= 7, else OCRS_ERR_ARG (H >= 8 would have a second
+   pooled row); ocrs_avgpool_bn_reduce also needs 256 % (C / 8) == 0.  seq / gseq: fp32 [W][N][C]. */
 int ocrs_avgpool_fwd(const void* z, const float* tr, float* seq, int C, int N, int H, int W, int dtype, hipStream_t st);
 int ocrs_avgpool_bn_reduce(const float* gseq, const void* z, const float* saved, double* gsum, int C, int N, int H, int W, int dtype, hipStream_t st);
 int ocrs_avgpool_dz(const float* gseq, const void* z, const float* coef, void* dz, int C, int N, int H, int W, int dtype, hipStream_t st);

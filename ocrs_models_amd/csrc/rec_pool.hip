@@ -442,8 +442,11 @@ int ocrs_dz_apply(const void* g, const void* z, const float* bn, const float* co
 }
 
 // BatchNorm2d + AvgPool2d((4,1)) on H=5 + permute to (T=W, N, C) fp32 (models.py:241-242, 259-262), and its backward pieces.
+// All three compute ONE pooled row from rows 0..3 (rows 4.. lie in no window): that is AvgPool2d((4,1)) for 4 <= H <= 7 only; any other H is
+// OCRS_ERR_ARG (H < 4 would read past the image, H >= 8 has a second pooled row).
+static bool avgpool_ok(int C, int H) { return C >= 8 && C % 8 == 0 && H >= 4 && H <= 7; }
 int ocrs_avgpool_fwd(const void* z, const float* tr, float* seq, int C, int N, int H, int W, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(z && tr && seq && C % 8 == 0 && H >= 4);
+    OCRS_CHECK_ARG(z && tr && seq && avgpool_ok(C, H));
     const int grid = ew_grid((long)N * W * (C / 8));
     if (dtype == 1)
         hipLaunchKernelGGL(k_avgpool_fwd<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)z, tr, seq, C, N, H, W);
@@ -453,7 +456,7 @@ int ocrs_avgpool_fwd(const void* z, const float* tr, float* seq, int C, int N, i
     return OCRS_OK;
 }
 int ocrs_avgpool_bn_reduce(const float* gseq, const void* z, const float* saved, double* gsum, int C, int N, int H, int W, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(gseq && z && saved && gsum && C % 8 == 0 && 256 % (C / 8) == 0);
+    OCRS_CHECK_ARG(gseq && z && saved && gsum && avgpool_ok(C, H) && 256 % (C / 8) == 0);
     int grid = ew_grid((long)N * W * (C / 8));
     if (grid > 4 * kNumCU) grid = 4 * kNumCU;  // (ends in 2 C same-address fp64 atomics per block: see ocrs_rec_bn_reduce)
     if (dtype == 1)
@@ -464,7 +467,7 @@ int ocrs_avgpool_bn_reduce(const float* gseq, const void* z, const float* saved,
     return OCRS_OK;
 }
 int ocrs_avgpool_dz(const float* gseq, const void* z, const float* coef, void* dz, int C, int N, int H, int W, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(gseq && z && coef && dz && C % 8 == 0);
+    OCRS_CHECK_ARG(gseq && z && coef && dz && avgpool_ok(C, H));
     const int grid = ew_grid((long)N * H * W * (C / 8));
     if (dtype == 1)
         hipLaunchKernelGGL(k_avgpool_dz<bf16>, dim3(grid), dim3(256), 0, st, gseq, (const bf16*)z, coef, (bf16*)dz, C, N, H, W);

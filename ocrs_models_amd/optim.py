@@ -151,7 +151,8 @@ def clip_grad_norm_(parameters, max_norm: float, scale_in_place: bool = True):
     ps = [p for p in ([parameters] if isinstance(parameters, torch.Tensor) else list(parameters)) if p.grad is not None]
     if not ps:
         return torch.zeros(())
-    key = tuple(p.grad.data_ptr() for p in ps)
+    # (the sizes belong to the key: the allocator hands a freed gradient's address to the next one, whatever its size)
+    key = tuple((p.grad.data_ptr(), p.grad.numel()) for p in ps)
     t = _clip_cache.get(key)
     if t is None:
         _clip_cache.clear()

@@ -344,6 +344,43 @@ def pool_pieces_reference(case, mode="f64", last=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# BatchNorm (no ReLU) + AvgPool2d((4, 1)) + permute to [W][N][C], and the pieces of its backward, with dyadic caller-supplied coefficients
+# ---------------------------------------------------------------------------------------------------------------------------------
+def avgpool_case(seed, N, H, W, C):
+    """z: integers in [-2, 2] (NCHW), gseq: integers in [-2, 2] [W][N][C]; tr / saved / coef as pool_pieces_case.  The pool's factor 0.25 makes
+    seq and dz multiples of 0.125 and the terms of gsum[1] multiples of 0.125: avgpool_reference asserts that they stay storable and summable."""
+    g = gen(seed)
+    pow2 = lambda n, lo, hi: torch.pow(2.0, ints(g, (n,), lo, hi))  # noqa: E731
+    sign = lambda n: ints(g, (n,), 0, 1) * 2 - 1  # noqa: E731
+    tr = torch.stack([pow2(C, -1, 1) * sign(C), ints(g, (C,), -1, 1), torch.zeros(C)])
+    saved = torch.stack([ints(g, (C,), -1, 1), pow2(C, -1, 1)])  # [mean | rstd]
+    coef = torch.stack([pow2(C, -1, 1) * sign(C), pow2(C, -2, 0) * sign(C), ints(g, (C,), -1, 1)])
+    return {"dims": (N, H, W, C), "z": ints(g, (N, C, H, W), -2, 2), "tr": tr, "saved": saved, "coef": coef, "gseq": ints(g, (W, N, C), -2, 2)}
+
+
+def avgpool_reference(case):
+    """float64, written out: seq[w][n][c] = mean_{h<4} z * scale + shift; ghat = gseq / 4 on rows 0..3 and ZERO on every further row;
+    gsum = [sum ghat | sum ghat zhat]; dz = coef0 ghat + coef1 z + coef2 (NCHW).  `tail` = rows 4.. of dz = coef1 z + coef2 alone."""
+    N, H, W, C = case["dims"]
+    assert 4 <= H <= 7
+    v = lambda t: t.double().view(1, C, 1, 1)  # noqa: E731
+    z = case["z"].double()
+    tr, saved, coef = case["tr"], case["saved"], case["coef"]
+    seq = (z[:, :, :4].mean(2) * tr[0].double().view(1, C, 1) + tr[1].double().view(1, C, 1)).permute(2, 0, 1).contiguous()  # [W][N][C]
+    ghat = torch.zeros_like(z)
+    ghat[:, :, :4] = (case["gseq"].double().permute(1, 2, 0) * 0.25).unsqueeze(2)
+    zhat = (z - v(saved[0])) * v(saved[1])
+    gsum = torch.cat([ghat.sum((0, 2, 3)), (ghat * zhat).sum((0, 2, 3))])
+    dz = v(coef[0]) * ghat + v(coef[1]) * z + v(coef[2])
+    tail = v(coef[1]) * z[:, :, 4:] + v(coef[2])
+    for name, t in (("seq", seq), ("dz", dz), ("ghat zhat", ghat * zhat)):
+        storable(t * 4, "4 " + name)  # multiples of 0.125 ...
+        assert torch.equal(t.float().bfloat16().double(), t), f"{name}: not bf16-representable"  # ... that bf16 holds
+    summable(ghat * zhat * 8, (0, 2, 3), "gsum"), summable(case["gseq"], (0, 1), "gsum[0]"), summable(z[:, :, :4] * 8, 2, "row sum")
+    return {"seq": seq, "gsum": gsum, "dz": dz, "tail": tail}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # GEMMs
 # ---------------------------------------------------------------------------------------------------------------------------------
 def gemm_operands(seed, P, K, M):
@@ -420,6 +457,7 @@ WGRAD_GEMM_CASES = [(4001, 768, 1536, 256, 512), (77, 100, 128, 36, 40)]  # (P, 
 WGRAD_GATHER_CASES = [(3, 40, 24, 7, 9, 3, 1), (1, 8, 8, 3, 3, 3, 1)]     # (N, CA, CB, H, W, K, pad) of ocrs_wgrad_gather
 POOL_PIECES_CASES = [(2, 8, 12, 64, 2, 2), (2, 9, 13, 64, 2, 2), (3, 8, 7, 128, 2, 1), (2, 7, 5, 128, 2, 1), (2, 5, 9, 128, 1, 1),
                      (2, 9, 12, 64, 2, 2), (2, 8, 13, 64, 2, 2)]  # (the last two: only a partial last row / only a partial last column)
+AVGPOOL_CASES = [(2, 5, 9, 128), (3, 5, 1, 128), (1, 4, 7, 8), (2, 7, 6, 64), (5, 5, 26, 128)]  # (N, H, W, C): the model's H = 5; no / three rows outside the window
 
 
 def seed_of(*key):

@@ -408,6 +408,38 @@ def test_bn_relu_pool_pieces_bit_exact(dev, dname, dims):
     assert same(dsum, ref["dsum"] + 0.25), "dsum"  # (multiples of 0.25 far below 2^22: the caller's 0.25 adds exactly)
 
 
+@pytest.mark.parametrize("dname", ["fp32", "bf16"])
+@pytest.mark.parametrize("dims", X.AVGPOOL_CASES, ids=_ids)
+def test_avgpool_pieces_bit_exact(dev, dname, dims):
+    """BatchNorm + AvgPool2d((4,1)) + permute (ocrs_avgpool_fwd / _bn_reduce / _dz) on integer z and gseq with dyadic tr / saved / coef: seq, gsum and
+    dz EQUAL to float64.  Singled out: seq is laid out [W][N][C], and every row of dz from the fifth on is coef1 z + coef2 with no share of
+    the gradient (the pool has ONE output row, from rows 0..3)."""
+    from ocrs_models_amd._lib import lib, ptr
+    from ocrs_models_amd.models import _DT
+
+    dtype = DT[dname]
+    L, dt = lib(), _DT[dtype]
+    N, H, W, C = dims
+    case = X.avgpool_case(X.seed_of(12, dims), *dims)
+    ref = X.avgpool_reference(case)
+    z, gseq = nhwc(case["z"], dtype).to(dev), case["gseq"].contiguous().to(dev)
+    tr, saved, coef = case["tr"].contiguous().to(dev), case["saved"].contiguous().to(dev), case["coef"].contiguous().to(dev)
+    seq = torch.full((W, N, C), float("nan"), device=dev)
+    L.avgpool_fwd(ptr(z), ptr(tr), ptr(seq), C, N, H, W, dt)
+    gsum = torch.zeros(2 * C, dtype=torch.float64, device=dev)
+    L.avgpool_bn_reduce(ptr(gseq), ptr(z), ptr(saved), ptr(gsum), C, N, H, W, dt)
+    dz = torch.full_like(z, float("nan"))
+    L.avgpool_dz(ptr(gseq), ptr(z), ptr(coef), ptr(dz), C, N, H, W, dt)
+    torch.cuda.synchronize()
+    if N > 1 and W > 1:
+        assert not same(seq.view(N, W, C).transpose(0, 1), ref["seq"]), "seq is laid out [N][W][C], not [W][N][C]"
+    assert same(seq, ref["seq"]), "seq"
+    assert same(gsum, ref["gsum"]), "gsum"
+    got = host(dz)
+    assert same(got[:, :, 4:], ref["tail"]), "rows 4.. of dz: coef1 z + coef2, no share of the gradient"
+    assert same(got[:, :, :4], ref["dz"][:, :, :4]), "rows 0..3 of dz"
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 7. GEMMs
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -125,6 +125,25 @@ def test_pool_pieces_cases(dims):
         assert moved > 1e-2, moved
 
 
+@pytest.mark.parametrize("dims", X.AVGPOOL_CASES, ids=_ids)
+def test_avgpool_cases(dims):
+    """the reference asserts storable / summable itself; here: float32 arithmetic gives the same values, a gradient share on row 4 and a
+    [N][W][C] layout would both be seen"""
+    N, H, W, C = dims
+    case = X.avgpool_case(X.seed_of(12, dims), *dims)
+    ref = X.avgpool_reference(case)
+    z, tr = case["z"], case["tr"]
+    s = ((z[:, :, 0] + z[:, :, 1]) + z[:, :, 2]) + z[:, :, 3]
+    seq32 = ((s * 0.25) * tr[0].view(1, C, 1) + tr[1].view(1, C, 1)).permute(2, 0, 1)
+    assert seq32.dtype == torch.float32 and torch.equal(seq32.double(), ref["seq"])
+    assert torch.equal(ref["dz"][:, :, 4:], ref["tail"])
+    if H > 4:
+        share = case["coef"][0].double().view(1, C, 1, 1) * (case["gseq"].double().permute(1, 2, 0) * 0.25).unsqueeze(2)
+        assert float(share.abs().max()) > 0  # what row 4 would receive
+    if N > 1 and W > 1:
+        assert not torch.equal(ref["seq"].reshape(-1), ref["seq"].permute(1, 0, 2).reshape(-1))
+
+
 def _bf16_exact(*ts):
     return all(torch.equal(t.bfloat16().float(), t) for t in ts)
 

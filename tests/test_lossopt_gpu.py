@@ -284,3 +284,20 @@ def test_clip_grad_norm_against_float64(dev, set_name):
         for p, g in zip(ps, grads):
             want_g = g.astype(np.float64) * float(c32)
             assert (np.abs(p.grad.cpu().numpy().astype(np.float64) - want_g) <= R.ulp32(want_g)).all()
+
+
+def test_clip_grad_norm_table_follows_the_gradient_size(dev):
+    """Gradients of different sizes at the SAME address, one call after the other -- what the caching allocator does with a freed gradient: the
+    pointer table cached for the first must not serve the next (it did: the norm of n4096 came out as that of its first 2049 elements whenever
+    the allocator happened to reuse the address)."""
+    import ocrs_models_amd as oa
+
+    g = R.opt_grads(0)[4]
+    buf = torch.from_numpy(np.array(g)).to(dev)
+    for n in (2048, 4096, 2049, 1):
+        p = torch.nn.Parameter(torch.zeros(n, device=dev))
+        p.grad = buf[:n]
+        assert p.grad.data_ptr() == buf.data_ptr()
+        norm = oa.optim.clip_grad_norm_([p], 1e9)
+        n64 = R.norm64([g[:n]])
+        assert abs(float(norm.item()) - n64) <= R.NORM_REL * n64, (n, float(norm.item()), n64)
