@@ -609,6 +609,16 @@ long ocrs_ctc_align_ws_bytes(int T, int N, int Lmax);
  * ocrs_ctc_beam_ws_bytes(T, N, W) bytes.  One workgroup per sample. */
 int ocrs_ctc_beam_decode(const float* lp, const long long* in_len, int T, int N, int C, int W, long row0, int ld, int* labels, int* lens, float* score, void* ws,
                          long ws_bytes, hipStream_t st);
+/* ocrs_ctc_beam_decode with a character n-gram language model fused into the ranking (Python: text.CharLM, lm= of
+ * text.beam_decode_spans; restated in tests/beam_lm_ref.py; no reference counterpart).  gain: dense fp32 table of C^order entries, order in
+ * 1..3; gain[ctx..., c] is the credit for appending label c after the last order - 1 labels of the prefix (padded on the left with 0, the
+ * blank, which never occurs inside a labelling); entries finite or -inf (a forbidden transition), column c = 0 never read.  Every prefix
+ * carries lm, the fp32 sum of its labels' gains in order; candidates are ranked by total + lm and exist iff total and rank are both > -inf;
+ * the CTC numbers, merges and tie rule are those of ocrs_ctc_beam_decode, and a table of zeros gives its bytes.  score: the CTC log-mass of
+ * the best prefix's labelling, as above; lm_score [rows] fp32: its lm (in_len 0 and nothing survived: 0).  Argument checks and workspace as
+ * ocrs_ctc_beam_decode, plus gain and lm_score not NULL and order in 1..3 (else error 1, nothing launched). */
+int ocrs_ctc_beam_decode_lm(const float* lp, const long long* in_len, int T, int N, int C, int W, const float* gain, int order, long row0, int ld, int* labels,
+                            int* lens, float* score, float* lm_score, void* ws, long ws_bytes, hipStream_t st);
 /* The t0 / t1 / peak that ocrs_ctc_decode_spans derives from ctc_greedy_decode_text's runs (datasets/util.py:147-177), for a GIVEN labelling:
  * Viterbi over blank | l1 | blank | ... | lL | blank (ties: stay, then one state back, then two; the final blank wins a tied end).  Reads
  * labels / lens of rows row0 .. row0 + N - 1; character k gets the first / last step the path spends in its state and peak = the largest

@@ -8,6 +8,8 @@
 //                 candidate index ascending) come from a radix select over the 48-bit composite (order key of the total | 65535 - index):
 //                 one LDS histogram of 256 bins per 8-bit digit, at most six passes, ending at the first digit whose bin is taken whole
 //                 (the usual case after one or two).  The survivors are ranked inside one wave by counting larger composites.
+//                 k_ctc_beam<true> (Python: lm= of text.beam_decode_spans; restated in tests/beam_lm_ref.py) ranks by
+//                 total + the gains of a character n-gram table instead of the total alone; k_ctc_beam<false> is the kernel of §18.
 //   k_ctc_align   one wave per sample, lanes over the 2 L + 1 states of blank | l1 | blank | ... | lL | blank, T sequential steps with the two
 //                 delta rows in LDS; the 2-bit back-pointers of a step leave as two ballots per 64 states.  Lane 0 walks them back.
 //
@@ -41,9 +43,18 @@ __device__ __forceinline__ float logaddexp(float a, float b) {
 
 // ---- prefix beam search ------------------------------------------------------------------------------------------------------------------
 // nodes [N][T * W + 1] (parent node, label): node 0 is the empty prefix, node 1 + t W + r the prefix that step t created at rank r.
+//
+// LM = true: every slot also carries lm, the fp32 sum of the gains of its labels, last2, the label before its last, and the
+// offset of its context's row in the gain table; a candidate's rank is its total + lm (+ gain[row + c] for an extension), read again by every
+// pass like lp[t][c] is recomputed.  LM = false is the kernel of §18: none of the additions below is instantiated.
+template <bool LM>
 __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restrict__ lp, const long long* __restrict__ in_len, int T, int N, int C, int W, int cshift,
                                                            long row0, int ld, int* __restrict__ labels, int* __restrict__ lens, float* __restrict__ score,
-                                                           int2* __restrict__ nodes_all) {
+                                                           int2* __restrict__ nodes_all, const float* __restrict__ gain, int order,
+                                                           float* __restrict__ lm_score) {
+    __shared__ float s_lm[LM ? 2 : 1][LM ? BEAM_MAX_W : 1];
+    __shared__ int s_l2[LM ? 2 : 1][LM ? BEAM_MAX_W : 1];
+    __shared__ float2 s_lmrow[LM ? BEAM_MAX_W : 1];  // lm | offset of the context's row in gain (bits)
     __shared__ float s_lb[2][BEAM_MAX_W], s_lnb[2][BEAM_MAX_W];
     __shared__ int s_node[2][BEAM_MAX_W], s_par[2][BEAM_MAX_W], s_last[2][BEAM_MAX_W];
     __shared__ float4 s_slot[BEAM_MAX_W];  // lb | total | last label (bits) | total of the stay candidate
@@ -64,6 +75,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
         s_lb[0][0] = 0.f, s_lnb[0][0] = NEG_INF, s_node[0][0] = 0, s_par[0][0] = -1, s_last[0][0] = 0;
         s_nb = 1;
         nodes[0] = make_int2(-1, 0);
+        if constexpr (LM) s_lm[0][0] = 0.f, s_l2[0][0] = 0;
     }
     float lpn = (live && Ti > 0) ? lp[(long)n * C + c] : NEG_INF;
     __syncthreads();
@@ -93,6 +105,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
             if (q >= 0) stlnb = logaddexp(stlnb, (s_last[cur][q] == e ? s_lb[cur][q] : s_tot[q]) + s_lp[e]);
             s_stlb[tid] = stlb, s_stlnb[tid] = stlnb;
             s_slot[tid] = make_float4(lb, tot, __int_as_float(e), logaddexp(stlb, stlnb));
+            if constexpr (LM) {
+                const int ro = order == 3 ? (s_l2[cur][tid] * C + e) * C : (order == 2 ? e * C : 0);
+                s_lmrow[tid] = make_float2(s_lm[cur][tid], __int_as_float(ro));
+            }
         }
         unsigned long long sup = 0ULL;
         if (live && c != 0)
@@ -100,7 +116,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
                 if (s_last[cur][j] == c && s_qs[j] >= 0) sup |= 1ULL << s_qs[j];
         s_hist[tid] = 0u;
         __syncthreads();
-        // candidate (i, c): index i C + c; c = 0 is the stay.  -> exists, composite = order key of its total | 65535 - index
+        // candidate (i, c): index i C + c; c = 0 is the stay.  -> exists, composite = order key of its total (LM: its rank) | 65535 - index
         auto cand = [&](int i, unsigned long long& comp) -> bool {
             const float4 s = s_slot[i];
             float v;
@@ -111,6 +127,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
                 v = (__float_as_int(s.z) == c ? s.x : s.y) + lpc;
             }
             if (!(v > NEG_INF)) return false;
+            if constexpr (LM) {  // rank = total + lm'; an extension's lm' = lm + gain[row + c], the add the new slot repeats
+                const float2 m = s_lmrow[i];
+                v += c == 0 ? m.x : m.x + gain[__float_as_int(m.y) + c];
+                if (!(v > NEG_INF)) return false;
+            }
             comp = ((unsigned long long)ukey(v) << 16) | (unsigned long long)(0xFFFF - (i * C + c));
             return true;
         };
@@ -179,12 +200,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
                 if (cc == 0) {
                     s_lb[nxt][rank] = s_stlb[i], s_lnb[nxt][rank] = s_stlnb[i];
                     s_node[nxt][rank] = s_node[cur][i], s_par[nxt][rank] = s_par[cur][i], s_last[nxt][rank] = s_last[cur][i];
+                    if constexpr (LM) s_lm[nxt][rank] = s_lm[cur][i], s_l2[nxt][rank] = s_l2[cur][i];
                 } else {
                     const float4 s = s_slot[i];
                     const int node = 1 + t * W + rank;
                     s_lb[nxt][rank] = NEG_INF, s_lnb[nxt][rank] = ((__float_as_int(s.z) == cc ? s.x : s.y) + s_lp[cc]) + 0.0f;
                     s_node[nxt][rank] = node, s_par[nxt][rank] = s_node[cur][i], s_last[nxt][rank] = cc;
                     nodes[node] = make_int2(s_node[cur][i], cc);
+                    if constexpr (LM) {
+                        const float2 m = s_lmrow[i];
+                        s_lm[nxt][rank] = m.x + gain[__float_as_int(m.y) + cc], s_l2[nxt][rank] = s_last[cur][i];
+                    }
                 }
             }
             if (tid == 0) s_nb = K;
@@ -196,6 +222,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
         const long out = (row0 + n) * (long)ld;
         if (s_nb == 0) {  // every candidate of some step was at -inf
             lens[row0 + n] = 0, score[row0 + n] = NEG_INF;
+            if constexpr (LM) lm_score[row0 + n] = 0.f;
         } else {
             int len = 0;
             for (int x = s_node[cur][0]; x > 0 && len < Ti; x = nodes[x].x) ++len;
@@ -207,6 +234,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_ctc_beam(const float* __restri
             }
             lens[row0 + n] = len;
             score[row0 + n] = logaddexp(s_lb[cur][0], s_lnb[cur][0]);
+            if constexpr (LM) lm_score[row0 + n] = s_lm[cur][0];
         }
     }
 }
@@ -318,8 +346,23 @@ int ocrs_ctc_beam_decode(const float* lp, const long long* in_len, int T, int N,
     OCRS_CHECK_ARG(lp && in_len && labels && lens && score && ws && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 && ws_bytes >= ocrs_ctc_beam_ws_bytes(T, N, W));
     int cshift = 1;
     while ((1 << cshift) < C) ++cshift;
-    hipLaunchKernelGGL(k_ctc_beam, dim3((unsigned)N), dim3(BEAM_THREADS), 0, st, lp, in_len, T, N, C, W, cshift, row0, ld, labels, lens, score,
-                       reinterpret_cast<int2*>(ws));
+    hipLaunchKernelGGL(k_ctc_beam<false>, dim3((unsigned)N), dim3(BEAM_THREADS), 0, st, lp, in_len, T, N, C, W, cshift, row0, ld, labels, lens, score,
+                       reinterpret_cast<int2*>(ws), nullptr, 0, nullptr);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+int ocrs_ctc_beam_decode_lm(const float* lp, const long long* in_len, int T, int N, int C, int W, const float* gain, int order, long row0, int ld, int* labels,
+                            int* lens, float* score, float* lm_score, void* ws, long ws_bytes, hipStream_t st) {
+    OCRS_CHECK_ARG(W >= 1 && W <= BEAM_MAX_W && C >= 2 && C <= BEAM_MAX_C && order >= 1 && order <= 3);
+    OCRS_CHECK_ARG(T > 0 && N >= 0 && row0 >= 0 && ld >= T && (long)T * W < (1L << 31) - 1);
+    OCRS_CHECK_ARG(gain && lm_score);
+    if (N == 0) return OCRS_OK;
+    OCRS_CHECK_ARG(lp && in_len && labels && lens && score && ws && (reinterpret_cast<uintptr_t>(ws) & 7) == 0 && ws_bytes >= ocrs_ctc_beam_ws_bytes(T, N, W));
+    int cshift = 1;
+    while ((1 << cshift) < C) ++cshift;
+    hipLaunchKernelGGL(k_ctc_beam<true>, dim3((unsigned)N), dim3(BEAM_THREADS), 0, st, lp, in_len, T, N, C, W, cshift, row0, ld, labels, lens, score,
+                       reinterpret_cast<int2*>(ws), gain, order, lm_score);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

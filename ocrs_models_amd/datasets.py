@@ -281,6 +281,25 @@ def _page_crops(img_dir: str, cache_dir: str, image_id: str, boxes: list) -> lis
     return out
 
 
+def hiertext_text_lines(root_dir: str, train=True, max_images=None):
+    """The line selection of ``HierTextRecognition`` (hiertext.py:160-186): the split's lines file, generated from the annotations if it is
+    missing, cut to its first ``max_images`` lines -> (image directory, crop cache directory, lines file, its JSON lines).  Reads no image."""
+    split = "train" if train else "validation"
+    img_dir = f"{root_dir}/{split}"
+    annotations_file = f"{root_dir}/gt/{split}.jsonl.gz"
+    if not os.path.exists(img_dir):
+        raise Exception(f'Image directory "{img_dir}" not found')
+    if not os.path.exists(annotations_file):
+        raise Exception(f'Label data file "{annotations_file}" not found')
+    lines_file = annotations_file.replace(".jsonl.gz", "-lines.jsonl")
+    generate_text_line_annotations(annotations_file, lines_file)
+    with open(lines_file) as fp:
+        text_lines = [line for line in fp]
+    if max_images:
+        text_lines = text_lines[:max_images]
+    return img_dir, f"{root_dir}/{split}-lines-cache", lines_file, text_lines
+
+
 class HierTextRecognition(Dataset):
     """HierText dataset for text recognition: the reference's ``HierTextRecognition`` (hiertext.py:145-304; same directory layout, lines
     file and crop cache) with every line crop resident in device memory.  ``augment`` stands where the reference takes ``transform``: the
@@ -296,20 +315,7 @@ class HierTextRecognition(Dataset):
             raise TypeError("HierTextRecognition takes augment=True/False, not a transform: the augmentations of "
                             "text_recognition_data_augmentations() run inside the batch kernels on the device")
         self.alphabet = [c for c in (DEFAULT_ALPHABET if alphabet is None else alphabet)]
-        split = "train" if train else "validation"
-        self._img_dir = f"{root_dir}/{split}"
-        self._cache_dir = f"{root_dir}/{split}-lines-cache"
-        annotations_file = f"{root_dir}/gt/{split}.jsonl.gz"
-        if not os.path.exists(self._img_dir):
-            raise Exception(f'Image directory "{self._img_dir}" not found')
-        if not os.path.exists(annotations_file):
-            raise Exception(f'Label data file "{annotations_file}" not found')
-        lines_file = annotations_file.replace(".jsonl.gz", "-lines.jsonl")
-        generate_text_line_annotations(annotations_file, lines_file)
-        with open(lines_file) as fp:
-            text_lines = [line for line in fp]
-        if max_images:
-            text_lines = text_lines[:max_images]
+        self._img_dir, self._cache_dir, lines_file, text_lines = hiertext_text_lines(root_dir, train, max_images)
         self.augment = bool(augment)
         self.output_height = output_height
         self.device = torch.device(device)

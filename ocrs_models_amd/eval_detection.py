@@ -1,6 +1,7 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
     python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]] [--chars] [--beam-width N]
+        [--lm FILE [--lm-weight A] [--lm-bonus B]]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
@@ -12,7 +13,9 @@ in reading order, instead of the words.  ``--lines --reading-order`` prints thos
 character of its text sits on the page and the recogniser's log-prob of it (``"char_quads"``, ``"char_log_probs"``), and to every line object the text and
 character range of each of its words (``"word_texts"``, ``"word_chars"``): ``inference.char_boxes`` / ``word_chars``.  ``--beam-width N`` (with
 ``--rec-model``) decodes by CTC prefix beam search with N prefixes instead of greedily and adds ``"log_prob"``, the log-mass of the text, to every
-object.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
+object.  ``--lm FILE`` (with ``--beam-width``) loads a character language model written by ``python -m ocrs_models_amd.char_lm``
+and fuses ``A log P + B`` per character into the beam's ranking (``--lm-weight A``, default 1; ``--lm-bonus B``, default 0); every object
+gains ``"lm_score"``.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ from . import inference
 from .checkpoint import load_model_state
 from .models import DetectionModel
 from .recognition import RecognitionModel
-from .text import DEFAULT_ALPHABET
+from .text import DEFAULT_ALPHABET, CharLM
 
 
 def _to_pil(img: torch.Tensor) -> Image.Image:
@@ -62,6 +65,10 @@ def main(argv=None):
                         "--lines, every word's text and character range")
     parser.add_argument("--beam-width", type=int, default=None, metavar="N", help="with --rec-model: decode by CTC prefix beam search with N prefixes "
                         "(1..64) instead of greedily and add the text's log-prob to the JSON objects")
+    parser.add_argument("--lm", metavar="FILE", help="with --beam-width: a character language model (.npz of ocrs_models_amd.char_lm) fused into the "
+                        "beam's ranking; adds the text's language-model score to the JSON objects")
+    parser.add_argument("--lm-weight", type=float, default=1.0, metavar="A", help="with --lm: the gain per character is A log P + B (default 1)")
+    parser.add_argument("--lm-bonus", type=float, default=0.0, metavar="B", help="with --lm: see --lm-weight (default 0)")
     args = parser.parse_args(argv)
     if args.reading_order and not args.lines:
         parser.error("--reading-order needs --lines")
@@ -69,6 +76,8 @@ def main(argv=None):
         parser.error("--beam-width needs --rec-model")
     if args.beam_width is not None and not 1 <= args.beam_width <= 64:
         parser.error("--beam-width must be in 1..64")
+    if args.lm is not None and args.beam_width is None:
+        parser.error("--lm needs --beam-width")
 
     device = torch.device("cuda:0")
     model = DetectionModel().to(device)
@@ -98,9 +107,15 @@ def main(argv=None):
         rec = RecognitionModel(DEFAULT_ALPHABET).to(device)
         load_model_state(args.rec_model, rec, device)
         rec.eval()
+    lm = None
+    if args.lm is not None and rec is not None:
+        model_lm = CharLM.load(args.lm)
+        if model_lm.alphabet is not None and model_lm.alphabet != DEFAULT_ALPHABET:
+            parser.error("--lm: the language model was built for another alphabet")
+        lm = model_lm.gain(args.lm_weight, args.lm_bonus, device)
     if args.lines:
         if rec is not None:
-            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width)
+            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width, lm=lm)
             for line in lines:
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]
@@ -113,10 +128,13 @@ def main(argv=None):
         packed = inference.rectify_crops(page, det["quads"], plan)
         batches = inference.crops_to_batches(packed, plan)
         if args.chars:
-            spans = inference.decode_crop_spans(rec, batches, args.beam_width)
+            spans = inference.decode_crop_spans(rec, batches, args.beam_width, lm)
             texts, chars, _ = inference.chars_to_host(spans, inference.char_boxes(det["quads"], plan, spans))
             for quad, p in zip(quads, batches[2]):
                 print(json.dumps({"quad": quad, "text": texts[p], **chars[p]}))
+        elif lm is not None:
+            for quad, text, score, lm_score in zip(quads, *inference.recognize_crops(rec, batches, beam_width=args.beam_width, lm=lm)):
+                print(json.dumps({"quad": quad, "text": text, "log_prob": score, "lm_score": lm_score}))
         elif args.beam_width is not None:
             for quad, text, score in zip(quads, *inference.recognize_crops(rec, batches, beam_width=args.beam_width)):
                 print(json.dumps({"quad": quad, "text": text, "log_prob": score}))

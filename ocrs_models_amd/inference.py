@@ -54,6 +54,11 @@ greedy decode returns the labelling of the single most probable alignment -- and
 dict; the spans that ``chars=True`` needs come from a forced alignment of the chosen labelling.  None, the default, is the greedy path
 unchanged; the same three waits either way.
 
+Language model (``text.CharLM`` / ``LMGain``; restated for the tests in tests/beam_lm_ref.py).  With ``lm=model.gain(...)`` next to
+``beam_width`` the beam ranks every prefix by its log-mass + the gains of a character n-gram table and every dict gains ``"lm_score"`` next to
+``"log_prob"``, which keeps its meaning.  None, the default, is the plain beam unchanged; ``lm`` without ``beam_width`` is an argument error; the
+same waits.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
@@ -67,7 +72,7 @@ import torch
 
 from ._lib import lib, ptr
 from .input_pipeline import _need_cuda, resize, transform_image
-from .text import (DEFAULT_ALPHABET, _check_beam_width, beam_decode_spans_async, decode_text, greedy_decode_batch_async, greedy_decode_spans_async, round_up,
+from .text import (DEFAULT_ALPHABET, LMGain, _check_beam_width, _check_lm, beam_decode_spans_async, decode_text, greedy_decode_batch_async, greedy_decode_spans_async, round_up,
                    span_arrays)
 
 MASK_SIZE = (800, 600)   # train_detection.py's mask_size: the size the detection model is trained and evaluated at
@@ -272,7 +277,8 @@ class CharSpans:
     ``labels[p, k]``, was collapsed from the time steps ``t0[p, k] .. t1[p, k]`` and has the log-prob ``peak[p, k]``, the largest of its class
     over those steps; ``lens[p]`` characters.  Entries of a row from ``lens[p]`` on are not written.  ``buf`` is the one int32 buffer all five
     are views of (``text.span_arrays``): one copy brings them to the host.  ``scores`` (R,) fp32, beam decodes only: the
-    log-mass of every row's labelling; None for the greedy decode."""
+    log-mass of every row's labelling; None for the greedy decode.  ``lm_scores`` (R,) fp32, beam decodes with a language model only
+    (DESIGN.md §19): the gains of every row's labelling; None otherwise."""
     buf: torch.Tensor
     labels: torch.Tensor  # (R,ld) int32
     t0: torch.Tensor      # (R,ld) int32
@@ -280,6 +286,7 @@ class CharSpans:
     peak: torch.Tensor    # (R,ld) fp32
     lens: torch.Tensor    # (R,) int32
     scores: torch.Tensor | None = None  # (R,) fp32
+    lm_scores: torch.Tensor | None = None  # (R,) fp32
 
     def arrays(self):
         return self.buf, self.labels, self.t0, self.t1, self.peak, self.lens
@@ -301,12 +308,22 @@ def _check_batches(rec_model, batches, who: str):
         raise RuntimeError(f"{who}: the model must be in eval mode (model.eval())")
 
 
-def decode_crop_spans(rec_model, batches, beam_width: int | None = None) -> CharSpans:
+def _check_lm_args(who: str, beam_width, lm):
+    """``lm`` is a keyword of the beam decode: without ``beam_width`` it is an argument error"""
+    if lm is not None:
+        if beam_width is None:
+            raise RuntimeError(f"{who}: lm needs beam_width (the greedy decode has no hypotheses to choose among)")
+        _check_lm(who, lm)
+
+
+def decode_crop_spans(rec_model, batches, beam_width: int | None = None, lm: LMGain | None = None) -> CharSpans:
     """Eval forward of the recogniser per batch, as ``recognize_crops``, with the decode that keeps the spans: the chunks write their rows
     into one set of arrays whose pitch is the longest chunk's number of time steps.  Every forward is queued before the first decode (the
     pitch is known once the last forward has its shape); no synchronisation, nothing is copied.  ``beam_width``: None = the greedy decode;
     a width = prefix beam search and forced alignment (``text.beam_decode_spans_async``) into the same arrays, with
-    ``scores`` set."""
+    ``scores`` set.  ``lm`` (with a width): the gain table of a language model fused into the beam's ranking, with
+    ``lm_scores`` set."""
+    _check_lm_args("decode_crop_spans", beam_width, lm)
     _check_batches(rec_model, batches, "decode_crop_spans")
     if beam_width is not None:
         _check_beam_width("decode_crop_spans", beam_width)
@@ -318,12 +335,14 @@ def decode_crop_spans(rec_model, batches, beam_width: int | None = None) -> Char
     spans = CharSpans(*span_arrays(rows, max([lp.shape[0] for lp in lps], default=1), dev))
     if beam_width is not None:
         spans.scores = torch.empty(rows, dtype=torch.float32, device=dev)
+    if lm is not None:
+        spans.lm_scores = torch.empty(rows, dtype=torch.float32, device=dev)
     row = 0
     for lp, iw in zip(lps, image_widths):
         if beam_width is None:
             greedy_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), spans.arrays(), row)
         else:
-            beam_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), beam_width, spans.arrays(), row, spans.scores)
+            beam_decode_spans_async(lp, iw.div(4, rounding_mode="floor"), beam_width, spans.arrays(), row, spans.scores, lm, spans.lm_scores)
         row += lp.shape[1]
     return spans
 
@@ -372,12 +391,14 @@ def word_chars(lines: TextLines, plan: CropPlan, spans: CharSpans, boxes: CharBo
 def chars_to_host(spans: CharSpans, boxes: CharBoxes, alphabet=DEFAULT_ALPHABET, ranges: torch.Tensor | None = None):
     """The characters on the host, in the rows' (width-sorted) order: ``(texts, chars, ranges)`` with ``chars[p] = {"char_quads": [4x2 lists],
     "char_log_probs": [floats]}``, one entry per character of ``texts[p]``, and ``ranges`` the (N,2) result of ``word_chars`` as a list (None
-    without it).  Spans of a beam decode (``spans.scores``) add ``"log_prob"`` to every ``chars[p]``.  The copies are queued on the current
+    without it).  Spans of a beam decode (``spans.scores``) add ``"log_prob"`` to every ``chars[p]``, those of one with a language model
+    (``spans.lm_scores``) ``"lm_score"`` too.  The copies are queued on the current
     stream and there is ONE wait for all of them."""
     alphabet = list(alphabet)
     sp_h, cq_h = _to_host_async(spans.buf), _to_host_async(boxes.quads)
     rg_h = None if ranges is None else _to_host_async(ranges)
     sc_h = None if spans.scores is None else _to_host_async(spans.scores)
+    lm_h = None if spans.lm_scores is None else _to_host_async(spans.lm_scores)
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(spans.buf.device))
     done.synchronize()
@@ -389,34 +410,42 @@ def chars_to_host(spans: CharSpans, boxes: CharBoxes, alphabet=DEFAULT_ALPHABET,
     if sc_h is not None:  # a beam decode: the labelling's log-mass travels with the characters
         for d, sc in zip(chars, sc_h.tolist()):
             d["log_prob"] = sc
+    if lm_h is not None:
+        for d, sc in zip(chars, lm_h.tolist()):
+            d["lm_score"] = sc
     return texts, chars, None if rg_h is None else rg_h.tolist()
 
 
 def _beam_texts_to_host(spans: CharSpans, alphabet):
-    """texts and scores of a beam decode's span rows on the host, in the rows' order: two copies and ONE wait, for the event behind them"""
+    """texts, scores and language-model scores (None without a model) of a beam decode's span rows on the host, in the rows' order: two or
+    three copies and ONE wait, for the event behind them"""
     sp_h, sc_h = _to_host_async(spans.buf), _to_host_async(spans.scores)
+    lm_h = None if spans.lm_scores is None else _to_host_async(spans.lm_scores)
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(spans.buf.device))
     done.synchronize()
     rows, ld = spans.labels.shape
     lens, alphabet = [max(n, 0) for n in sp_h[4 * rows * ld:].tolist()], list(alphabet)  # (-1: a row without any labelling of finite mass)
     texts = [decode_text(row[:n], alphabet) for row, n in zip(sp_h[:rows * ld].view(rows, ld), lens)]
-    return texts, sc_h.tolist()
+    return texts, sc_h.tolist(), None if lm_h is None else lm_h.tolist()
 
 
-def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = False, beam_width: int | None = None):
+def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None):
     """Eval forward of the recogniser per batch with ``input_lengths = image_width // 4`` (as ``train_rec.test``) and the device greedy
     decode.  ``batches`` is what ``crops_to_batches`` returned: ``(batch tensors, image widths, perm)``.  Returns the strings in quad order.
     Every chunk's forward and decode are queued before the first label copy is waited for.  ``chars=True``: ``(strings in quad order,
     CharSpans)`` -- the same strings from the decode that keeps every character's time steps and log-prob (``decode_crop_spans``), whose
     device arrays ``char_boxes`` and ``word_chars`` take; one wait, for the one copy of the span buffer.  ``beam_width``: the
     strings of prefix beam search instead -- ``(strings, log-probs of the strings)``, with ``chars=True`` ``(strings, CharSpans, log-probs)``;
-    both forms decode into one span buffer and wait once."""
+    both forms decode into one span buffer and wait once.  ``lm`` (with ``beam_width``): the beam ranks by log-prob + the
+    language model's gains, and the gains of the strings are appended to either tuple; the same one wait."""
+    _check_lm_args("recognize_crops", beam_width, lm)
     if beam_width is not None:
-        spans = decode_crop_spans(rec_model, batches, beam_width)
-        texts, scores = _beam_texts_to_host(spans, alphabet)
+        spans = decode_crop_spans(rec_model, batches, beam_width, lm)
+        texts, scores, lm_sc = _beam_texts_to_host(spans, alphabet)
         texts, scores = [texts[p] for p in batches[2]], [scores[p] for p in batches[2]]
-        return (texts, spans, scores) if chars else (texts, scores)
+        tail = () if lm_sc is None else ([lm_sc[p] for p in batches[2]],)
+        return ((texts, spans, scores) if chars else (texts, scores)) + tail
     if chars:
         spans = decode_crop_spans(rec_model, batches)
         sp_h = _to_host_async(spans.buf)
@@ -440,7 +469,7 @@ def recognize_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool =
 
 
 def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLines | None = None, n_lines: int = 0, order: ReadingOrder | None = None,
-                line_page_offs: list | None = None, chars_plan: CropPlan | None = None, beam_width: int | None = None) -> list[dict]:
+                line_page_offs: list | None = None, chars_plan: CropPlan | None = None, beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
     """The tail of ``ocr_page``, ``read_lines`` and ``ocr_pages``: ``recognize_crops`` on ``batches``, then the flat result list -- one
     ``{"quad", "text"}`` per word, or with ``lines`` one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  With ``order``
     the list is in reading order -- position k holds line ``order.line_order[k]`` -- and every dict has ``"block"``, counted from 0 on every
@@ -449,19 +478,22 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
     ``chars_plan`` (the plan the crops were cut with; ``chars=True`` of the callers): every dict also has ``"char_quads"`` and
     ``"char_log_probs"``, line dicts ``"word_chars"`` and ``"word_texts"`` too.  The boxes and word ranges are queued behind the
     decodes and copied with the labels: still one wait here.  ``beam_width``: the texts of prefix beam search and
-    ``"log_prob"`` in every dict; still one wait."""
+    ``"log_prob"`` in every dict; still one wait.  ``lm``: the beam's ranking includes the language model's gains and
+    every dict has ``"lm_score"`` next to ``"log_prob"``; its copy joins the same wait."""
     words_h = _to_host_async(words)
     if lines is not None:
         lq_h, order_h, offs_h = (_to_host_async(t) for t in (lines.quads, lines.word_order, lines.line_offsets))
     if order is not None:
         ro_h, nb_h = _to_host_async(order.line_order), _to_host_async(order.new_block)
-    scores = None
-    if chars_plan is None and beam_width is not None:
+    scores = lm_sc = None
+    if chars_plan is None and beam_width is not None and lm is not None:
+        texts, scores, lm_sc = recognize_crops(rec_model, batches, alphabet, beam_width=beam_width, lm=lm)
+    elif chars_plan is None and beam_width is not None:
         texts, scores = recognize_crops(rec_model, batches, alphabet, beam_width=beam_width)
     elif chars_plan is None:
         texts = recognize_crops(rec_model, batches, alphabet)
     else:
-        spans = decode_crop_spans(rec_model, batches, beam_width)
+        spans = decode_crop_spans(rec_model, batches, beam_width, lm)
         boxes = char_boxes(words if lines is None else lines.quads, chars_plan, spans)
         ranges = None if lines is None else word_chars(lines, chars_plan, spans, boxes, alphabet)
         texts, chars, ranges = chars_to_host(spans, boxes, alphabet, ranges)
@@ -471,6 +503,8 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
     if lines is None:
         if chars_plan is not None:
             return [{"quad": q, "text": t, **c} for q, t, c in zip(wl, texts, chars)]
+        if lm_sc is not None:
+            return [{"quad": q, "text": t, "log_prob": sc, "lm_score": ls} for q, t, sc, ls in zip(wl, texts, scores, lm_sc)]
         if scores is not None:
             return [{"quad": q, "text": t, "log_prob": sc} for q, t, sc in zip(wl, texts, scores)]
         return [{"quad": q, "text": t} for q, t in zip(wl, texts)]
@@ -479,6 +513,9 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
     if scores is not None:
         for l, d in enumerate(out):
             d["log_prob"] = scores[l]
+    if lm_sc is not None:
+        for l, d in enumerate(out):
+            d["lm_score"] = lm_sc[l]
     if chars_plan is not None:
         for l, d in enumerate(out):
             rg = [ranges[i] for i in word_order[offs[l]:offs[l + 1]]]
@@ -497,13 +534,16 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
              output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, chars: bool = False,
-             beam_width: int | None = None) -> list[dict]:
+             beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
     A page without components returns ``[]`` without launching the recogniser.  ``chars=True``: every dict also has ``"char_quads"``, the
     rectangle of every character of ``"text"`` on the page, and ``"char_log_probs"``, the recogniser's log-prob of each; the
     same three waits.
     ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
-    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits."""
+    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
+    ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
+    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits."""
+    _check_lm_args("ocr_page", beam_width, lm)
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
@@ -511,7 +551,7 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thresh
     plan = crop_plan(quads, output_height)
     packed = rectify_crops(page_u8, quads, plan)
     return _read_crops(rec_model, crops_to_batches(packed, plan, max_batch, width_unit), alphabet, quads, chars_plan=plan if chars else None,
-                       beam_width=beam_width)
+                       beam_width=beam_width, lm=lm)
 
 
 # ------------------------------------------------------------------ words -> lines -------------------------------------------------------
@@ -647,26 +687,30 @@ def page_text(result: list[dict]) -> str:
 
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
                alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0,
-               chars: bool = False, beam_width: int | None = None) -> list[dict]:
+               chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
     ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
     ``reading_order=True`` is queued behind the line stage and changes nothing about the crops (lines are cropped in line order).
     ``chars=True``: the characters' quads, log-probs and word ranges as ``ocr_lines`` describes them, queued behind the decodes; the same waits.
     ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
-    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits."""
+    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
+    ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
+    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits."""
+    _check_lm_args("read_lines", beam_width, lm)
     lines = find_lines(quads, None, max_gap, min_cos)
     order = _order_lines(lines, block_gap) if reading_order else None
     plan = crop_plan(lines.quads, output_height, lines.n_lines)
     packed = rectify_crops(page_u8, lines.quads, plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
-    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order, chars_plan=plan if chars else None, beam_width=beam_width)
+    return _read_crops(rec_model, batches, alphabet, quads, lines, plan.host()[0], order, chars_plan=plan if chars else None, beam_width=beam_width,
+                       lm=lm)
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
-              beam_width: int | None = None) -> list[dict]:
+              beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
@@ -675,12 +719,13 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thres
     ``chars=True``: every dict keeps those keys and gains ``"char_quads"`` (one 4x2 list per character of ``"text"``: where it
     sits on the page), ``"char_log_probs"`` (the recogniser's log-prob of each), ``"word_chars"`` (parallel to ``"words"``: the ``[first, end]``
     of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits.  ``beam_width``: as in
-    ``read_lines``."""
+    ``read_lines``; ``lm``: as in ``read_lines``."""
+    _check_lm_args("ocr_lines", beam_width, lm)
     det = detect_words(det_model, page_u8, size, threshold, expand)
     if det["n"] == 0:
         return []
     return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars,
-                      beam_width)
+                      beam_width, lm)
 
 
 # ------------------------------------------------------------------ page batches ---------------------------------------------------------
@@ -874,7 +919,7 @@ def split_by_page(items: list, offs: list) -> list[list]:
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
-              beam_width: int | None = None) -> list[list[dict]]:
+              beam_width: int | None = None, lm: LMGain | None = None) -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
@@ -884,7 +929,10 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
     ``reading_order=True`` (with ``lines``): every page's list in reading order with ``"block"``, as ``ocr_lines`` returns it; the same waits.
     ``chars=True``: the character keys of ``ocr_lines`` / ``ocr_page`` in every dict; the same waits.
     ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
-    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits."""
+    ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
+    ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
+    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits."""
+    _check_lm_args("ocr_pages", beam_width, lm)
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
@@ -908,6 +956,7 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
         packed = rectify_crops_pages(packed_pages, page_offs, page_sizes, words, det["page_of_word"], plan)
     batches = crops_to_batches(packed, plan, max_batch, width_unit)
     if not lines:
-        return split_by_page(_read_crops(rec_model, batches, alphabet, words, chars_plan=plan if chars else None, beam_width=beam_width), word_offs_h)
+        return split_by_page(_read_crops(rec_model, batches, alphabet, words, chars_plan=plan if chars else None, beam_width=beam_width, lm=lm),
+                             word_offs_h)
     n_lines, lpo = plan.host()[0], lpo_h.tolist()
-    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo, plan if chars else None, beam_width), lpo)
+    return split_by_page(_read_crops(rec_model, batches, alphabet, words, tl, n_lines, order, lpo, plan if chars else None, beam_width, lm), lpo)

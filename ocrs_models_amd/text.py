@@ -10,11 +10,14 @@
 * ``beam_decode_spans``, ``ctc_align_spans``                                         CTC prefix beam search next to the greedy rule of
   datasets/util.py:147-177, and the forced alignment that gives its labelling spans (``ocrs_ctc_beam_decode`` / ``ocrs_ctc_align_spans``,
   csrc/ctc_beam.hip)
+* ``CharLM``, ``LMGain``                                                             a character n-gram model counted on the host and its
+  gain table on the device, which ``lm=`` of the beam decoders fuses into the ranking (``ocrs_ctc_beam_decode_lm``)
 """
 from __future__ import annotations
 
 import string
 
+import numpy as np
 import torch
 
 from ._lib import lib, ptr
@@ -191,17 +194,134 @@ BEAM_MAX_WIDTH, BEAM_MAX_CLASSES = 64, 256  # what ocrs_ctc_beam_decode supports
 class _BeamSpans(_DecodeSpans):
     """Result handle of beam_decode_spans_async: the span arrays and the scores on the device, and on their way into pinned host memory."""
 
-    def __init__(self, arrays, host, event, N, ld, scores, scores_host):
+    def __init__(self, arrays, host, event, N, ld, scores, scores_host, lm_scores=None, lm_scores_host=None):
         super().__init__(arrays, host, event, N, ld, None)
-        self.scores, self.scores_host = scores, scores_host
+        self.scores, self.scores_host, self.lm_scores, self.lm_scores_host = scores, scores_host, lm_scores, lm_scores_host
 
     def result(self):
         """list of N dicts ``labels``, ``t0``, ``t1``, ``peak`` as ``greedy_decode_spans`` returns them, plus ``score``, the log-mass of the
-        labelling (waits for the copies only)"""
+        labelling, and with a language model ``lm_score``, the sum of its gains (waits for the copies only)"""
         out = super().result()
         for d, s in zip(out, self.scores_host.tolist()):
             d["score"] = s
+        if self.lm_scores_host is not None:
+            for d, s in zip(out, self.lm_scores_host.tolist()):
+                d["lm_score"] = s
         return out
+
+
+LM_MAX_ORDER = 3  # what ocrs_ctc_beam_decode_lm supports (csrc/ctc_beam.hip)
+
+
+class LMGain:
+    """A gain table of DESIGN.md §19 on a device: ``table`` float32 of shape ``(C,) * order``, ``table[ctx..., c]`` the credit for appending
+    label c after the last ``order - 1`` labels (padded on the left with 0).  Entries are finite or -inf; NaN and +inf are refused here."""
+
+    def __init__(self, table, device=None):
+        t = np.ascontiguousarray(np.asarray(table, dtype=np.float32))
+        if not 1 <= t.ndim <= LM_MAX_ORDER or t.shape != (t.shape[0],) * t.ndim or t.shape[0] < 2:
+            raise RuntimeError(f"LMGain: expected a table of shape (C,) * order with C >= 2 and order in 1..{LM_MAX_ORDER}, got {t.shape}")
+        if np.isnan(t).any() or (t == np.inf).any():
+            raise RuntimeError("LMGain: the table holds NaN or +inf (entries must be finite or -inf)")
+        self.order, self.C = t.ndim, t.shape[0]
+        self.table = torch.from_numpy(t).to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+
+
+def witten_bell(counts: np.ndarray) -> np.ndarray:
+    """float64 counts ``n[ctx..., c]`` of shape ``(C,) * order`` -> float64 P(c | ctx) of the same shape by interpolated Witten-Bell smoothing
+    (DESIGN.md §19): with n(ctx) the count of ctx, d(ctx) its number of distinct followers and ctx' the context without its oldest label,
+    P_k(c | ctx) = (n(ctx, c) + d(ctx) P_{k-1}(c | ctx')) / (n(ctx) + d(ctx)) where n(ctx) > 0, else P_{k-1}(c | ctx'); P_0 = 1 / (C - 1) for
+    c >= 1 and 0 for the blank.  The counts of a shorter context are the sums over the oldest label."""
+    n = np.asarray(counts, dtype=np.float64)
+    C = n.shape[0]
+    levels = [n]
+    while levels[0].ndim > 1:
+        levels.insert(0, levels[0].sum(axis=0))
+    p = np.full(C, 1.0 / (C - 1))
+    p[0] = 0.0
+    for nk in levels:
+        tot, d = nk.sum(axis=-1, keepdims=True), (nk > 0).sum(axis=-1, keepdims=True).astype(np.float64)
+        back = np.broadcast_to(p, nk.shape)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            p = np.where(tot > 0, (nk + d * back) / (tot + d), back)
+    return p
+
+
+class CharLM:
+    """Character n-gram language model over the recogniser's labels: ``log_probs`` float32 of shape ``(C,) * order``,
+    ``log_probs[ctx..., c] = log P(c | ctx)`` with the context padded on the left with 0 (the blank: start of line); every row sums to 1
+    over c = 1..C-1 and column 0 is -inf.  Counted and smoothed on the host in numpy float64, a one-off whose result is reproducible bit
+    for bit; ``gain`` puts the table the beam search reads on the device."""
+
+    def __init__(self, log_probs, alphabet=None, order: int | None = None):
+        lp = np.ascontiguousarray(np.asarray(log_probs, dtype=np.float32))
+        if not 1 <= lp.ndim <= LM_MAX_ORDER or lp.shape != (lp.shape[0],) * lp.ndim or (order is not None and order != lp.ndim):
+            raise RuntimeError(f"CharLM: expected log-probs of shape (C,) * order with order in 1..{LM_MAX_ORDER}, got {lp.shape}")
+        if alphabet is not None and len(alphabet) + 1 != lp.shape[0]:
+            raise RuntimeError(f"CharLM: {lp.shape[0]} classes for an alphabet of {len(alphabet)} characters")
+        self.log_probs, self.alphabet, self.order = lp, None if alphabet is None else "".join(alphabet), lp.ndim
+        self._gains = {}
+
+    @staticmethod
+    def count(rows, lengths, n_classes: int, order: int = 3) -> np.ndarray:
+        """float64 n-gram counts of shape ``(n_classes,) * order`` over the lines ``rows[i, :lengths[i]]``, each padded on the left with
+        ``order - 1`` zeros"""
+        if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= LM_MAX_ORDER:
+            raise RuntimeError(f"CharLM: order must be an integer in 1..{LM_MAX_ORDER}, got {order!r}")
+        C = int(n_classes)
+        if C < 2:
+            raise RuntimeError("CharLM: expected at least two classes (the blank and one label)")
+        rows = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        lengths = lengths.cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+        rows = rows.astype(np.int64).reshape(len(lengths), -1) if len(lengths) else np.zeros((0, 1), dtype=np.int64)
+        lengths = np.minimum(lengths.astype(np.int64), rows.shape[1])
+        valid = np.arange(rows.shape[1])[None, :] < lengths[:, None]
+        if ((rows < 1) | (rows >= C))[valid].any():
+            raise RuntimeError(f"CharLM: labels must lie in 1..{C - 1}")
+        padded = np.concatenate([np.zeros((rows.shape[0], order - 1), dtype=np.int64), np.where(valid, rows, 0)], axis=1)
+        flat = np.zeros(valid.shape, dtype=np.int64)
+        for k in range(order):
+            flat = flat * C + padded[:, k:k + rows.shape[1]]
+        return np.bincount(flat[valid], minlength=C ** order).astype(np.float64).reshape((C,) * order)
+
+    @classmethod
+    def from_labels(cls, rows, lengths, n_classes: int, order: int = 3, alphabet=None):
+        """the model of already encoded lines (``rows`` (N, L) labels in 1..n_classes-1, ``lengths`` (N,)), such as the device line store's"""
+        with np.errstate(divide="ignore"):
+            return cls(np.log(witten_bell(cls.count(rows, lengths, n_classes, order))).astype(np.float32), alphabet)
+
+    @classmethod
+    def from_texts(cls, texts, alphabet=DEFAULT_ALPHABET, order: int = 3, unknown_char: str = "?"):
+        """the model of text lines, encoded with ``encode_text``"""
+        enc = [encode_text(t, alphabet, unknown_char).numpy() for t in texts]
+        rows = np.zeros((len(enc), max([len(e) for e in enc], default=0) or 1), dtype=np.int64)
+        for i, e in enumerate(enc):
+            rows[i, :len(e)] = e
+        return cls.from_labels(rows, np.asarray([len(e) for e in enc], dtype=np.int64), len(alphabet) + 1, order, alphabet)
+
+    def save(self, path: str) -> None:
+        """one .npz: the table, the alphabet (empty: none) and the order"""
+        with open(path, "wb") as f:
+            np.savez(f, log_probs=self.log_probs, alphabet=np.asarray(self.alphabet or ""), order=np.asarray(self.order, dtype=np.int64))
+
+    @classmethod
+    def load(cls, path: str):
+        with np.load(path, allow_pickle=False) as z:
+            alphabet = str(z["alphabet"][()])
+            return cls(z["log_probs"], alphabet or None, int(z["order"]))
+
+    def gain(self, weight: float = 1.0, bonus: float = 0.0, device=None) -> LMGain:
+        """The table the beam search adds per appended label: ``float32(weight * log P + bonus)``, computed in float64 (column 0, which is
+        never read, stays -inf).  ``weight`` scales the model against the recogniser, ``bonus`` pays every label for the probability mass a
+        longer text loses.  Cached per (weight, bonus, device); NaN or +inf (a negative weight on a forbidden transition) is refused."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        key = (float(weight), float(bonus), str(dev))
+        if key not in self._gains:
+            with np.errstate(invalid="ignore"):
+                g = (float(weight) * self.log_probs.astype(np.float64) + float(bonus)).astype(np.float32)
+            g[..., 0] = -np.inf
+            self._gains[key] = LMGain(g, dev)
+        return self._gains[key]
 
 
 def _span_args(who: str, log_probs, input_lengths):
@@ -233,32 +353,57 @@ def _align_into(lp, il, T, N, C, row0, ld, labels, lens, t0, t1, peak):
     lib().ctc_align_spans(ptr(lp), ptr(il), T, N, C, int(row0), ld, ptr(labels), ptr(lens), ptr(t0), ptr(t1), ptr(peak), ptr(ws), ws.numel())
 
 
-def beam_decode_spans_async(log_probs: torch.Tensor, input_lengths, beam_width: int, out=None, row0: int = 0, scores: torch.Tensor | None = None):
+def _check_lm(who: str, lm, C=None):
+    if not isinstance(lm, LMGain):
+        raise RuntimeError(f"{who}: lm must be an LMGain (CharLM.gain(...)), got {type(lm).__name__}")
+    if C is not None and lm.C != C:
+        raise RuntimeError(f"{who}: the language model has {lm.C} classes, the log-probs {C}")
+
+
+def beam_decode_spans_async(log_probs: torch.Tensor, input_lengths, beam_width: int, out=None, row0: int = 0, scores: torch.Tensor | None = None,
+                            lm: LMGain | None = None, lm_scores: torch.Tensor | None = None):
     """``greedy_decode_spans_async`` for the best labelling under CTC prefix beam search with ``beam_width`` prefixes (DESIGN.md §18,
     ``ocrs_ctc_beam_decode``) and the spans of its forced alignment (``ocrs_ctc_align_spans``): the same span arrays, the same ``out`` /
     ``row0`` contract.  ``scores``: float32 device tensor with one entry per row of ``out`` that receives the labelling's log-mass at
     ``row0 + n`` (required with ``out``; without it a new one is made and copied with the arrays).  One beam launch and one align launch on
-    the current stream."""
+    the current stream.
+    ``lm`` (``ocrs_ctc_beam_decode_lm``): the gain table of a language model on the log-probs' device; the prefixes are ranked
+    by log-mass + gains, ``scores`` keeps its meaning and ``lm_scores``, under the rules of ``scores``, receives the gains of the labelling.
+    None: the plain beam, the launches and bytes it has always had."""
     who = "beam_decode_spans"
     _check_beam_width(who, beam_width)
     if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3:
         raise RuntimeError(f"{who}: expected (T,N,C) log-probs on the GPU (no CPU path)")
     if not 2 <= log_probs.shape[2] <= BEAM_MAX_CLASSES:
         raise RuntimeError(f"{who}: {log_probs.shape[2]} classes, supported are 2..{BEAM_MAX_CLASSES}")
+    if lm is not None:
+        _check_lm(who, lm, log_probs.shape[2])
+    elif lm_scores is not None:
+        raise RuntimeError(f"{who}: lm_scores without lm")
     lp, il, T, N, C, dev = _span_args(who, log_probs, input_lengths)
+    if lm is not None and lm.table.device != dev:
+        raise RuntimeError(f"{who}: the language model's table is on {lm.table.device}, the log-probs on {dev}")
     own = out is None
     if own:
         out, row0 = span_arrays(N, T, dev), 0
         scores = torch.empty(N, dtype=torch.float32, device=dev)
+        lm_scores = None if lm is None else torch.empty(N, dtype=torch.float32, device=dev)
     _, labels, t0, t1, peak, lens = out
     rows, ld = labels.shape
     if ld < T or row0 < 0 or row0 + N > rows or lens.numel() != rows:
         raise RuntimeError(f"{who}: rows {row0}..{row0 + N} of pitch {T} do not fit span arrays of {rows} rows of pitch {ld}")
     if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == rows):
         raise RuntimeError(f"{who}: scores must be a contiguous float32 device tensor with one entry per row ({rows})")
+    if lm is not None and not (isinstance(lm_scores, torch.Tensor) and lm_scores.is_cuda and lm_scores.dtype == torch.float32 and lm_scores.is_contiguous()
+                               and lm_scores.numel() == rows):
+        raise RuntimeError(f"{who}: lm_scores must be a contiguous float32 device tensor with one entry per row ({rows})")
     if N:
         ws = torch.empty(lib().ctc_beam_ws_bytes(T, N, beam_width), dtype=torch.uint8, device=dev)
-        lib().ctc_beam_decode(ptr(lp), ptr(il), T, N, C, beam_width, int(row0), ld, ptr(labels), ptr(lens), ptr(scores), ptr(ws), ws.numel())
+        if lm is None:
+            lib().ctc_beam_decode(ptr(lp), ptr(il), T, N, C, beam_width, int(row0), ld, ptr(labels), ptr(lens), ptr(scores), ptr(ws), ws.numel())
+        else:
+            lib().ctc_beam_decode_lm(ptr(lp), ptr(il), T, N, C, beam_width, ptr(lm.table), lm.order, int(row0), ld, ptr(labels), ptr(lens), ptr(scores),
+                                     ptr(lm_scores), ptr(ws), ws.numel())
         _align_into(lp, il, T, N, C, row0, ld, labels, lens, t0, t1, peak)
     if not own:
         return None
@@ -266,14 +411,19 @@ def beam_decode_spans_async(log_probs: torch.Tensor, input_lengths, beam_width: 
     host.copy_(out[0], non_blocking=True)
     scores_host = torch.empty(N, dtype=torch.float32, pin_memory=True)
     scores_host.copy_(scores, non_blocking=True)
+    lm_host = None
+    if lm is not None:
+        lm_host = torch.empty(N, dtype=torch.float32, pin_memory=True)
+        lm_host.copy_(lm_scores, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
-    return _BeamSpans(out, host, ev, N, T, scores, scores_host)
+    return _BeamSpans(out, host, ev, N, T, scores, scores_host, lm_scores, lm_host)
 
 
-def beam_decode_spans(log_probs: torch.Tensor, input_lengths, beam_width: int):
-    """(T,N,C) log-probs on the GPU -> list of N dicts ``labels``, ``t0``, ``t1``, ``peak`` (one entry per character) and ``score``."""
-    return beam_decode_spans_async(log_probs, input_lengths, beam_width).result()
+def beam_decode_spans(log_probs: torch.Tensor, input_lengths, beam_width: int, lm: LMGain | None = None):
+    """(T,N,C) log-probs on the GPU -> list of N dicts ``labels``, ``t0``, ``t1``, ``peak`` (one entry per character) and ``score``; with
+    ``lm`` also ``lm_score``."""
+    return beam_decode_spans_async(log_probs, input_lengths, beam_width, lm=lm).result()
 
 
 def ctc_align_spans(log_probs: torch.Tensor, input_lengths, labels, label_lengths):

@@ -8,7 +8,9 @@ whose arg-max runs look like text (tools/chars_time.py's generator), input lengt
 between stream events around that stage's entry point over ``--reps`` runs -- ``ocrs_ctc_beam_decode`` at W = 4, 16 and 32,
 ``ocrs_ctc_align_spans`` on the W = 16 labellings, ``ocrs_ctc_decode_spans`` -- all alternating in one loop, then the eval forward of a
 randomly initialised ``RecognitionModel`` on a 256 x 1 x 64 x 836 batch between events of its own, and the share of (forward + beam + align)
-that the W = 16 beam with its alignment takes.
+that the W = 16 beam with its alignment takes.  Then the language-model form: ``ocrs_ctc_beam_decode_lm`` with random gain
+tables of orders 1, 2 and 3 next to ``ocrs_ctc_beam_decode`` at W = 4, 16 and 64, the four entry points alternating in one loop of their own
+(no alignment launches), with the ratio of each order's median to the plain beam's at the same width.
 """
 from __future__ import annotations
 
@@ -29,6 +31,48 @@ from ocrs_models_amd.recognition import RecognitionModel  # noqa: E402
 from tools.chars_time import C, N, T, text_like_log_probs  # noqa: E402
 
 WIDTHS = (4, 16, 32)
+LM_WIDTHS, LM_ORDERS = (4, 16, 64), (1, 2, 3)
+
+
+def random_gain(order: int, dev) -> torch.Tensor:
+    """a dense table shaped like a smoothed model's: 0.7 log-softmax(1.5 N(0,1)) + 0.5 over the labels, column 0 (never read) at -inf"""
+    g = torch.Generator().manual_seed(order)
+    logp = torch.log_softmax(1.5 * torch.randn((C,) * (order - 1) + (C - 1,), generator=g, dtype=torch.float64), dim=-1)
+    table = torch.full((C,) * order, float("-inf"), dtype=torch.float64)
+    table[..., 1:] = 0.7 * logp + 0.5
+    return table.float().contiguous().to(dev)
+
+
+def time_lm(L, lp, in_len, reps: int, common: dict):
+    """plain and LM entry points alternating in one loop -> one JSON line per (W, order) and per W for the plain beam"""
+    dev = lp.device
+    tables = {o: random_gain(o, dev) for o in LM_ORDERS}
+    _, labels, _, _, _, lens = text.span_arrays(N, T, dev)
+    score, lm_score = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(L.ctc_beam_ws_bytes(T, N, max(LM_WIDTHS)), dtype=torch.uint8, device=dev)
+    p = [t.data_ptr() for t in (lp, in_len, labels, lens, score, lm_score, ws)]
+
+    def run():
+        for w in LM_WIDTHS:
+            L.ctc_beam_decode(p[0], p[1], T, N, C, w, 0, T, p[2], p[3], p[4], p[6], ws.numel())
+            for o in LM_ORDERS:
+                L.ctc_beam_decode_lm(p[0], p[1], T, N, C, w, tables[o].data_ptr(), o, 0, T, p[2], p[3], p[4], p[5], p[6], ws.numel())
+
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    L.timing = {s: [] for s in ("ctc_beam_decode", "ctc_beam_decode_lm")}
+    for _ in range(reps):
+        run()
+    torch.cuda.synchronize()
+    timing, L.timing = L.timing, None
+    for w in LM_WIDTHS:  # (W is argument 5 of both entry points, the order argument 7 of the LM one)
+        plain = statistics.median(e0.elapsed_time(e1) for e0, e1, a in timing["ctc_beam_decode"] if a[5] == w)
+        print(json.dumps({"stage": "ctc_beam_decode", "loop": "lm", "W": w, "gpu_ms": round(plain, 4), **common}), flush=True)
+        for o in LM_ORDERS:
+            ms = statistics.median(e0.elapsed_time(e1) for e0, e1, a in timing["ctc_beam_decode_lm"] if a[5] == w and a[7] == o)
+            print(json.dumps({"stage": "ctc_beam_decode_lm", "W": w, "order": o, "table_bytes": 4 * C ** o, "gpu_ms": round(ms, 4),
+                              "ratio_to_plain": round(ms / plain, 4), **common}), flush=True)
 
 
 def main():
@@ -68,6 +112,7 @@ def main():
     print(json.dumps({"stage": "ctc_align_spans", "gpu_ms": round(align, 4), **common}), flush=True)
     spans = statistics.median(e0.elapsed_time(e1) for e0, e1, _ in timing["ctc_decode_spans"])
     print(json.dumps({"stage": "ctc_decode_spans", "gpu_ms": round(spans, 4), **common}), flush=True)
+    time_lm(L, lp, in_len, args.reps, common)
 
     model = RecognitionModel(text.DEFAULT_ALPHABET).to(dev).eval()
     img = torch.rand(N, 1, 64, 4 * T, device=dev) - 0.5
