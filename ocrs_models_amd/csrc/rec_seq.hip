@@ -175,13 +175,17 @@ __global__ __launch_bounds__(256) void k_ctc_alpha(const float* __restrict__ lp,
 }
 
 // 'mean' reduction: loss = mean_n( nll_n / max(L_n, 1) )   (one block)
+// (the target length clamped as in the recursion kernels: a device-side length beyond the tensor extents divides by the L the lattice and the
+// gradient's scale were built with, so that the gradient stays the gradient of this loss)
 __global__ __launch_bounds__(256) void k_ctc_reduce(const float* __restrict__ nll, const long long* __restrict__ tg_len, float* __restrict__ loss,
-                                                    int N) {
+                                                    int N, int Lpad, int Smax) {
     __shared__ float s_sum[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < N; i += 256) {
-        const float L = (float)(tg_len[i] > 1 ? tg_len[i] : 1);
-        s += nll[i] / L;
+        int L = (int)tg_len[i];
+        L = L < 0 ? 0 : (L > Lpad ? Lpad : L);
+        L = 2 * L + 1 > Smax ? (Smax - 1) / 2 : L;
+        s += nll[i] / (float)(L > 1 ? L : 1);
     }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = s;
@@ -503,7 +507,7 @@ int ocrs_ctc_fwd(const float* lp, const int* targets, const long long* in_len, c
     } else {
         hipLaunchKernelGGL((k_ctc_alpha<false, 16>), dim3(N), dim3(256), 0, st, lp, targets, in_len, tg_len, (void*)alpha, (float*)nullptr, nll, T, N, C, Lpad, Smax);
     }
-    hipLaunchKernelGGL(k_ctc_reduce, dim3(1), dim3(256), 0, st, nll, tg_len, loss, N);
+    hipLaunchKernelGGL(k_ctc_reduce, dim3(1), dim3(256), 0, st, nll, tg_len, loss, N, Lpad, Smax);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
@@ -520,7 +524,7 @@ int ocrs_ctc_fwd_ab(const float* lp, const int* targets, const long long* in_len
         hipLaunchKernelGGL((k_ctc_ab<8>), grid, dim3(256), 0, st, lp, targets, in_len, tg_len, alpha, beta, nll, T, N, C, Lpad, Smax);
     else
         hipLaunchKernelGGL((k_ctc_ab<16>), grid, dim3(256), 0, st, lp, targets, in_len, tg_len, alpha, beta, nll, T, N, C, Lpad, Smax);
-    hipLaunchKernelGGL(k_ctc_reduce, dim3(1), dim3(256), 0, st, nll, tg_len, loss, N);
+    hipLaunchKernelGGL(k_ctc_reduce, dim3(1), dim3(256), 0, st, nll, tg_len, loss, N, Lpad, Smax);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
@@ -546,7 +550,7 @@ int ocrs_ctc_fwd_h16(const float* lp, const int* targets, const long long* in_le
     } else {
         hipLaunchKernelGGL((k_ctc_alpha<true, 16>), dim3(N), dim3(256), 0, st, lp, targets, in_len, tg_len, alpha16, rowmax, nll, T, N, C, Lpad, Smax);
     }
-    hipLaunchKernelGGL(k_ctc_reduce, dim3(1), dim3(256), 0, st, nll, tg_len, loss, N);
+    hipLaunchKernelGGL(k_ctc_reduce, dim3(1), dim3(256), 0, st, nll, tg_len, loss, N, Lpad, Smax);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
