@@ -535,6 +535,35 @@ int ocrs_rectify_crops_pages(const unsigned char* pages, long pages_bytes, const
                              const int* page_of_quad, const int* plan, const long long* totals, long max_tiles, float* packed, long packed_floats,
                              hipStream_t st);
 
+/* ------------------------------------------------------------------ tiles --------------------- */
+/* Detection in overlapping tiles by the rule of DESIGN.md §20 (csrc/ocr_tiles.hip; Python: inference.tile_plan, tile_batch,
+ * binarize_resize_tiles and the tile= argument of the detection drivers; restated in tests/tiles_ref.py).  The reference has no tiled path:
+ * both entry points stand where eval_detection.py:32-57 resizes the whole page, with a tile's window in the place of the page.  tiles [T][5]
+ * int = {page, y0, x0, th, tw}: window rows y0 .. y0 + th - 1 and columns x0 .. x0 + tw - 1 of that page; the tiles of a page are its tile
+ * rows times its tile columns, numbered row-major.  Page store and page_sizes as in "page batches".  Nothing here synchronises.
+ *
+ * resize(transform_image(page[:, y0:y0+th, x0:x0+tw]), [oh, ow], antialias=True) (eval_detection.py:32-34 on the window alone) for every
+ * tile, read from the uint8 store directly: out (T,1,oh,ow) fp32, bit-identical to ocrs_transform_image_u8 + ocrs_resize_aa of the window
+ * (the same two passes and weights; the uint8 -> [-0.5, 0.5] map is applied per tap).  Windows may differ in size; max_th >= every th.  Two
+ * launches for any T.  A tile that is not inside its page, is taller than max_th, or whose page is not inside pages_bytes is not written.
+ * T, max_th, oh <= 65535.  ws: ocrs_tile_batch_ws_floats(T, max_th, ow) floats (host only, no GPU needed; 0 = nothing to do). */
+long ocrs_tile_batch_ws_floats(int T, int max_th, int ow);
+int ocrs_tile_batch(const unsigned char* pages, long pages_bytes, const long long* page_offs, const int* page_sizes, int B, const int* tiles, int T, int max_th,
+                    float* ws, long ws_floats, float* out, int oh, int ow, hipStream_t st);
+/* The most tiles a page may have along one axis, and the largest pitch of the cut tables below. */
+#define OCRS_TILES_AXIS_MAX 64
+/* binarize_mask + resize(.., NEAREST) (eval_detection.py:54-57) of every tile's probabilities into the masks of the pages, one launch:
+ * prob (T,h,w) fp32 -> out (B,Hmax,Wmax) uint8, 0 outside (H_p, W_p).  Page p's tiles are tile_offs[p] .. tile_offs[p + 1] - 1 (tile_offs
+ * [B + 1] int), grids [B][2] int = (tile rows, tile columns), each in 1 .. max_axis; row_cuts / col_cuts [B][max_axis] int: tile row i owns
+ * the page rows after row_cuts[p][i - 1] up to row_cuts[p][i], the last one every row after the cut before it (columns alike).  The byte of
+ * page pixel (y, x) is prob[t][ys][xs] > threshold for its owner tile t, ys = min(int(floorf((float)(y - y0) * ((float)h / th))), h - 1) and
+ * xs alike: the arithmetic of ocrs_binarize_resize_nearest with the window in the place of the page, so a page with one tile gets the bytes
+ * of ocrs_binarize_resize_pages.  1 <= max_axis <= OCRS_TILES_AXIS_MAX, else error 1 and nothing is launched.  A tile index outside 0..T-1
+ * contributes background, and source indices are clamped to the tile: a bad table reads nothing outside prob. */
+int ocrs_binarize_resize_tiles(const float* prob, int T, int h, int w, const int* tiles, const int* tile_offs, const int* page_sizes, const int* grids,
+                               const int* row_cuts, const int* col_cuts, int max_axis, unsigned char* out, int B, int Hmax, int Wmax, float threshold,
+                               hipStream_t st);
+
 /* ------------------------------------------------------------------ reading order ------------- */
 /* The lines of every page in the order they are read, column by column, and where a new block starts, by the geometric rule of DESIGN.md §16
  * (csrc/reading_order.hip; Python: inference.reading_order; restated in tests/reading_ref.py).  line_quads [cap][4][2] fp32 and n_lines [1] int

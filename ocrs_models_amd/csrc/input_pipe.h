@@ -31,10 +31,14 @@ __device__ __forceinline__ float aa_w(const AaSpan& s, int j) {
     return s.total != 0.0f ? w / s.total : w;
 }
 // one output element of a pass: the span's weights against cnt inputs `stride` elements apart, src at the span's first input.  Every
-// antialiased resize (ocrs_resize_aa, ocrs_resize_aa_packed) sums through this one loop, which is what makes their results the same bits.
-__device__ __forceinline__ float aa_dot(const AaSpan& s, const float* __restrict__ src, size_t stride) {
+// antialiased resize (ocrs_resize_aa, ocrs_resize_aa_packed, ocrs_tile_batch) sums through this one loop, which is what makes their results
+// the same bits.  A uint8 source is a raw page: every tap goes through px_u8 first, the value transform_image would have stored for it.
+__device__ __forceinline__ float aa_tap(const float* p) { return *p; }
+__device__ __forceinline__ float aa_tap(const uint8_t* p) { return px_u8(*p); }
+template <typename S>
+__device__ __forceinline__ float aa_dot(const AaSpan& s, const S* __restrict__ src, size_t stride) {
     float acc = 0.0f;
-    for (int j = 0; j < s.cnt; ++j) acc += aa_w(s, j) * src[(size_t)j * stride];
+    for (int j = 0; j < s.cnt; ++j) acc += aa_w(s, j) * aa_tap(src + (size_t)j * stride);
     return acc;
 }
 

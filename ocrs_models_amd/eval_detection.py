@@ -1,7 +1,7 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
     python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]] [--chars] [--beam-width N]
-        [--lm FILE [--lm-weight A] [--lm-bonus B]]
+        [--lm FILE [--lm-weight A] [--lm-bonus B]] [--tile TH TW [--tile-overlap VH VW]]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
@@ -15,7 +15,9 @@ character range of each of its words (``"word_texts"``, ``"word_chars"``): ``inf
 ``--rec-model``) decodes by CTC prefix beam search with N prefixes instead of greedily and adds ``"log_prob"``, the log-mass of the text, to every
 object.  ``--lm FILE`` (with ``--beam-width``) loads a character language model written by ``python -m ocrs_models_amd.char_lm``
 and fuses ``A log P + B`` per character into the beam's ranking (``--lm-weight A``, default 1; ``--lm-bonus B``, default 0); every object
-gains ``"lm_score"``.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
+gains ``"lm_score"``.  ``--tile TH TW`` detects the page in overlapping tiles of TH x TW page pixels instead of squeezing it to the
+model's size whole (``detect_words(tile=...)``; ``--tile-overlap VH VW``, default an eighth of the tile); ``-text-probs.png`` then
+shows the tiles' probability maps side by side in their grid.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -69,6 +71,10 @@ def main(argv=None):
                         "beam's ranking; adds the text's language-model score to the JSON objects")
     parser.add_argument("--lm-weight", type=float, default=1.0, metavar="A", help="with --lm: the gain per character is A log P + B (default 1)")
     parser.add_argument("--lm-bonus", type=float, default=0.0, metavar="B", help="with --lm: see --lm-weight (default 0)")
+    parser.add_argument("--tile", type=int, nargs=2, default=None, metavar=("TH", "TW"), help="detect in overlapping tiles of TH x TW page pixels and "
+                        "compose one page mask from them, for pages much larger than the model's 800 x 600")
+    parser.add_argument("--tile-overlap", type=int, nargs=2, default=None, metavar=("VH", "VW"), help="with --tile: the overlap of neighbouring tiles "
+                        "in page pixels (default: an eighth of the tile)")
     args = parser.parse_args(argv)
     if args.reading_order and not args.lines:
         parser.error("--reading-order needs --lines")
@@ -78,6 +84,10 @@ def main(argv=None):
         parser.error("--beam-width must be in 1..64")
     if args.lm is not None and args.beam_width is None:
         parser.error("--lm needs --beam-width")
+    if args.tile_overlap is not None and args.tile is None:
+        parser.error("--tile-overlap needs --tile")
+    if args.tile is not None and (min(args.tile) < 1 or any(not 0 <= v < t for v, t in zip(args.tile_overlap or (0, 0), args.tile))):
+        parser.error("--tile must be at least 1 x 1 and --tile-overlap in 0 .. tile - 1 per axis")
 
     device = torch.device("cuda:0")
     model = DetectionModel().to(device)
@@ -92,13 +102,19 @@ def main(argv=None):
 
     torch.cuda.synchronize()
     start = time.time()
-    det = inference.detect_words(model, page)
+    tile = None if args.tile is None else tuple(args.tile)
+    det = inference.detect_words(model, page, tile=tile, overlap=None if args.tile_overlap is None else tuple(args.tile_overlap))
     torch.cuda.synchronize()
     print(f"Predicted text in {time.time() - start:.2f}s", file=sys.stderr)
 
     text_regions = page[0].float() / 255.0 * det["text_mask"].float()
     _to_pil(text_regions).save(f"{args.out_basename}-text-regions.png")
-    _to_pil(det["probs"]).save(f"{args.out_basename}-text-probs.png")
+    probs = det["probs"]
+    if tile is not None:  # (T,h,w) in row-major tile order -> the maps side by side in their grid
+        plan = inference.tile_plan(page.shape[1], page.shape[2], tile, None if args.tile_overlap is None else tuple(args.tile_overlap))
+        ny, nx = len(plan.rows.starts), len(plan.cols.starts)
+        probs = probs.view(ny, nx, *probs.shape[-2:]).permute(0, 2, 1, 3).reshape(ny * probs.shape[-2], nx * probs.shape[-1])
+    _to_pil(probs).save(f"{args.out_basename}-text-probs.png")
     quads = det["quads"].tolist()
     draw_quads(page_h, quads).save(f"{args.out_basename}-text-words.png")
 

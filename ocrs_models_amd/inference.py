@@ -59,6 +59,10 @@ Language model (``text.CharLM`` / ``LMGain``; restated for the t
 ``"log_prob"``, which keeps its meaning.  None, the default, is the plain beam unchanged; ``lm`` without ``beam_width`` is an argument error; the
 same waits.
 
+Tiles (csrc/ocr_tiles.hip, C ABI section "tiles"; restated for the tests in tests/tiles_ref.py).  With ``tile=(Th, Tw)`` the detection
+drivers cut the page into overlapping windows at (near) native resolution, run the detector on every window and compose ONE page mask from
+the tiles before the components are labelled; None, the default, is the whole-page path unchanged; the same waits.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
@@ -143,9 +147,16 @@ def expand_quads(quads: torch.Tensor, dist: float, counts: torch.Tensor | None =
     return out
 
 
-def detect_words(model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE) -> dict:
+def detect_words(model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE, tile=None, overlap=None,
+                 tile_batch: int = 16) -> dict:
     """eval_detection.py:32-67 for one (1,H,W) uint8 page on the device -> ``probs`` (h,w), ``text_mask`` (H,W) uint8, ``quads`` (N,4,2) in
-    page coordinates and ``n``.  The model must be in eval mode.  One host synchronisation (the component count)."""
+    page coordinates and ``n``.  The model must be in eval mode.  One host synchronisation (the component count).
+    ``tile = (Th, Tw)``: detect in overlapping tiles of that many page pixels instead of squeezing the whole page to ``size``:
+    every window of ``tile_plan(H, W, tile, overlap)`` is resized to ``size`` on its own, the eval forward runs over the tiles in chunks of
+    at most ``tile_batch``, and the tile probabilities are composed into ONE page mask -- every pixel from the tile that owns it -- before the
+    components are labelled, so a word across a seam stays one word.  ``probs`` becomes (T,h,w) and the dict gains ``tiles``, the (T,5) int32
+    device table ``(page, y0, x0, th, tw)``.  ``overlap=None``: an eighth of the tile.  ``tile=None``, the default, is the path above unchanged;
+    the same one synchronisation either way."""
     from .postprocess import extract_cc_quads_device
 
     _need_cuda(page_u8, "detect_words")
@@ -153,13 +164,23 @@ def detect_words(model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float 
         raise RuntimeError("detect_words: expected a (1,H,W) uint8 page")
     if model.training:
         raise RuntimeError("detect_words: the model must be in eval mode (model.eval())")
-    H, W = page_u8.shape[-2:]
-    img = resize(transform_image(page_u8), size)
-    with torch.inference_mode():
-        probs = model(img.unsqueeze(0))[0, 0]
-    text_mask = binarize_resize(probs, (H, W), threshold)
+    _check_tile_args("detect_words", tile, tile_batch)
+    H, W = (int(v) for v in page_u8.shape[-2:])
+    extra = {}
+    if tile is None:
+        img = resize(transform_image(page_u8), size)
+        with torch.inference_mode():
+            probs = model(img.unsqueeze(0))[0, 0]
+        text_mask = binarize_resize(probs, (H, W), threshold)
+    else:
+        if H < 1 or W < 1:
+            raise RuntimeError("detect_words: a tiled page needs at least one pixel")
+        dev = page_u8.device
+        store = (page_u8.contiguous().view(-1), _to_device_async([0], torch.int64, dev), _to_device_async([[H, W]], torch.int32, dev))  # the page is its own store
+        probs, masks, tables = _detect_tiles(model, store, [(H, W)], (H, W), size, threshold, tile, overlap, tile_batch, "detect_words")
+        text_mask, extra = masks[0], {"tiles": tables.tiles}
     quads = expand_quads(extract_cc_quads_device(text_mask), expand)
-    return {"probs": probs, "text_mask": text_mask, "quads": quads, "n": quads.shape[0]}
+    return {"probs": probs, "text_mask": text_mask, "quads": quads, "n": quads.shape[0], **extra}
 
 
 @dataclass
@@ -534,7 +555,7 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: TextLi
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
              output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, chars: bool = False,
-             beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
+             beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
     A page without components returns ``[]`` without launching the recogniser.  ``chars=True``: every dict also has ``"char_quads"``, the
     rectangle of every character of ``"text"`` on the page, and ``"char_log_probs"``, the recogniser's log-prob of each; the
@@ -542,9 +563,10 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thresh
     ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
     ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
     ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
-    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits."""
+    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits.
+    ``tile``, ``overlap``, ``tile_batch``: detect in overlapping tiles, as ``detect_words`` describes; the same waits."""
     _check_lm_args("ocr_page", beam_width, lm)
-    det = detect_words(det_model, page_u8, size, threshold, expand)
+    det = detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
     if det["n"] == 0:
         return []
     quads = det["quads"]
@@ -710,7 +732,7 @@ def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_hei
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
-              beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
+              beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
@@ -719,9 +741,10 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=MASK_SIZE, thres
     ``chars=True``: every dict keeps those keys and gains ``"char_quads"`` (one 4x2 list per character of ``"text"``: where it
     sits on the page), ``"char_log_probs"`` (the recogniser's log-prob of each), ``"word_chars"`` (parallel to ``"words"``: the ``[first, end]``
     of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits.  ``beam_width``: as in
-    ``read_lines``; ``lm``: as in ``read_lines``."""
+    ``read_lines``; ``lm``: as in ``read_lines``.  ``tile``, ``overlap``, ``tile_batch``: detect in overlapping
+    tiles, as ``detect_words`` describes; still three waits."""
     _check_lm_args("ocr_lines", beam_width, lm)
-    det = detect_words(det_model, page_u8, size, threshold, expand)
+    det = detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
     if det["n"] == 0:
         return []
     return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars,
@@ -831,28 +854,221 @@ def cc_quads_pages(text_masks: torch.Tensor):
     return gather_page_quads(raw, ncomp)
 
 
-def detect_words_batch(model, pages, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE) -> dict:
+# ------------------------------------------------------------------ tiled detection ------------------------------------------------------
+TILES_AXIS_MAX = 64  # OCRS_TILES_AXIS_MAX of include/ocrs_hip.h: the most tiles a page may have along one axis
+
+
+@dataclass
+class AxisPlan:
+    """The tiles of one axis of a page: tile i covers ``starts[i] .. starts[i] + lengths[i] - 1`` and owns the coordinates
+    ``cuts[i - 1] + 1 .. cuts[i]`` (``cuts[-1]`` read as -1); the last cut is the axis' last coordinate."""
+    starts: list[int]
+    lengths: list[int]
+    cuts: list[int]
+
+
+@dataclass
+class TilePlan:
+    """What ``tile_plan`` returns, all on the host: the page's size, its tile rows and tile columns, and ``windows``, the ``(y0, x0, th, tw)``
+    of its ``len(rows.starts) * len(cols.starts)`` tiles numbered row-major."""
+    H: int
+    W: int
+    rows: AxisPlan
+    cols: AxisPlan
+    windows: list[tuple[int, int, int, int]]
+
+
+def _need_int_pair(value, who: str, name: str) -> tuple[int, int]:
+    """an int (both axes) or a pair of ints, bools excluded -> (rows, columns)"""
+    pair = (value, value) if isinstance(value, int) else value
+    if (not isinstance(pair, (tuple, list)) or len(pair) != 2 or any(not isinstance(v, int) or isinstance(v, bool) for v in pair)):
+        raise RuntimeError(f"{who}: {name} must be an int or a pair of ints (rows, columns) in page pixels")
+    return int(pair[0]), int(pair[1])
+
+
+def _axis_plan(L: int, T: int, V: int) -> AxisPlan:
+    if L <= T:
+        return AxisPlan([0], [L], [L - 1])
+    n = -(-(L - V) // (T - V))
+    starts = [(i * (L - T)) // (n - 1) for i in range(n)]
+    cuts = [(starts[i] + starts[i + 1] + T - 1) // 2 for i in range(n - 1)] + [L - 1]
+    return AxisPlan(starts, [T] * n, cuts)
+
+
+def tile_plan(H: int, W: int, tile, overlap=None) -> TilePlan:
+    """The overlapping tiles of an H x W page by the rule of DESIGN.md §20, host integer arithmetic only.  ``tile = (Th, Tw)`` and
+    ``overlap = (Vh, Vw)`` in page pixels (an int stands for both axes), ``0 <= V < T`` per axis.  An axis no longer than the tile has one
+    tile of its own length; otherwise ``ceil((L - V) / (T - V))`` tiles of length T spread evenly from 0 to L - T, each owning the
+    coordinates up to the middle of its overlap with the next.  ``overlap=None`` means ``(Th // 8, Tw // 8)``: a stated default, not a
+    measured one -- no trained detector was at hand to tune it with."""
+    who = "tile_plan"
+    H, W = _need_int_pair((H, W), who, "the page size")
+    Th, Tw = _need_int_pair(tile, who, "tile")
+    if H < 1 or W < 1 or Th < 1 or Tw < 1:
+        raise RuntimeError(f"{who}: the page and the tile must have at least one pixel per axis")
+    Vh, Vw = (Th // 8, Tw // 8) if overlap is None else _need_int_pair(overlap, who, "overlap")
+    if not (0 <= Vh < Th and 0 <= Vw < Tw):
+        raise RuntimeError(f"{who}: overlap must be in 0 .. tile - 1 per axis, got {(Vh, Vw)} for tile {(Th, Tw)}")
+    rows, cols = _axis_plan(H, Th, Vh), _axis_plan(W, Tw, Vw)
+    windows = [(y0, x0, th, tw) for y0, th in zip(rows.starts, rows.lengths) for x0, tw in zip(cols.starts, cols.lengths)]
+    return TilePlan(H, W, rows, cols, windows)
+
+
+@dataclass
+class TileTables:
+    """The plans of B pages as the device tables of the C ABI section "tiles", all int32 views of one buffer (one host-to-device copy):
+    ``tiles`` (T,5) = page, y0, x0, th, tw; ``tile_offs`` (B+1,); ``page_sizes`` (B,2); ``grids`` (B,2) = tile rows, tile columns;
+    ``row_cuts`` / ``col_cuts`` (B,max_axis).  ``max_axis`` (the cut tables' pitch) and ``max_th`` (the tallest window) are host ints."""
+    tiles: torch.Tensor
+    tile_offs: torch.Tensor
+    page_sizes: torch.Tensor
+    grids: torch.Tensor
+    row_cuts: torch.Tensor
+    col_cuts: torch.Tensor
+    max_axis: int
+    max_th: int
+
+
+def tile_tables(plans, device) -> TileTables:
+    """A list of ``TilePlan``, one per page of a batch -> their ``TileTables`` on ``device``.  No synchronisation.  More than
+    ``TILES_AXIS_MAX`` tiles along an axis of a page is an argument error."""
+    plans = list(plans)
+    if not plans or any(not isinstance(p, TilePlan) for p in plans):
+        raise RuntimeError("tile_tables: expected a list of at least one TilePlan")
+    B = len(plans)
+    K = max(max(len(p.rows.starts), len(p.cols.starts)) for p in plans)
+    if K > TILES_AXIS_MAX:
+        raise RuntimeError(f"tile_tables: {K} tiles along one axis of a page; at most {TILES_AXIS_MAX} are supported (use a larger tile)")
+    tiles, offs, sizes, grids, rc, cc = [], [0], [], [], [], []
+    for b, p in enumerate(plans):
+        tiles += [v for y0, x0, th, tw in p.windows for v in (b, y0, x0, th, tw)]
+        offs.append(offs[-1] + len(p.windows))
+        sizes += [p.H, p.W]
+        grids += [len(p.rows.starts), len(p.cols.starts)]
+        rc += p.rows.cuts + [p.H - 1] * (K - len(p.rows.cuts))
+        cc += p.cols.cuts + [p.W - 1] * (K - len(p.cols.cuts))
+    T = offs[-1]
+    if T > 65535:
+        raise RuntimeError(f"tile_tables: {T} tiles in one batch; at most 65535 are supported")
+    buf = _to_device_async(tiles + offs + sizes + grids + rc + cc, torch.int32, device)
+    parts = torch.split(buf, [5 * T, B + 1, 2 * B, 2 * B, B * K, B * K])
+    return TileTables(parts[0].view(T, 5), parts[1], parts[2].view(B, 2), parts[3].view(B, 2), parts[4].view(B, K), parts[5].view(B, K), K,
+                      max(th for p in plans for _, _, th, _ in p.windows))
+
+
+def _need_store(pages_packed, page_offs, page_sizes, who: str) -> int:
+    """the page store of ``pack_pages`` -> B"""
+    for t in (pages_packed, page_offs, page_sizes):
+        _need_cuda(t, who)
+    if pages_packed.dtype != torch.uint8 or pages_packed.dim() != 1:
+        raise RuntimeError(f"{who}: expected the flat uint8 buffer of pack_pages")
+    B = page_offs.numel()
+    if page_offs.dtype != torch.int64 or page_sizes.dtype != torch.int32 or tuple(page_sizes.shape) != (B, 2):
+        raise RuntimeError(f"{who}: page_offs must be (B,) int64 and page_sizes (B,2) int32")
+    return B
+
+
+def tile_batch(pages_packed: torch.Tensor, page_offs: torch.Tensor, page_sizes: torch.Tensor, tiles: torch.Tensor, max_th: int, size) -> torch.Tensor:
+    """Every tile window of every page as the detector sees it (``ocrs_tile_batch``): the page store of ``pack_pages`` and a (T,5) int32
+    device table of tiles ``(page, y0, x0, th, tw)`` -> (T,1,oh,ow) fp32, tile t being ``resize(transform_image(page[:, y0:y0+th, x0:x0+tw]),
+    size)`` to the bit.  The windows are read from the uint8 store directly; ``max_th`` is at least the tallest window (it sizes the workspace).
+    Two launches for any T, no synchronisation."""
+    who = "tile_batch"
+    B = _need_store(pages_packed, page_offs, page_sizes, who)
+    _need_cuda(tiles, who)
+    if tiles.dtype != torch.int32 or tiles.dim() != 2 or tiles.shape[1] != 5:
+        raise RuntimeError(f"{who}: tiles must be (T,5) int32 on the device")
+    oh, ow = int(size[0]), int(size[1])
+    T, max_th = tiles.shape[0], int(max_th)
+    if oh < 1 or ow < 1 or max_th < 1:
+        raise RuntimeError(f"{who}: size and max_th must be at least 1")
+    out = torch.empty(T, 1, oh, ow, dtype=torch.float32, device=tiles.device)
+    if T:
+        L = lib()
+        ws_floats = L.tile_batch_ws_floats(T, max_th, ow)
+        ws = torch.empty(ws_floats, dtype=torch.float32, device=tiles.device)
+        L.tile_batch(ptr(pages_packed.contiguous()), pages_packed.numel(), ptr(page_offs.contiguous()), ptr(page_sizes.contiguous()), B, ptr(tiles.contiguous()), T,
+                     max_th, ptr(ws), ws_floats, ptr(out), oh, ow)
+    return out
+
+
+_tile_images = tile_batch  # (the drivers below take a keyword of this name: the size of the forward chunks)
+
+
+def binarize_resize_tiles(probs: torch.Tensor, tables: TileTables, canvas, threshold: float = 0.5) -> torch.Tensor:
+    """(T,h,w) fp32 tile probabilities and the ``TileTables`` of their B pages -> the uint8 canvas (B,Hmax,Wmax) of ``binarize_resize_pages``:
+    every page pixel takes ``probs[t] > threshold`` at the nearest source pixel of the tile t that owns it (``ocrs_binarize_resize_tiles``,
+    DESIGN.md §20), 0 outside the pages, in one launch.  A page with one tile gets the bytes of ``binarize_resize_pages``."""
+    who = "binarize_resize_tiles"
+    _need_cuda(probs, who)
+    if not isinstance(tables, TileTables):
+        raise RuntimeError(f"{who}: expected the TileTables of tile_tables")
+    T, B = tables.tiles.shape[0], tables.page_sizes.shape[0]
+    if probs.dtype != torch.float32 or probs.dim() != 3 or probs.shape[0] != T:
+        raise RuntimeError(f"{who}: expected (T,h,w) float32 probabilities, one map per tile")
+    _, h, w = probs.shape
+    Hmax, Wmax = int(canvas[0]), int(canvas[1])
+    out = torch.empty(B, Hmax, Wmax, dtype=torch.uint8, device=probs.device)
+    lib().binarize_resize_tiles(ptr(probs.contiguous()), T, h, w, ptr(tables.tiles), ptr(tables.tile_offs), ptr(tables.page_sizes), ptr(tables.grids),
+                                ptr(tables.row_cuts), ptr(tables.col_cuts), tables.max_axis, ptr(out), B, Hmax, Wmax, float(threshold))
+    return out
+
+
+def _check_tile_args(who: str, tile, chunk):
+    if tile is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1):
+        raise RuntimeError(f"{who}: tile_batch must be an int >= 1 (the most tiles per eval forward)")
+
+
+def _detect_tiles(model, store, sizes, canvas, size, threshold: float, tile, overlap, chunk: int, who: str):
+    """The tiled front half of detection for the pages of ``store`` (``sizes``: their host ``(H, W)``): plans, one ``ocrs_tile_batch``, the
+    eval forward over the tiles in chunks of at most ``chunk``, the composed canvas.  -> ``(probs (T,h,w), masks (B,*canvas), TileTables)``.
+    No host synchronisation."""
+    try:
+        plans = [tile_plan(H, W, tile, overlap) for H, W in sizes]
+    except RuntimeError as e:
+        raise RuntimeError(f"{who}: {e}") from None
+    tables = tile_tables(plans, store[0].device)
+    imgs = _tile_images(*store, tables.tiles, tables.max_th, size)
+    with torch.inference_mode():
+        parts = [model(imgs[a:a + chunk])[:, 0] for a in range(0, imgs.shape[0], chunk)]
+        probs = parts[0] if len(parts) == 1 else torch.cat(parts)
+    return probs, binarize_resize_tiles(probs, tables, canvas, threshold), tables
+
+
+def detect_words_batch(model, pages, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE, tile=None, overlap=None,
+                       tile_batch: int = 16, _store=None) -> dict:
     """``detect_words`` for a list of (1,H_p,W_p) uint8 device pages of any sizes: one eval forward of the (B,1,h,w) batch of
     ``resize(transform_image(page), size)``, the masks of all pages in one zero-padded canvas, ``ocrs_cc_quads`` on the canvas, the quads
     compacted and expanded.  -> ``probs`` (B,h,w), ``text_masks`` (B,Hmax,Wmax) uint8, ``quads`` (N_total,4,2) grouped by page in raster order,
     ``page_of_word`` (N_total,) int32, ``word_offs`` (B+1,) int32 and ``counts``, the words per page as a host list.  One host synchronisation
-    (the word offsets).  A canvas ``ocrs_cc_quads`` cannot take raises ValueError, as ``extract_cc_quads_device`` does."""
+    (the word offsets).  A canvas ``ocrs_cc_quads`` cannot take raises ValueError, as ``extract_cc_quads_device`` does.
+    ``tile``: detect every page in overlapping tiles of that many page pixels, as ``detect_words`` describes; the tiles of all
+    pages are cut in one call and pooled into the forward chunks; ``probs`` becomes (T,h,w) and the dict gains ``tiles`` (T,5) int32 and
+    ``tile_offs`` (B+1,) int32 (page p's tiles are ``tile_offs[p]:tile_offs[p + 1]``).  None, the default, is the path above unchanged; the
+    same one synchronisation either way."""
     pages = _check_pages(pages, "detect_words_batch")
     if not pages:
         raise RuntimeError("detect_words_batch: expected at least one page")
     if model.training:
         raise RuntimeError("detect_words_batch: the model must be in eval mode (model.eval())")
+    _check_tile_args("detect_words_batch", tile, tile_batch)
     dev = pages[0].device
     sizes = [(int(p.shape[1]), int(p.shape[2])) for p in pages]
     canvas = (max(h for h, _ in sizes), max(w for _, w in sizes))
     _cc_quads_pages_sizes(len(pages), *canvas)  # (refuses the batch before anything is launched)
-    img = torch.stack([resize(transform_image(p), size) for p in pages])
-    with torch.inference_mode():
-        probs = model(img)[:, 0]
-    text_masks = binarize_resize_pages(probs, _to_device_async(sizes, torch.int32, dev), canvas, threshold)
+    extra = {}
+    if tile is None:
+        img = torch.stack([resize(transform_image(p), size) for p in pages])
+        with torch.inference_mode():
+            probs = model(img)[:, 0]
+        text_masks = binarize_resize_pages(probs, _to_device_async(sizes, torch.int32, dev), canvas, threshold)
+    else:
+        store = pack_pages(pages) if _store is None else _store
+        probs, text_masks, tables = _detect_tiles(model, store, sizes, canvas, size, threshold, tile, overlap, tile_batch, "detect_words_batch")
+        extra = {"tiles": tables.tiles, "tile_offs": tables.tile_offs}
     flat, page_of_word, word_offs, counts = cc_quads_pages(text_masks)
     quads = expand_quads(flat, expand) if flat.shape[0] else flat
-    return {"probs": probs, "text_masks": text_masks, "quads": quads, "page_of_word": page_of_word, "word_offs": word_offs, "counts": counts}
+    return {"probs": probs, "text_masks": text_masks, "quads": quads, "page_of_word": page_of_word, "word_offs": word_offs, "counts": counts, **extra}
 
 
 def find_lines_pages(quads: torch.Tensor, page_of_word: torch.Tensor, word_offs: torch.Tensor, max_gap: float = 2.0, min_cos: float = 0.9) -> TextLines:
@@ -919,7 +1135,7 @@ def split_by_page(items: list, offs: list) -> list[list]:
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, threshold: float = 0.5, expand: float = SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
-              beam_width: int | None = None, lm: LMGain | None = None) -> list[list[dict]]:
+              beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16) -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
@@ -931,17 +1147,20 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=MASK_SIZE, t
     ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
     ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
     ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
-    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits."""
+    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits.
+    ``tile``, ``overlap``, ``tile_batch``: detect every page in overlapping tiles, as ``detect_words`` describes; the tiles of all
+    pages are pooled into the same forward chunks and cut from the page store the crops are cut from; the same waits."""
     _check_lm_args("ocr_pages", beam_width, lm)
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
     B = len(pages)
-    det = detect_words_batch(det_model, pages, size, threshold, expand)
+    store = None if tile is None else pack_pages(pages)
+    det = detect_words_batch(det_model, pages, size, threshold, expand, tile, overlap, tile_batch, store)
     words = det["quads"]
     if words.shape[0] == 0:
         return [[] for _ in range(B)]
-    packed_pages, page_offs, page_sizes = pack_pages(pages)
+    packed_pages, page_offs, page_sizes = pack_pages(pages) if store is None else store
     word_offs_h = [0]
     for c in det["counts"]:
         word_offs_h.append(word_offs_h[-1] + c)
