@@ -448,7 +448,7 @@ int ocrs_mask_metrics(const void* pred, int pred_kind, const void* target, int t
                       hipStream_t st);
 
 /* ------------------------------------------------------------------ page inference ------------ */
-/* From a page to recognition batches (csrc/ocr_infer.hip; Python: ocrs_models_amd/inference.py, which states the geometry rules).  Quads are
+/* From a page to recognition batches (csrc/ocr_infer.hip; Python: ocrs_models_amd/inference/, which states the geometry rules).  Quads are
  * [..][4][2] fp32 (x, y) in pixel-centre coordinates, 16-byte aligned.  Nothing here synchronises: counts are device-side with a capacity.
  *
  * binarize_mask + resize(.., InterpolationMode.NEAREST) (ocrs_models/eval_detection.py:54-57) in one launch: prob (B,1,h,w) fp32 ->

@@ -5,7 +5,7 @@
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
-on the page).  With ``--rec-model`` the words are recognised too (``inference.ocr_page``'s stages) and printed, one JSON object per line.
+on the page).  With ``--rec-model`` the words are recognised too (``inference.read_words``) and printed, one JSON object per line.
 With ``--lines`` the words are grouped into text lines first (``inference.find_lines``): ``-text-lines.png`` shows the line quads, and with
 ``--rec-model`` every LINE is recognised (``inference.read_lines``) and printed as one JSON object with its quad, its text and its words' quads
 in reading order, instead of the words.  ``--lines --reading-order`` prints those objects in the page's reading order (column by column,
@@ -140,23 +140,8 @@ def main(argv=None):
             line_quads = found.quads[:int(found.n_lines)].tolist()
         draw_quads(page_h, line_quads).save(f"{args.out_basename}-text-lines.png")
     elif rec is not None:
-        plan = inference.crop_plan(det["quads"])
-        packed = inference.rectify_crops(page, det["quads"], plan)
-        batches = inference.crops_to_batches(packed, plan)
-        if args.chars:
-            spans = inference.decode_crop_spans(rec, batches, args.beam_width, lm)
-            texts, chars, _ = inference.chars_to_host(spans, inference.char_boxes(det["quads"], plan, spans))
-            for quad, p in zip(quads, batches[2]):
-                print(json.dumps({"quad": quad, "text": texts[p], **chars[p]}))
-        elif lm is not None:
-            for quad, text, score, lm_score in zip(quads, *inference.recognize_crops(rec, batches, beam_width=args.beam_width, lm=lm)):
-                print(json.dumps({"quad": quad, "text": text, "log_prob": score, "lm_score": lm_score}))
-        elif args.beam_width is not None:
-            for quad, text, score in zip(quads, *inference.recognize_crops(rec, batches, beam_width=args.beam_width)):
-                print(json.dumps({"quad": quad, "text": text, "log_prob": score}))
-        else:
-            for quad, text in zip(quads, inference.recognize_crops(rec, batches)):
-                print(json.dumps({"quad": quad, "text": text}))
+        for word in inference.read_words(rec, page, det["quads"], chars=args.chars, beam_width=args.beam_width, lm=lm):
+            print(json.dumps(word))
 
 
 if __name__ == "__main__":

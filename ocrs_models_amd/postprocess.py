@@ -19,7 +19,7 @@ The same contract on the GPU (csrc/postprocess.hip, C ABI ``ocrs_cc_quads`` / ``
 * ``extract_cc_quads_device(mask)``: the quads of one device mask, on the device (one sync, to read the count).
 * ``box_match_metrics_device(pred_quads, target_quads)``: ``box_match_metrics`` of two device quad sets.
 * ``expand_quads_device(quads, dist)``: ``expand_quads`` (postprocess.py:39-76) of a device quad set (csrc/ocr_infer.hip; the rule, and what
-  of it is UNPINNED without shapely, is in ocrs_models_amd/inference.py's docstring).
+  of it is UNPINNED without shapely, is in ocrs_models_amd/inference/__init__.py's docstring).
 
 Components, their numbering and the hull vertex sequence are identical to the host's (integer work); the calipers, clipping and areas
 repeat the host's fp64 operations in the host's order, so quads agree to rounding and the four counts agree exactly in practice (DESIGN.md

@@ -122,8 +122,21 @@ def span_arrays(rows: int, ld: int, device):
     ``labels | t0 | t1 | peak | lens`` (so that one copy brings all of them to the host) -> ``(buf, labels, t0, t1, peak, lens)``; ``peak`` is
     the float32 view of its part.  Not initialised: entries of a row from its length on are never written."""
     buf = torch.empty(4 * rows * ld + rows, dtype=torch.int32, device=device)
-    part = [buf[k * rows * ld:(k + 1) * rows * ld].view(rows, ld) for k in range(4)]
-    return buf, part[0], part[1], part[2], part[3].view(torch.float32), buf[4 * rows * ld:]
+    return (buf, *span_views(buf, rows, ld))
+
+
+def span_views(buf: torch.Tensor, rows: int, ld: int):
+    """The one statement of the span buffer's layout: a flat int32 buffer ``labels | t0 | t1 | peak | lens`` for ``rows`` samples at a row
+    pitch of ``ld``, on the device or its copy on the host -> the views ``(labels, t0, t1, peak, lens)``; the first four are (rows, ld),
+    ``peak`` the float32 view of its part, ``lens`` (rows,).  Nothing is copied: the views alias ``buf``."""
+    cells = rows * ld
+    part = buf[:4 * cells].view(4, rows, ld)
+    return part[0], part[1], part[2], part[3].view(torch.float32), buf[4 * cells:]
+
+
+def span_lengths(lens: torch.Tensor) -> list[int]:
+    """``lens`` of ``span_views`` on the host as a list; -1, a beam row without any labelling of finite mass, reads as an empty row"""
+    return [max(n, 0) for n in lens.tolist()]
 
 
 class _DecodeSpans:
@@ -135,11 +148,9 @@ class _DecodeSpans:
     def result(self):
         """list of N dicts ``labels``, ``t0``, ``t1`` (int lists) and ``peak`` (float list), one entry per character (waits for the copy only)"""
         self.event.synchronize()
-        N, ld = self.N, self.ld
-        part = [self.host[k * N * ld:(k + 1) * N * ld].view(N, ld) for k in range(4)]
-        lens = [max(n, 0) for n in self.host[4 * N * ld:].tolist()]  # (-1: a beam row without any labelling of finite mass)
-        labels, t0, t1, peak = part[0].tolist(), part[1].tolist(), part[2].tolist(), part[3].view(torch.float32).tolist()
-        return [{"labels": labels[i][:n], "t0": t0[i][:n], "t1": t1[i][:n], "peak": peak[i][:n]} for i, n in enumerate(lens)]
+        *part, lens = span_views(self.host, self.N, self.ld)
+        labels, t0, t1, peak = (p.tolist() for p in part)
+        return [{"labels": labels[i][:n], "t0": t0[i][:n], "t1": t1[i][:n], "peak": peak[i][:n]} for i, n in enumerate(span_lengths(lens))]
 
 
 def greedy_decode_spans_async(log_probs: torch.Tensor, input_lengths, out=None, row0: int = 0):

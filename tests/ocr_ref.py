@@ -1,4 +1,4 @@
-"""CPU restatement of the page-inference rules (ocrs_models_amd/inference.py's docstring) in plain numpy / torch, for the tests of
+"""CPU restatement of the page-inference rules (ocrs_models_amd/inference/__init__.py's docstring) in plain numpy / torch, for the tests of
 csrc/ocr_infer.hip.  Nothing here calls the package's kernels."""
 from __future__ import annotations
 

@@ -1,4 +1,4 @@
-"""Page inference on the GPU (csrc/ocr_infer.hip, ocrs_models_amd/inference.py) against the CPU restatement of its rules (tests/ocr_ref.py),
+"""Page inference on the GPU (csrc/ocr_infer.hip, ocrs_models_amd/inference/) against the CPU restatement of its rules (tests/ocr_ref.py),
 torch's CPU operators and the package's own single-crop functions.
 
 Tolerances.  binarize_resize, the pad columns, chunking and the per-crop resize are BIT-EXACT (a compare and an index rule; the same filter
@@ -288,6 +288,27 @@ def test_ocr_page_of_an_empty_page(dev, det_model):
     plan = inf.crop_plan(det["quads"])
     batches, widths, perm = inf.crops_to_batches(inf.rectify_crops(page, det["quads"], plan), plan)
     assert batches == [] and widths == [] and perm == []
+
+
+@pytest.mark.parametrize("opts", [{}, {"chars": True, "beam_width": 4}], ids=["greedy", "chars+beam4"])
+def test_read_words_is_the_half_of_ocr_page_after_detection(dev, rec_model, opts):
+    """30 bars of five widths, so the width-sorted crops are no run of the raster order, in chunks of 8: read_words on detect_words' quads
+    returns what ocr_page returns for the page, dict for dict"""
+    from ocrs_models_amd import inference as inf
+    from tests.test_lines_gpu import bar_page
+
+    bars = [(15 + 52 * c, 18 + 40 * r, 24 + 4 * ((7 * (6 * r + c)) % 5), 12) for r in range(5) for c in range(6)]
+    page, det_model = bar_page(230, 340, bars, dev)
+    det = inf.detect_words(det_model, page, size=(230, 340))
+    assert det["n"] == 30
+    perm = inf.crop_plan(det["quads"]).host_perm()
+    assert sorted(perm) == list(range(30)) and perm != list(range(30))
+    want = inf.ocr_page(det_model, rec_model, page, size=(230, 340), max_batch=8, **opts)
+    got = inf.read_words(rec_model, page, det["quads"], max_batch=8, **opts)
+    keys = ["quad", "text"] + (["char_quads", "char_log_probs", "log_prob"] if opts else [])
+    assert len(got) == 30 and all(list(d) == keys for d in got)
+    assert got == want
+    assert torch.equal(torch.tensor([d["quad"] for d in got]), det["quads"].cpu())
 
 
 # ------------------------------------------------------------------ CLI ----------------------------------------------------------------

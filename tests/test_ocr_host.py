@@ -1,4 +1,4 @@
-"""CPU-only checks of the page-inference path (csrc/ocr_infer.hip, ocrs_models_amd/inference.py): the ABI is declared and exported, the size
+"""CPU-only checks of the page-inference path (csrc/ocr_infer.hip, ocrs_models_amd/inference/): the ABI is declared and exported, the size
 query answers without a GPU, the CPU restatement of the geometry rules (tests/ocr_ref.py) gives the closed-form answers the rules imply, and
 the device functions have no CPU fallback."""
 import ctypes
@@ -173,6 +173,124 @@ def test_plan_chunks_matches_the_restated_batching_rule():
         hist = np.bincount(ows, minlength=801).tolist()
         assert plan_chunks(hist, max_batch, unit) == chunks
     assert plan_chunks([0] * 801, 256, 64) == []
+
+
+# ------------------------------------------------------------------ span buffer layout --------------------------------------------------
+def test_span_views_state_the_buffer_layout_on_a_cpu_buffer():
+    """labels | t0 | t1 | peak | lens: what is written through the views of ``span_arrays`` is read back through ``span_views`` of the flat
+    buffer and through the host reader of the decode handles; a beam row without a labelling (-1) and an empty row both read as empty."""
+    from ocrs_models_amd import text
+
+    rows, ld = 3, 4
+    buf, labels, t0, t1, peak, lens = text.span_arrays(rows, ld, "cpu")
+    assert buf.dtype == torch.int32 and buf.numel() == 4 * rows * ld + rows
+    buf.fill_(-7)
+    labels[0, :2] = torch.tensor([5, 9], dtype=torch.int32)
+    t0[0, :2] = torch.tensor([0, 3], dtype=torch.int32)
+    t1[0, :2] = torch.tensor([1, 3], dtype=torch.int32)
+    peak[0, :2] = torch.tensor([-0.125, -1.5])
+    lens.copy_(torch.tensor([2, 0, -1], dtype=torch.int32))
+    # the views alias the one buffer, part after part
+    assert buf[:2].tolist() == [5, 9] and buf[rows * ld:rows * ld + 2].tolist() == [0, 3] and buf[2 * rows * ld:2 * rows * ld + 2].tolist() == [1, 3]
+    assert buf[3 * rows * ld:3 * rows * ld + 2].view(torch.float32).tolist() == [-0.125, -1.5] and buf[4 * rows * ld:].tolist() == [2, 0, -1]
+    got = text.span_views(buf.clone(), rows, ld)  # (the pinned copy of a device buffer is such a flat tensor)
+    assert [tuple(v.shape) for v in got] == [(rows, ld)] * 4 + [(rows,)]
+    assert got[3].dtype == torch.float32 and all(v.dtype == torch.int32 for v in got[:3] + got[4:])
+    assert got[0][0, :2].tolist() == [5, 9] and got[1][0, :2].tolist() == [0, 3] and got[2][0, :2].tolist() == [1, 3]
+    assert got[3][0, :2].tolist() == [-0.125, -1.5]
+    assert got[4].tolist() == [2, 0, -1] and text.span_lengths(got[4]) == [2, 0, 0]
+
+    class Arrived:
+        def synchronize(self):
+            pass
+
+    handle = text._DecodeSpans((buf, labels, t0, t1, peak, lens), buf.clone(), Arrived(), rows, ld, None)
+    empty = {"labels": [], "t0": [], "t1": [], "peak": []}
+    assert handle.result() == [{"labels": [5, 9], "t0": [0, 3], "t1": [1, 3], "peak": [-0.125, -1.5]}, empty, empty]
+
+
+# ------------------------------------------------------------------ result assembly -----------------------------------------------------
+def _quad(i):
+    return [[10.0 * i, 0.0], [10.0 * i + 8, 0.0], [10.0 * i + 8, 4.0], [10.0 * i, 4.0]]
+
+
+_WORDS = [_quad(i) for i in range(5)]                 # words 0..2 on page 0, 3..4 on page 1, in raster order
+_LINE_QUADS = [_quad(20), _quad(21), _quad(22)]       # lines 0, 1 on page 0, line 2 on page 1
+_LINES = (_LINE_QUADS, [2, 0, 1, 3, 4], [0, 2, 3, 5])  # line 0 = words 2, 0 (chain order is not raster order), line 1 = word 1, line 2 = words 3, 4
+_READING = ([1, 0, 2], [0, 1, 0], [0, 2, 3])           # page 0 is read line 1, then line 0 in a block of its own; page 1 starts again at block 0
+_LINE_TEXTS = ["ab cd", "ef", "gh i"]
+_LINE_RANGES = [[3, 5], [0, 2], [0, 2], [0, 2], [3, 4]]  # by flat word index
+_WORD_TEXTS = ["w0", "w1", "w2", "w3", "w4"]
+_OPTIONS = [dict(), dict(beam=True), dict(beam=True, lm=True), dict(chars=True), dict(chars=True, beam=True), dict(chars=True, beam=True, lm=True)]
+
+
+def _record(texts, perm, ranges=None, chars=False, beam=False, lm=False):
+    """the ``Decoded`` of crops whose rows arrive in width-sorted order: row ``perm[i]`` is quad i's.  -> (record, the per-quad values)"""
+    from ocrs_models_amd.inference import Decoded
+
+    n = len(texts)
+    assert sorted(perm) == list(range(n)) and perm != list(range(n))
+    want = {"text": texts}
+    if chars:
+        want["char_quads"] = [[_quad(100 * i + k) for k in range(len(t))] for i, t in enumerate(texts)]
+        want["char_log_probs"] = [[-0.25 * (k + 1) - i for k in range(len(t))] for i, t in enumerate(texts)]
+    if beam:
+        want["log_prob"] = [-1.5 - i for i in range(n)]
+    if lm:
+        want["lm_score"] = [-0.5 * i for i in range(n)]
+    rows = {key: [None] * n for key in want}
+    for i, p in enumerate(perm):
+        for key in want:
+            rows[key][p] = want[key][i]
+    char_rows = [{"char_quads": q, "char_log_probs": s} for q, s in zip(rows["char_quads"], rows["char_log_probs"])] if chars else None
+    rec = Decoded.in_quad_order(perm, rows["text"], rows.get("log_prob"), rows.get("lm_score"), char_rows, ranges if chars else None)
+    return rec, want
+
+
+@pytest.mark.parametrize("opts", _OPTIONS, ids=lambda o: "+".join(o) or "greedy")
+def test_assemble_results_word_dicts(opts):
+    from ocrs_models_amd.inference import assemble_results
+
+    rec, want = _record(_WORD_TEXTS, [3, 0, 4, 1, 2], **opts)
+    keys = ["quad", "text"] + [k for k in ("char_quads", "char_log_probs", "log_prob", "lm_score") if k in want]
+    got = assemble_results(rec, _WORDS)
+    assert got == [{"quad": _WORDS[i], **{k: want[k][i] for k in keys[1:]}} for i in range(5)]
+    assert all(list(d) == keys for d in got)
+
+
+@pytest.mark.parametrize("reading", [False, True], ids=["line-order", "reading-order"])
+@pytest.mark.parametrize("opts", _OPTIONS, ids=lambda o: "+".join(o) or "greedy")
+def test_assemble_results_line_dicts(opts, reading):
+    from ocrs_models_amd.inference import assemble_results
+
+    rec, want = _record(_LINE_TEXTS, [2, 0, 1], _LINE_RANGES, **opts)
+    words_of = [[_WORDS[2], _WORDS[0]], [_WORDS[1]], [_WORDS[3], _WORDS[4]]]
+    lines = []
+    for l in range(3):
+        d = {"quad": _LINE_QUADS[l], "text": _LINE_TEXTS[l], "words": words_of[l]}
+        d.update({k: want[k][l] for k in ("char_quads", "char_log_probs", "log_prob", "lm_score") if k in want})
+        lines.append(d)
+    keys = ["quad", "text", "words"] + [k for k in ("char_quads", "char_log_probs", "log_prob", "lm_score") if k in want]
+    if opts.get("chars"):
+        for d, rg, texts in zip(lines, ([[0, 2], [3, 5]], [[0, 2]], [[0, 2], [3, 4]]), (["ab", "cd"], ["ef"], ["gh", "i"])):
+            d["word_chars"], d["word_texts"] = rg, texts
+        keys += ["word_chars", "word_texts"]
+    if reading:
+        lines = [{**lines[1], "block": 0}, {**lines[0], "block": 1}, {**lines[2], "block": 0}]  # block restarts on the second page
+        keys += ["block"]
+    got = assemble_results(rec, _WORDS, _LINES, _READING if reading else None)
+    assert got == lines
+    assert all(list(d) == keys for d in got)
+
+
+def test_assemble_results_needs_nothing_from_the_gpu_side():
+    import ast
+    import inspect
+
+    from ocrs_models_amd.inference import assemble
+
+    imported = [n for n in ast.walk(ast.parse(inspect.getsource(assemble))) if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert [getattr(n, "module", None) for n in imported] == ["__future__"]
 
 
 # ------------------------------------------------------------------ no CPU path ---------------------------------------------------------
