@@ -619,6 +619,42 @@ int ocrs_word_chars(const float* words, long wcap, const float* line_quads, cons
                     const int* plan, long rows, int ld, const int* labels, const int* lens, const float* s0, const float* s1, int space, int* word_chars,
                     hipStream_t st);
 
+/* ------------------------------------------------------------------ chain crops -------------- */
+/* Line crops cut along the polyline of the line's words by the rule of DESIGN.md §21 (csrc/line_chain.hip, the plan in csrc/ocr_infer.hip;
+ * Python: inference/chain.py; restated in tests/chain_ref.py), in the place of the line quad's rectangle.  words [wcap][4][2] and the line
+ * table (n_lines [1], line_offsets [cap + 1], word_order) as the "text lines" or "page batches" stages wrote them, cap <= wcap.  A line whose
+ * offsets do not describe words inside 0..wcap-1 is skipped by every kernel here.  Nothing synchronises, there are no atomics: equal input
+ * gives equal bytes.  Zero lines launch nothing.
+ *
+ * spine [2 wcap][8] fp32, 16-byte aligned: row 2p is the word at chain position p (line l's words are the positions line_offsets[l] ..
+ * line_offsets[l + 1] - 1), row 2p + 1 the gap behind it; each {start, len, A.x, A.y, dir.x, dir.y, 0, 0}.  A word's A is the mid-point of its left
+ * edge and dir its axis u; a gap leads from the right mid-point of its word to the left one of the next (len 0 and dir 0 where that would go
+ * backwards: the spine jumps); the last word of a line has an all-zero gap row.  start = the running fp32 sum of the lengths before, in chain
+ * order.  line_dims [cap][2] fp32, 16-byte aligned: S = the sum of all lengths, H = the largest word height.  Rows of lines from n_lines on are
+ * not written.  One wave per line, 64 words per round. */
+int ocrs_line_spines(const float* words, long wcap, const int* n_lines, long cap, const int* line_offsets, const int* word_order, float* spine, float* line_dims,
+                     hipStream_t st);
+/* ocrs_crop_plan with (h, w) = (clamp(rint(H), 1, 32768), clamp(rint(S), 1, 32768)) of line_dims in the place of a quad's crop frame: the same
+ * kernel, table and totals. */
+int ocrs_crop_plan_dims(const float* line_dims, const int* count, long cap, int output_height, int* plan, long long* totals, hipStream_t st);
+/* ocrs_rectify_crops along the spine: sample (y, x) of line l's (h, w) crop is the page at P(s, t), s = (x + 0.5) / w * S, t = ((y + 0.5) / h - 0.5) * H,
+ * on the last segment of the line with start <= s; the same tiling, clamp and four-tap blend.  plan / totals: ocrs_crop_plan_dims'. */
+int ocrs_rectify_chain(const unsigned char* page, int H, int W, const float* spine, const float* line_dims, const int* line_offsets, long wcap, const int* plan,
+                       const long long* totals, long max_tiles, float* packed, long packed_floats, hipStream_t st);
+/* The same from a page store, as ocrs_rectify_crops_pages: line l is cut from page page_of_line[l]; a crop's bytes are those ocrs_rectify_chain
+ * writes for it from its own page. */
+int ocrs_rectify_chain_pages(const unsigned char* pages, long pages_bytes, const long long* page_offs, const int* page_sizes, int B, const float* spine,
+                             const float* line_dims, const int* line_offsets, long wcap, const int* page_of_line, const int* plan, const long long* totals,
+                             long max_tiles, float* packed, long packed_floats, hipStream_t st);
+/* ocrs_char_boxes for chain crops, same rows and arrays: s0 = (float)a0 / (float)ow * S, s1 likewise (positions along the spine);
+ * char_quads = P(s0, -H/2), P(s1, -H/2), P(s1, +H/2), P(s0, +H/2): a quadrilateral that follows the spine. */
+int ocrs_char_boxes_chain(const float* spine, const float* line_dims, const int* line_offsets, long wcap, const int* plan, long cap, long rows, int ld,
+                          const int* lens, const int* t0, const int* t1, float* s0, float* s1, float* char_quads, hipStream_t st);
+/* ocrs_word_chars for chain crops, same output: word j of a chain owns the characters whose centre 0.5f * (s0 + s1) lies in [b_{j-1}, b_j),
+ * b_j = start(word j + 1) - 0.5f * len(gap j) from the spine table (non-decreasing along a chain), less the `space` labels at both ends. */
+int ocrs_word_chars_chain(const float* spine, long wcap, const int* n_lines, long cap, const int* line_offsets, const int* word_order, const int* plan, long rows,
+                          int ld, const int* labels, const int* lens, const float* s0, const float* s1, int space, int* word_chars, hipStream_t st);
+
 /* ------------------------------------------------------------------ beam search -------------- */
 /* CTC prefix beam search and forced alignment by the rule of DESIGN.md §18 (csrc/ctc_beam.hip; Python: text.beam_decode_spans,
  * text.ctc_align_spans; restated in tests/beam_ref.py).  Both generalise ctc_greedy_decode_text (datasets/util.py:147-177), the greedy rule:

@@ -11,6 +11,7 @@
 //                   every word finds the two ends of its range by bisecting the characters' centres (they are non-decreasing), then trims
 //
 // Integer and latency work over small arrays: no LDS, no atomics, nothing synchronises; equal input gives equal bytes.
+#include "char_range.h"
 #include "crop_frame.h"
 
 namespace {
@@ -164,15 +165,7 @@ __device__ __forceinline__ void word_extent(const float* __restrict__ q, const C
     lo = fminf(fminf(p0, p1), fminf(p2, p3));
     hi = fmaxf(fmaxf(p0, p1), fmaxf(p2, p3));
 }
-// #{ k < n : centre of character k < b }; the centres 0.5f * (s0 + s1) are non-decreasing in k
-__device__ __forceinline__ int chars_below(const float* __restrict__ s0, const float* __restrict__ s1, int n, float b) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (0.5f * (s0[mid] + s1[mid]) < b) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (chars_below() and store_word_range() are char_range.h's: k_word_chars_chain of line_chain.hip ends the same way)
 // One wave per line l (four lines per workgroup), lane j of round r holds word 64 r + j of the line's chain.  B_j, the running maximum of the
 // boundaries b_j = 0.5f * (hi_j + lo_{j+1}), is an inclusive max scan across the lanes with the last lane's value carried into the next round.
 // Word j owns the characters with B_{j-1} <= centre < B_j (no lower bound for the first word, no upper bound for the last), then gives up
@@ -223,10 +216,8 @@ __global__ __launch_bounds__(256) void k_word_chars(const float* __restrict__ wo
         carry = __shfl(B, 63, 64);
         if (w >= 0) {
             int first = j == 0 ? 0 : chars_below(c0, c1, nch, below);
-            int end = j == m - 1 ? nch : chars_below(c0, c1, nch, B);
-            while (first < end && lab[first] == space) ++first;
-            while (end > first && lab[end - 1] == space) --end;
-            *reinterpret_cast<int2*>(word_chars + 2 * w) = make_int2(first, end);
+            const int end = j == m - 1 ? nch : chars_below(c0, c1, nch, B);
+            store_word_range(lab, first, end, space, word_chars, w);
         }
     }
 }

@@ -7,6 +7,8 @@ struct CropFrame {
     float ox, oy, ux, uy, lng, sht;  // origin corner, unit width axis u (v = (-uy, ux)), side lengths along u and v
     int h, w;
 };
+// rows or columns of a crop whose side is `len` page pixels long (fmaxf also turns a NaN length into 1)
+__device__ __forceinline__ int crop_len(float len) { return (int)fminf(fmaxf(rintf(len), 1.0f), 32768.0f); }
 __device__ __forceinline__ CropFrame crop_frame(const float* __restrict__ q) {
     const float4 a = reinterpret_cast<const float4*>(q)[0], c = reinterpret_cast<const float4*>(q)[1];
     const float xs[4] = {a.x, a.z, c.x, c.z}, ys[4] = {a.y, a.w, c.y, c.w};
@@ -29,7 +31,7 @@ __device__ __forceinline__ CropFrame crop_frame(const float* __restrict__ q) {
         if (p < best) best = p, k = j;
     }
     f.ox = xs[k], f.oy = ys[k];
-    f.w = (int)fminf(fmaxf(rintf(f.lng), 1.0f), 32768.0f);  // (fmaxf also turns a NaN length into 1)
-    f.h = (int)fminf(fmaxf(rintf(f.sht), 1.0f), 32768.0f);
+    f.w = crop_len(f.lng);
+    f.h = crop_len(f.sht);
     return f;
 }

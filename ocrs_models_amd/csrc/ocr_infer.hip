@@ -15,12 +15,11 @@
 //
 // All of them are small and byte-bound: no LDS tiles, no MFMA; coalesced 4..16-byte vector accesses; every count stays on the device.
 #include "crop_frame.h"
-#include "input_pipe.h"
+#include "crop_sample.h"
 
 namespace {
 
-constexpr int kOwBins = 801;     // line_output_width() is clamped to [10, 800]
-constexpr int kTileElems = 1024;  // outputs of one k_rectify_crops workgroup: 256 lanes x one 16-byte store
+constexpr int kOwBins = 801;  // line_output_width() is clamped to [10, 800]
 
 // ---- binarize + nearest resize -------------------------------------------------------------------------------------------------
 // One lane = 16 consecutive output bytes of the flat (B, H, W) mask (the tensor base is 16-byte aligned, rows need not be): one b128 store.
@@ -163,9 +162,26 @@ __device__ __forceinline__ int line_output_width(int h, int w, int OH) {
     return min(kOwBins - 1, max(10, ow));
 }
 
-// One workgroup walks the quads in index order, 256 at a time: geometry, three running prefix sums (packed elements, horizontal-pass
+// Where crop i's (h, w) come from: the crop frame of a quad, or the (S, H) of a chain crop (line_chain.hip).
+struct QuadSize {
+    const float* __restrict__ quads;
+    __device__ __forceinline__ int2 operator()(long i) const {
+        const CropFrame f = crop_frame(quads + i * 8);
+        return make_int2(f.h, f.w);
+    }
+};
+struct DimsSize {
+    const float* __restrict__ dims;  // [cap][2]: S, H
+    __device__ __forceinline__ int2 operator()(long i) const {
+        const float2 d = reinterpret_cast<const float2*>(dims)[i];
+        return make_int2(crop_len(d.y), crop_len(d.x));
+    }
+};
+
+// One workgroup walks the crops in index order, 256 at a time: geometry, three running prefix sums (packed elements, horizontal-pass
 // elements, sampler tiles), a histogram of output widths; then a stable counting sort by output width (rank = bin start + earlier equals).
-__global__ __launch_bounds__(256) void k_crop_plan(const float* __restrict__ quads, const int* __restrict__ count, long cap, int OH, int* __restrict__ plan,
+template <class Size>
+__global__ __launch_bounds__(256) void k_crop_plan(const Size size, const int* __restrict__ count, long cap, int OH, int* __restrict__ plan,
                                                    long long* __restrict__ totals) {
     __shared__ int s_hist[kOwBins], s_cnt[kOwBins], s_ow[256];
     __shared__ long long s_scan[3][256];
@@ -180,8 +196,8 @@ __global__ __launch_bounds__(256) void k_crop_plan(const float* __restrict__ qua
         long long v[3] = {0, 0, 0};
         int h = 0, w = 0, ow = 0;
         if (i < n) {
-            const CropFrame f = crop_frame(quads + i * 8);
-            h = f.h, w = f.w;
+            const int2 hw2 = size(i);
+            h = hw2.x, w = hw2.y;
             ow = line_output_width(h, w, OH);
             const long long hw = (long long)h * w;
             v[0] = (hw + 3) & ~3LL;  // every crop starts 16-byte aligned in the packed buffer
@@ -246,15 +262,7 @@ __global__ __launch_bounds__(256) void k_crop_plan(const float* __restrict__ qua
 // frame is computed once (wave-uniform: scalar registers).  One lane = 4 consecutive samples -> one 16-byte store; the taps are byte loads
 // of the page, which stays in L2 (a page is a few MB).
 
-// the last of the n > 0 crops whose first tile is <= tile
-__device__ __forceinline__ long crop_of_tile(const int* __restrict__ plan, long n, long long tile) {
-    long lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const long mid = (lo + hi + 1) >> 1;
-        if (plan[mid * 8 + 5] <= tile) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+// (kTileElems, crop_of_tile() and the tap sample_u8() are crop_sample.h's: the chain sampler of line_chain.hip uses them too)
 // The sampler: this lane's 4 samples of tile `tile` of crop `crop`, taken from the (H, W) page.
 __device__ __forceinline__ void rectify_tile(const uint8_t* __restrict__ page, int H, int W, const float* __restrict__ quads, const int* __restrict__ plan, long crop,
                                              long long tile, float* __restrict__ packed, long packed_floats) {
@@ -265,7 +273,6 @@ __device__ __forceinline__ void rectify_tile(const uint8_t* __restrict__ page, i
     const long e0 = (long)(tile - plan[crop * 8 + 5]) * kTileElems + threadIdx.x * 4;
     if (e0 >= hw || (long)pl.w + e0 + 4 > packed_floats) return;
     const float vx = -f.uy, vy = f.ux;
-    const float xmax = (float)(W - 1), ymax = (float)(H - 1);
     float out[4];
     int y = (int)(e0 / w), x = (int)(e0 - (long)y * w);
 #pragma unroll
@@ -273,16 +280,7 @@ __device__ __forceinline__ void rectify_tile(const uint8_t* __restrict__ page, i
         float val = 0.0f;
         if (e0 + k < hw) {
             const float su = ((float)x + 0.5f) / (float)w * f.lng, sv = ((float)y + 0.5f) / (float)h * f.sht;
-            float px = f.ox + su * f.ux + sv * vx, py = f.oy + su * f.uy + sv * vy;
-            px = fminf(fmaxf(px, 0.0f), xmax), py = fminf(fmaxf(py, 0.0f), ymax);  // border padding
-            const int x0 = (int)px, y0 = (int)py;
-            const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-            const float fx = px - (float)x0, fy = py - (float)y0;
-            const uint8_t* r0 = page + (size_t)y0 * W;
-            const uint8_t* r1 = page + (size_t)y1 * W;
-            const float a = px_u8(r0[x0]), b = px_u8(r0[x1]), c = px_u8(r1[x0]), d = px_u8(r1[x1]);
-            const float top = a + (b - a) * fx, bot = c + (d - c) * fx;
-            val = top + (bot - top) * fy;
+            val = sample_u8(page, H, W, f.ox + su * f.ux + sv * vx, f.oy + su * f.uy + sv * vy);
             if (++x == w) x = 0, ++y;
         }
         out[k] = val;
@@ -382,7 +380,16 @@ int ocrs_expand_quads(const float* quads, float* out, const int* counts, int B, 
 int ocrs_crop_plan(const float* quads, const int* count, long cap, int output_height, int* plan, long long* totals, hipStream_t st) {
     OCRS_CHECK_ARG(cap >= 0 && cap <= (1L << 24) && output_height > 0 && output_height <= 4096 && totals && aligned16(totals));
     OCRS_CHECK_ARG(cap == 0 || (quads && plan && aligned16(quads) && aligned16(plan)));
-    hipLaunchKernelGGL(k_crop_plan, dim3(1), dim3(256), 0, st, quads, count, cap, output_height, plan, totals);
+    hipLaunchKernelGGL(k_crop_plan<QuadSize>, dim3(1), dim3(256), 0, st, QuadSize{quads}, count, cap, output_height, plan, totals);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+// section "chain crops": the same plan from the (S, H) of ocrs_line_spines
+int ocrs_crop_plan_dims(const float* line_dims, const int* count, long cap, int output_height, int* plan, long long* totals, hipStream_t st) {
+    OCRS_CHECK_ARG(cap >= 0 && cap <= (1L << 24) && output_height > 0 && output_height <= 4096 && totals && aligned16(totals));
+    OCRS_CHECK_ARG(cap == 0 || (line_dims && plan && aligned16(line_dims) && aligned16(plan)));
+    hipLaunchKernelGGL(k_crop_plan<DimsSize>, dim3(1), dim3(256), 0, st, DimsSize{line_dims}, count, cap, output_height, plan, totals);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

@@ -1,6 +1,6 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
-    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order]] [--chars] [--beam-width N]
+    python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order] [--rectify {quad,chain}]] [--chars] [--beam-width N]
         [--lm FILE [--lm-weight A] [--lm-bonus B]] [--tile TH TW [--tile-overlap VH VW]]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
@@ -9,7 +9,9 @@ on the page).  With ``--rec-model`` the words are recognised too (``inference.re
 With ``--lines`` the words are grouped into text lines first (``inference.find_lines``): ``-text-lines.png`` shows the line quads, and with
 ``--rec-model`` every LINE is recognised (``inference.read_lines``) and printed as one JSON object with its quad, its text and its words' quads
 in reading order, instead of the words.  ``--lines --reading-order`` prints those objects in the page's reading order (column by column,
-``inference.reading_order``), each with ``"block"``, the number of its text block.  ``--chars`` (with ``--rec-model``) adds to every object where each
+``inference.reading_order``), each with ``"block"``, the number of its text block.  ``--lines --rectify chain`` cuts every line's crop along the
+polyline of its words instead of as the rectangle of its line quad (``read_lines(rectify="chain")``); every line object gains
+``"spine"`` and ``"height"``.  ``--chars`` (with ``--rec-model``) adds to every object where each
 character of its text sits on the page and the recogniser's log-prob of it (``"char_quads"``, ``"char_log_probs"``), and to every line object the text and
 character range of each of its words (``"word_texts"``, ``"word_chars"``): ``inference.char_boxes`` / ``word_chars``.  ``--beam-width N`` (with
 ``--rec-model``) decodes by CTC prefix beam search with N prefixes instead of greedily and adds ``"log_prob"``, the log-mass of the text, to every
@@ -63,6 +65,9 @@ def main(argv=None):
                         "recognise and print one JSON object per line instead of per word")
     parser.add_argument("--reading-order", action="store_true", help="with --lines and --rec-model: print the lines in reading order, column by "
                         "column, each with the number of its block")
+    parser.add_argument("--rectify", choices=("quad", "chain"), default="quad", help="with --lines and --rec-model: cut every line's crop as the rectangle "
+                        "of its line quad (quad, the default) or along the polyline of its words (chain); chain adds the spine and its height to "
+                        "the JSON objects")
     parser.add_argument("--chars", action="store_true", help="with --rec-model: add every character's quad and log-prob to the JSON objects and, with "
                         "--lines, every word's text and character range")
     parser.add_argument("--beam-width", type=int, default=None, metavar="N", help="with --rec-model: decode by CTC prefix beam search with N prefixes "
@@ -78,6 +83,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.reading_order and not args.lines:
         parser.error("--reading-order needs --lines")
+    if args.rectify == "chain" and not args.lines:
+        parser.error("--rectify chain needs --lines")
     if args.beam_width is not None and not args.rec_model:
         parser.error("--beam-width needs --rec-model")
     if args.beam_width is not None and not 1 <= args.beam_width <= 64:
@@ -131,7 +138,8 @@ def main(argv=None):
         lm = model_lm.gain(args.lm_weight, args.lm_bonus, device)
     if args.lines:
         if rec is not None:
-            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width, lm=lm)
+            lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width, lm=lm,
+                                         rectify=args.rectify)
             for line in lines:
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]

@@ -63,18 +63,27 @@ Tiles (csrc/ocr_tiles.hip, C ABI section "tiles"; restated for t
 drivers cut the page into overlapping windows at (near) native resolution, run the detector on every window and compose ONE page mask from
 the tiles before the components are labelled; None, the default, is the whole-page path unchanged; the same waits.
 
+Chain crops (csrc/line_chain.hip, C ABI section "chain crops"; restated for the tests in tests/chain_ref.py).  The line quad is one
+rotated rectangle around all words of a line, so a curved line -- page curl, an arc, a sagging end -- is cut far higher than its text and runs
+diagonally through its crop.  With ``rectify="chain"`` ``read_lines``, ``ocr_lines`` and ``ocr_pages`` cut every line along the polyline of its words
+(``line_spines``: the mid-points of each word's left and right edge, joined across the gaps) at one constant height (``crop_plan_chain``,
+``rectify_chain`` / ``rectify_chain_pages``), every word upright and at full height; line dicts gain ``"spine"`` and ``"height"``, and with
+``chars=True`` the character quads follow the spine (``char_boxes_chain``, ``word_chars_chain``).  ``"quad"``, the default, is the rectangle path
+unchanged; the same waits.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
 per page.  The single-page functions above are what its tests compare it with.
 
-The package, by stage: ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order),
+The package, by stage: ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops),
 ``decode`` (the recogniser, characters, and the ``Decoded`` record every decode is read into), ``assemble`` (record + host lists -> result
 dicts, no GPU) and ``drivers`` (``ocr_page``, ``read_words``, ``read_lines``, ``ocr_lines``, ``ocr_pages``).  Everything is re-exported here.
 """
 from ..input_pipeline import resize, transform_image  # noqa: F401
 from ..text import DEFAULT_ALPHABET, decode_text  # noqa: F401
 from .assemble import assemble_results  # noqa: F401
+from .chain import LineSpines, char_boxes_chain, crop_plan_chain, line_spines, rectify_chain, rectify_chain_pages, word_chars_chain  # noqa: F401
 from .crops import CropPlan, crop_plan, crops_to_batches, plan_chunks, rectify_crops, rectify_crops_pages  # noqa: F401
 from .decode import CharBoxes, CharSpans, Decoded, char_boxes, chars_to_host, decode_crop_spans, recognize_crops, space_label, word_chars  # noqa: F401
 from .detect import (MASK_SIZE, SHRINK_DISTANCE, _cc_quads_pages_sizes, binarize_resize, binarize_resize_pages, cc_quads_pages, detect_words,  # noqa: F401

@@ -191,8 +191,9 @@ def _decode_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = F
     """The recogniser over ``batches`` (what ``crops_to_batches`` returned) -> the ``Decoded`` record every public form is a view of; the one
     place the batches' permutation is applied.  Greedy without characters: every chunk's forward and ``greedy_decode_batch_async`` are queued
     (the decodes on their side stream), then the label copies are waited for.  Anything else: ``decode_crop_spans`` and ONE wait, in
-    ``_spans_to_host``.  ``geometry`` = ``(quads, plan, lines)``, what the crops were cut with: ``char_boxes``, and with ``lines`` (a
-    ``TextLines``, else None) ``word_chars``, are queued behind the decodes and copied in the same wait."""
+    ``_spans_to_host``.  ``geometry`` = ``(boxes_of, ranges_of)``, the character stages of what the crops were cut with:
+    ``boxes_of(spans)`` (``char_boxes`` or ``char_boxes_chain`` on that geometry) and, for lines, ``ranges_of(spans, boxes, alphabet)``
+    (``word_chars`` / ``word_chars_chain``; None for word crops) are queued behind the decodes and copied in the same wait."""
     _check_lm_args("recognize_crops", beam_width, lm)
     perm = batches[2]
     if not chars and beam_width is None:
@@ -205,9 +206,9 @@ def _decode_crops(rec_model, batches, alphabet=DEFAULT_ALPHABET, chars: bool = F
     spans = decode_crop_spans(rec_model, batches, beam_width, lm)
     boxes = ranges = None
     if geometry is not None:
-        quads, plan, lines = geometry
-        boxes = char_boxes(quads, plan, spans)
-        ranges = None if lines is None else word_chars(lines, plan, spans, boxes, alphabet)
+        boxes_of, ranges_of = geometry
+        boxes = boxes_of(spans)
+        ranges = None if ranges_of is None else ranges_of(spans, boxes, alphabet)
     return Decoded.in_quad_order(perm, *_spans_to_host(spans, alphabet, boxes, ranges), spans)
 
 

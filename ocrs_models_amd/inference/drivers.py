@@ -9,7 +9,7 @@ from itertools import accumulate
 import torch
 
 from ..text import DEFAULT_ALPHABET, LMGain
-from . import crops, decode, detect
+from . import chain, crops, decode, detect
 from . import lines as line_stage
 from .args import _check_pages, _to_host_async
 from .assemble import assemble_results
@@ -17,7 +17,7 @@ from .assemble import assemble_results
 
 def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: line_stage.TextLines | None = None, n_lines: int = 0,
                 order: line_stage.ReadingOrder | None = None, line_page_offs: list | None = None, chars_plan: crops.CropPlan | None = None,
-                beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
+                beam_width: int | None = None, lm: LMGain | None = None, spines: chain.LineSpines | None = None) -> list[dict]:
     """The tail of ``ocr_page``, ``read_lines`` and ``ocr_pages``: the device half -- the early host copies, then ``decode._decode_crops`` on
     ``batches`` -- and ``assemble_results`` on what arrived: the flat result list -- one ``{"quad", "text"}`` per word, or with ``lines``
     one ``{"quad", "text", "words"}`` per line for its first ``n_lines`` lines.  With ``order`` the list is in reading order -- position k holds line ``order.line_order[k]`` -- and every dict has ``"block"``, counted from 0 on every
@@ -27,34 +27,63 @@ def _read_crops(rec_model, batches, alphabet, words: torch.Tensor, lines: line_s
     ``"char_log_probs"``, line dicts ``"word_chars"`` and ``"word_texts"`` too.  The boxes and word ranges are queued behind the
     decodes and copied with the labels: still one wait here.  ``beam_width``: the texts of prefix beam search and
     ``"log_prob"`` in every dict; still one wait.  ``lm``: the beam's ranking includes the language model's gains and
-    every dict has ``"lm_score"`` next to ``"log_prob"``; its copy joins the same wait."""
+    every dict has ``"lm_score"`` next to ``"log_prob"``; its copy joins the same wait.  ``spines`` (with ``lines``): the
+    crops are chain crops cut along these spines; every line dict gains ``"spine"`` and ``"height"``, whose tables travel with the line
+    tables, and the characters' boxes and word ranges follow the spines (``char_boxes_chain`` / ``word_chars_chain``); the same waits."""
     words_h = _to_host_async(words)
     if lines is not None:
         lq_h, wo_h, offs_h = (_to_host_async(t) for t in (lines.quads, lines.word_order, lines.line_offsets))
+    if spines is not None:
+        kn_h, dims_h = _to_host_async(spines.knots()), _to_host_async(spines.line_dims)
     if order is not None:
         ro_h, nb_h = _to_host_async(order.line_order), _to_host_async(order.new_block)
-    geometry = None if chars_plan is None else (words if lines is None else lines.quads, chars_plan, lines)
+    geometry = None
+    if chars_plan is not None and spines is not None:
+        geometry = (partial(chain.char_boxes_chain, spines, chars_plan), partial(chain.word_chars_chain, spines, chars_plan))
+    elif chars_plan is not None:
+        geometry = (partial(decode.char_boxes, words if lines is None else lines.quads, chars_plan),
+                    None if lines is None else partial(decode.word_chars, lines, chars_plan))
     rec = decode._decode_crops(rec_model, batches, alphabet, chars_plan is not None, beam_width, lm, geometry)
     if lines is None:
         return assemble_results(rec, words_h.tolist())
     reading = None
     if order is not None:
         reading = (ro_h[:n_lines].tolist(), nb_h[:n_lines].tolist(), [0, n_lines] if line_page_offs is None else line_page_offs)
-    return assemble_results(rec, words_h.tolist(), (lq_h[:n_lines].tolist(), wo_h.tolist(), offs_h[:n_lines + 1].tolist()), reading)
+    offs = offs_h[:n_lines + 1].tolist()
+    knots = None if spines is None else (kn_h[:offs[-1]].tolist(), dims_h[:n_lines].tolist())
+    return assemble_results(rec, words_h.tolist(), (lq_h[:n_lines].tolist(), wo_h.tolist(), offs), reading, knots)
 
 
-def _read_quads(rec_model, cut, words: torch.Tensor, lines, order, output_height: int, max_batch: int, width_unit: int, alphabet, chars: bool,
-                beam_width, lm):
-    """The tail after detection, once: plan the crops of ``words`` -- or, with ``lines`` (a ``TextLines``), of its lines --, cut them with
-    ``cut(quads, plan)`` (one page: ``rectify_crops``; a page store: ``rectify_crops_pages``), batch them, read them (``_read_crops``).
+def _check_rectify(who: str, rectify, lines: bool = True):
+    """``rectify`` names how line crops are cut: "quad" (the line quad's rectangle) or "chain" (along the words' spine)"""
+    if rectify not in ("quad", "chain"):
+        raise RuntimeError(f'{who}: rectify must be "quad" or "chain"')
+    if rectify == "chain" and not lines:
+        raise RuntimeError(f'{who}: rectify="chain" cuts line crops: it needs lines=True')
+
+
+def _crop_stages(rectify: str, words: torch.Tensor, lines, output_height: int, cut_quads, cut_chain):
+    """How the crops of ``words`` -- or, with ``lines`` (a ``TextLines``), of its lines -- are planned and cut -> ``(plan_of, cut, spines)``
+    for ``_read_quads``.  "quad": ``crop_plan`` of the quads and ``cut_quads(quads, plan)`` (one page: ``rectify_crops``; a page store:
+    ``rectify_crops_pages``).  "chain" (lines only): ``line_spines``, then ``crop_plan_chain`` and ``cut_chain(spines, plan)``
+    (``rectify_chain`` / ``rectify_chain_pages``)."""
+    if rectify == "chain":
+        spines = chain.line_spines(lines)
+        return partial(chain.crop_plan_chain, spines, output_height), partial(cut_chain, spines), spines
+    quads, count = (words, None) if lines is None else (lines.quads, lines.n_lines)
+    return partial(crops.crop_plan, quads, output_height, count), partial(cut_quads, quads), None
+
+
+def _read_quads(rec_model, plan_of, cut, spines, words: torch.Tensor, lines, order, max_batch: int, width_unit: int, alphabet, chars: bool, beam_width, lm):
+    """The tail after detection, once: plan the crops (``plan_of()``), cut them (``cut(plan)``), batch them, read them (``_read_crops``);
+    the three first arguments are what ``_crop_stages`` returned.
     -> ``(flat result list, line_page_offs as a host list or None)``: the lines' page offsets are copied ahead of the plan's totals, so they
     have arrived when those have.  Two host synchronisations: the plan's totals and the labels."""
-    quads, count = (words, None) if lines is None else (lines.quads, lines.n_lines)
-    plan = crops.crop_plan(quads, output_height, count)
+    plan = plan_of()
     lpo_h = None if lines is None or lines.line_page_offs is None else _to_host_async(lines.line_page_offs)
-    batches = crops.crops_to_batches(cut(quads, plan), plan, max_batch, width_unit)
+    batches = crops.crops_to_batches(cut(plan), plan, max_batch, width_unit)
     lpo = None if lpo_h is None else lpo_h.tolist()
-    return _read_crops(rec_model, batches, alphabet, words, lines, plan.host()[0], order, lpo, plan if chars else None, beam_width, lm), lpo
+    return _read_crops(rec_model, batches, alphabet, words, lines, plan.host()[0], order, lpo, plan if chars else None, beam_width, lm, spines), lpo
 
 
 def read_words(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
@@ -63,8 +92,8 @@ def read_words(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_hei
     ``ocr_page`` returns, one crop and one dict per word.  Two host synchronisations: the plan's totals and the labels.  ``chars``,
     ``beam_width`` and ``lm`` as ``ocr_page`` describes them."""
     decode._check_lm_args("read_words", beam_width, lm)
-    return _read_quads(rec_model, partial(crops.rectify_crops, page_u8), quads, None, None, output_height, max_batch, width_unit, alphabet, chars,
-                       beam_width, lm)[0]
+    stages = _crop_stages("quad", quads, None, output_height, partial(crops.rectify_crops, page_u8), None)
+    return _read_quads(rec_model, *stages, quads, None, None, max_batch, width_unit, alphabet, chars, beam_width, lm)[0]
 
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
@@ -88,7 +117,7 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE,
 
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
                alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0,
-               chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
+               chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None, rectify: str = "quad") -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
     ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
@@ -97,18 +126,25 @@ def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_hei
     ``beam_width``: decode by CTC prefix beam search with that many prefixes instead of greedily; every dict gains
     ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
     ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
-    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits."""
+    log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits.
+    ``rectify``: ``"quad"``, the default, cuts every line as the rectangle of its line quad; ``"chain"`` cuts it along the
+    polyline of its words at one constant height, so the words of a curved line sit upright and at full height in the crop.  With
+    ``"chain"`` every dict keeps ``"quad"`` (still the line quad), ``"text"`` and ``"words"`` and gains ``"spine"`` (the 2n knots of its n
+    words as ``[x, y]`` lists: the mid-points of each word's left and right edge, in chain order) and ``"height"`` (the crop's height on the
+    page); with ``chars`` the character quads follow the spine; the same waits.  Any other value is an argument error."""
     decode._check_lm_args("read_lines", beam_width, lm)
+    _check_rectify("read_lines", rectify)
     found = line_stage.find_lines(quads, None, max_gap, min_cos)
     order = line_stage.reading_order(found, block_gap) if reading_order else None
-    return _read_quads(rec_model, partial(crops.rectify_crops, page_u8), quads, found, order, output_height, max_batch, width_unit, alphabet, chars,
-                       beam_width, lm)[0]
+    stages = _crop_stages(rectify, quads, found, output_height, partial(crops.rectify_crops, page_u8), partial(chain.rectify_chain, page_u8))
+    return _read_quads(rec_model, *stages, quads, found, order, max_batch, width_unit, alphabet, chars, beam_width, lm)[0]
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
-              beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16) -> list[dict]:
+              beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16,
+              rectify: str = "quad") -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
@@ -118,19 +154,22 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE
     sits on the page), ``"char_log_probs"`` (the recogniser's log-prob of each), ``"word_chars"`` (parallel to ``"words"``: the ``[first, end]``
     of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits.  ``beam_width``: as in
     ``read_lines``; ``lm``: as in ``read_lines``.  ``tile``, ``overlap``, ``tile_batch``: detect in overlapping
-    tiles, as ``detect_words`` describes; still three waits."""
+    tiles, as ``detect_words`` describes; still three waits.  ``rectify`` (DESIGN.md §21): ``"quad"`` or ``"chain"``, as in ``read_lines``;
+    still three waits."""
     decode._check_lm_args("ocr_lines", beam_width, lm)
+    _check_rectify("ocr_lines", rectify)
     det = detect.detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
     if det["n"] == 0:
         return []
     return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars,
-                      beam_width, lm)
+                      beam_width, lm, rectify)
 
 
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
-              beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16) -> list[list[dict]]:
+              beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16,
+              rectify: str = "quad") -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
@@ -144,8 +183,11 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=detect.MASK_
     ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
     log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits.
     ``tile``, ``overlap``, ``tile_batch``: detect every page in overlapping tiles, as ``detect_words`` describes; the tiles of all
-    pages are pooled into the same forward chunks and cut from the page store the crops are cut from; the same waits."""
+    pages are pooled into the same forward chunks and cut from the page store the crops are cut from; the same waits.
+    ``rectify`` (with ``lines``): ``"quad"`` or ``"chain"``, as in ``read_lines``; ``"chain"`` with ``lines=False`` is an
+    argument error; the same waits."""
     decode._check_lm_args("ocr_pages", beam_width, lm)
+    _check_rectify("ocr_pages", rectify, lines)
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
@@ -162,6 +204,7 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=detect.MASK_
         found = line_stage.find_lines_pages(words, det["page_of_word"], det["word_offs"], max_gap, min_cos)
         order = line_stage.reading_order(found, block_gap) if reading_order else None
     page_of_quad = found.page_of_line if lines else det["page_of_word"]
-    flat, offs = _read_quads(rec_model, lambda q, plan: crops.rectify_crops_pages(*store, q, page_of_quad, plan), words, found, order, output_height,
-                             max_batch, width_unit, alphabet, chars, beam_width, lm)
+    stages = _crop_stages(rectify, words, found, output_height, lambda q, plan: crops.rectify_crops_pages(*store, q, page_of_quad, plan),
+                          lambda sp, plan: chain.rectify_chain_pages(*store, sp, page_of_quad, plan))
+    flat, offs = _read_quads(rec_model, *stages, words, found, order, max_batch, width_unit, alphabet, chars, beam_width, lm)
     return line_stage.split_by_page(flat, offs if lines else [0, *accumulate(det["counts"])])
