@@ -655,6 +655,28 @@ int ocrs_char_boxes_chain(const float* spine, const float* line_dims, const int*
 int ocrs_word_chars_chain(const float* spine, long wcap, const int* n_lines, long cap, const int* line_offsets, const int* word_order, const int* plan, long rows,
                           int ld, const int* labels, const int* lens, const float* s0, const float* s1, int space, int* word_chars, hipStream_t st);
 
+/* ------------------------------------------------------------------ orientation -------------- */
+/* Pages scanned sideways or upside down (csrc/page_orient.hip; Python: inference/orient.py; restated for the tests in
+ * tests/orient_ref.py).  orientation = k in 0..3: the upright page is rot90(page, k), k quarter turns counter-clockwise.  A point (x, y) of
+ * the turned page of a page of H rows and W columns lies on the original page at (x, y) | ((W-1) - y, x) | ((W-1) - x, (H-1) - y) |
+ * (y, (H-1) - x) for k = 0 | 1 | 2 | 3 (pixel centres).  Nothing here allocates or synchronises.
+ * ocrs_turn_page_u8: dst = rot90(src, k) for the (H,W) uint8 page src, k in 1..3 (k = 0 is the caller's own page); dst is (W,H) for odd k and
+ * must not overlap src.  Any H, W >= 1. */
+int ocrs_turn_page_u8(const unsigned char* src, int H, int W, int k, unsigned char* dst, hipStream_t st);
+/* The table above (inverse == 0: turned-page points -> original-page points) or its inverse (original -> turned) on quads [n][4][2] fp32 of
+ * a page whose ORIGINAL is H x W: one fp32 operation per coordinate, corner j -> corner j.  count: optional device int32, only the first
+ * min(count, n) rows are written. */
+int ocrs_turn_quads(const float* quads, long n, const int* count, int H, int W, int k, int inverse, float* out, hipStream_t st);
+/* The axis vote.  Per quad the long side L and the short side by the crop-frame rule (the longer of c0->c1 and c1->c2; on a tie the one with
+ * the larger |x|), lengths as sqrtf(x * x + y * y) with one rounding per operation; a quad votes if short > 0 and long >= min_aspect * short
+ * (fp32) and adds |L| to H if |L.x| >= |L.y|, else to V.  votes: 2 fp64 (H, V) followed by 2 int32 (voters, K = min(sample, voters)), 24
+ * bytes, 8-byte aligned; the sums have a fixed order (no atomics).  picks [sample] int32: the K voters with the largest |L|, ties by the
+ * smaller index, in that order; entries from K on are -1.  count as above. */
+int ocrs_orient_votes(const float* quads, long n, const int* count, float min_aspect, int sample, double* votes, int* picks, hipStream_t st);
+/* scores[r] (fp64) = the mean over t < steps[r] of max_c log_probs[t][r][c] for the [T][B][C] fp32 log-probs of B crops, 1 <= steps[r] <= T
+ * (clamped; 0 steps give 0): the maxima exact, the sum in time order in fp64. */
+int ocrs_path_confidence(const float* log_probs, int T, int B, int C, const int* steps, double* scores, hipStream_t st);
+
 /* ------------------------------------------------------------------ beam search -------------- */
 /* CTC prefix beam search and forced alignment by the rule of DESIGN.md §18 (csrc/ctc_beam.hip; Python: text.beam_decode_spans,
  * text.ctc_align_spans; restated in tests/beam_ref.py).  Both generalise ctc_greedy_decode_text (datasets/util.py:147-177), the greedy rule:

@@ -1,7 +1,7 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
     python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order] [--rectify {quad,chain}]] [--chars] [--beam-width N]
-        [--lm FILE [--lm-weight A] [--lm-bonus B]] [--tile TH TW [--tile-overlap VH VW]]
+        [--lm FILE [--lm-weight A] [--lm-bonus B]] [--tile TH TW [--tile-overlap VH VW]] [--orientation {auto,0,1,2,3}]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
@@ -19,7 +19,11 @@ object.  ``--lm FILE`` (with ``--beam-width``) loads a characte
 and fuses ``A log P + B`` per character into the beam's ranking (``--lm-weight A``, default 1; ``--lm-bonus B``, default 0); every object
 gains ``"lm_score"``.  ``--tile TH TW`` detects the page in overlapping tiles of TH x TW page pixels instead of squeezing it to the
 model's size whole (``detect_words(tile=...)``; ``--tile-overlap VH VW``, default an eighth of the tile); ``-text-probs.png`` then
-shows the tiles' probability maps side by side in their grid.  The image is read and the pictures are written with PIL on the host; that is not a hot path.
+shows the tiles' probability maps side by side in their grid.  ``--orientation K`` reads a page scanned sideways or upside down: K
+quarter turns counter-clockwise make it upright, ``auto`` (with ``--rec-model``) lets ``inference.page_orientation`` find K.  The page is turned
+(``inference.turn_page``), detected and read upright -- the pictures show the upright page -- and the JSON objects come back on the page as it
+was given, each with ``"turns"``; the turns are printed to stderr and written to ``-orientation.json`` with the vote and the probe's scores.
+The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
 
@@ -55,6 +59,12 @@ def draw_quads(img_u8: np.ndarray, quads) -> Image.Image:
     return out
 
 
+def _load_rec(path: str, device) -> RecognitionModel:
+    rec = RecognitionModel(DEFAULT_ALPHABET).to(device)
+    load_model_state(path, rec, device)
+    return rec.eval()
+
+
 def main(argv=None):
     parser = ArgumentParser()
     parser.add_argument("model")
@@ -80,7 +90,12 @@ def main(argv=None):
                         "compose one page mask from them, for pages much larger than the model's 800 x 600")
     parser.add_argument("--tile-overlap", type=int, nargs=2, default=None, metavar=("VH", "VW"), help="with --tile: the overlap of neighbouring tiles "
                         "in page pixels (default: an eighth of the tile)")
+    parser.add_argument("--orientation", choices=("auto", "0", "1", "2", "3"), default=None, metavar="K", help="the page is scanned sideways or upside "
+                        "down: K in 0..3 quarter turns counter-clockwise make it upright; auto (with --rec-model) finds K from the word quads and "
+                        "a recogniser probe.  The JSON objects are on the page as given and gain the turns")
     args = parser.parse_args(argv)
+    if args.orientation == "auto" and not args.rec_model:
+        parser.error("--orientation auto needs --rec-model (the probe reads the longest words both ways up)")
     if args.reading_order and not args.lines:
         parser.error("--reading-order needs --lines")
     if args.rectify == "chain" and not args.lines:
@@ -103,14 +118,31 @@ def main(argv=None):
 
     page_h = np.asarray(Image.open(args.image).convert("L"), dtype=np.uint8)
     page = torch.from_numpy(page_h.copy())[None].to(device)
+    tile = None if args.tile is None else tuple(args.tile)
+    overlap = None if args.tile_overlap is None else tuple(args.tile_overlap)
+
+    rec = turns = det = None
+    if args.orientation is not None:
+        found = {"turns": int(args.orientation)} if args.orientation != "auto" else None
+        if found is None:
+            rec = _load_rec(args.rec_model, device)
+            found = inference.page_orientation(model, rec, page, tile=tile, overlap=overlap)
+            det = found.pop("det") if found["turns"] == 0 else None  # an upright page is detected once
+            found.pop("det", None)
+        turns = found["turns"]
+        print(f"Orientation: {turns} quarter turn(s) counter-clockwise make the page upright", file=sys.stderr)
+        with open(f"{args.out_basename}-orientation.json", "w") as f:
+            json.dump(found, f)
+        page = inference.turn_page(page, turns)  # from here on the upright page; the JSON objects are mapped back at the end
+        page_h = np.ascontiguousarray(np.rot90(page_h, turns))
 
     img = inference.resize(inference.transform_image(page), inference.MASK_SIZE)
     _to_pil((img[0] + 0.5).clamp(0, 1)).save(f"{args.out_basename}-input.png")
 
     torch.cuda.synchronize()
     start = time.time()
-    tile = None if args.tile is None else tuple(args.tile)
-    det = inference.detect_words(model, page, tile=tile, overlap=None if args.tile_overlap is None else tuple(args.tile_overlap))
+    if det is None:
+        det = inference.detect_words(model, page, tile=tile, overlap=overlap)
     torch.cuda.synchronize()
     print(f"Predicted text in {time.time() - start:.2f}s", file=sys.stderr)
 
@@ -118,18 +150,17 @@ def main(argv=None):
     _to_pil(text_regions).save(f"{args.out_basename}-text-regions.png")
     probs = det["probs"]
     if tile is not None:  # (T,h,w) in row-major tile order -> the maps side by side in their grid
-        plan = inference.tile_plan(page.shape[1], page.shape[2], tile, None if args.tile_overlap is None else tuple(args.tile_overlap))
+        plan = inference.tile_plan(page.shape[1], page.shape[2], tile, overlap)
         ny, nx = len(plan.rows.starts), len(plan.cols.starts)
         probs = probs.view(ny, nx, *probs.shape[-2:]).permute(0, 2, 1, 3).reshape(ny * probs.shape[-2], nx * probs.shape[-1])
     _to_pil(probs).save(f"{args.out_basename}-text-probs.png")
     quads = det["quads"].tolist()
     draw_quads(page_h, quads).save(f"{args.out_basename}-text-words.png")
 
-    rec = None
-    if args.rec_model and det["n"]:
-        rec = RecognitionModel(DEFAULT_ALPHABET).to(device)
-        load_model_state(args.rec_model, rec, device)
-        rec.eval()
+    if args.rec_model and det["n"] and rec is None:
+        rec = _load_rec(args.rec_model, device)
+    if not det["n"]:
+        rec = None
     lm = None
     if args.lm is not None and rec is not None:
         model_lm = CharLM.load(args.lm)
@@ -140,7 +171,7 @@ def main(argv=None):
         if rec is not None:
             lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width, lm=lm,
                                          rectify=args.rectify)
-            for line in lines:
+            for line in lines if turns is None else inference.turn_results(lines, turns, *inference.turn_shape(*page_h.shape, turns)):
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]
         else:
@@ -148,7 +179,7 @@ def main(argv=None):
             line_quads = found.quads[:int(found.n_lines)].tolist()
         draw_quads(page_h, line_quads).save(f"{args.out_basename}-text-lines.png")
     elif rec is not None:
-        for word in inference.read_words(rec, page, det["quads"], chars=args.chars, beam_width=args.beam_width, lm=lm):
+        for word in inference.read_words(rec, page, det["quads"], chars=args.chars, beam_width=args.beam_width, lm=lm, orientation=turns):
             print(json.dumps(word))
 
 

@@ -71,12 +71,20 @@ diagonally through its crop.  With ``rectify="chain"`` ``read_lines``, ``ocr_lin
 ``chars=True`` the character quads follow the spine (``char_boxes_chain``, ``word_chars_chain``).  ``"quad"``, the default, is the rectangle path
 unchanged; the same waits.
 
+Orientation (csrc/page_orient.hip, C ABI section "orientation"; restated for the tests in tests/orient_ref.py).  Every stage above
+assumes an upright page: the line stage never chains steep text, and the crop frame's ``u.x > 0`` hands an upside-down page to the recogniser
+upside down.  ``orientation=k`` of ``ocr_page``, ``ocr_lines`` and ``ocr_pages`` -- k quarter turns counter-clockwise make the page upright --
+reads ``turn_page(page, k)``, an exact permutation of the page's bytes, and maps ``"quad"``, ``"words"``, ``"char_quads"`` and ``"spine"`` back to the
+page that was passed (``turn_results``); every dict gains ``"turns"``; the same three waits.  ``orientation="auto"`` decides first
+(``page_orientation``: a vote over the word quads for the axis, ``orientation_votes``, and a recogniser probe of the longest words both ways
+up for the sign, ``path_confidence``; at most three more waits).  None, the default, is today's path unchanged.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
 per page.  The single-page functions above are what its tests compare it with.
 
-The package, by stage: ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops),
+The package, by stage: ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops), ``orient`` (page turns and their detection),
 ``decode`` (the recogniser, characters, and the ``Decoded`` record every decode is read into), ``assemble`` (record + host lists -> result
 dicts, no GPU) and ``drivers`` (``ocr_page``, ``read_words``, ``read_lines``, ``ocr_lines``, ``ocr_pages``).  Everything is re-exported here.
 """
@@ -90,4 +98,5 @@ from .detect import (MASK_SIZE, SHRINK_DISTANCE, _cc_quads_pages_sizes, binarize
                      detect_words_batch, expand_quads, gather_page_quads, pack_pages)
 from .drivers import _read_crops, ocr_lines, ocr_page, ocr_pages, read_lines, read_words  # noqa: F401
 from .lines import ReadingOrder, TextLines, find_lines, find_lines_pages, page_text, reading_order, split_by_page  # noqa: F401
+from .orient import orientation_votes, page_orientation, path_confidence, probe_batches, turn_page, turn_quads, turn_results, turn_shape  # noqa: F401
 from .tiles import TILES_AXIS_MAX, AxisPlan, TilePlan, TileTables, binarize_resize_tiles, tile_batch, tile_plan, tile_tables  # noqa: F401

@@ -9,7 +9,7 @@ from itertools import accumulate
 import torch
 
 from ..text import DEFAULT_ALPHABET, LMGain
-from . import chain, crops, decode, detect
+from . import chain, crops, decode, detect, orient
 from . import lines as line_stage
 from .args import _check_pages, _to_host_async
 from .assemble import assemble_results
@@ -62,6 +62,20 @@ def _check_rectify(who: str, rectify, lines: bool = True):
         raise RuntimeError(f'{who}: rectify="chain" cuts line crops: it needs lines=True')
 
 
+def _check_upright_turns(who: str, orientation):
+    """``orientation`` of ``read_words`` / ``read_lines``: None or the int the caller turned the page by (there is no detector here to probe with)"""
+    if orientation is not None:
+        orient._check_turns(who, orientation)
+
+
+def _turned_back(results: list, upright_u8: torch.Tensor, orientation) -> list:
+    """results read on the upright page -> on the page it was turned from by ``orientation`` quarter turns (None: as they are)"""
+    if orientation is None:
+        return results
+    H, W = orient.turn_shape(int(upright_u8.shape[-2]), int(upright_u8.shape[-1]), orientation)
+    return orient.turn_results(results, orientation, H, W)
+
+
 def _crop_stages(rectify: str, words: torch.Tensor, lines, output_height: int, cut_quads, cut_chain):
     """How the crops of ``words`` -- or, with ``lines`` (a ``TextLines``), of its lines -- are planned and cut -> ``(plan_of, cut, spines)``
     for ``_read_quads``.  "quad": ``crop_plan`` of the quads and ``cut_quads(quads, plan)`` (one page: ``rectify_crops``; a page store:
@@ -87,18 +101,21 @@ def _read_quads(rec_model, plan_of, cut, spines, words: torch.Tensor, lines, ord
 
 
 def read_words(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
-               alphabet=DEFAULT_ALPHABET, chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None) -> list[dict]:
+               alphabet=DEFAULT_ALPHABET, chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None, orientation: int | None = None) -> list[dict]:
     """The half of ``ocr_page`` after detection, the word counterpart of ``read_lines``: word quads (N,4,2), N > 0, on the device -> the list
     ``ocr_page`` returns, one crop and one dict per word.  Two host synchronisations: the plan's totals and the labels.  ``chars``,
-    ``beam_width`` and ``lm`` as ``ocr_page`` describes them."""
+    ``beam_width`` and ``lm`` as ``ocr_page`` describes them.  ``orientation``: ``page_u8`` and ``quads`` are always the
+    UPRIGHT page's; an int k says that this page is ``turn_page(original, k)``, and the results come back on the original page with
+    ``"turns": k`` (``turn_results``); None, the default, changes nothing; the same waits."""
     decode._check_lm_args("read_words", beam_width, lm)
+    _check_upright_turns("read_words", orientation)
     stages = _crop_stages("quad", quads, None, output_height, partial(crops.rectify_crops, page_u8), None)
-    return _read_quads(rec_model, *stages, quads, None, None, max_batch, width_unit, alphabet, chars, beam_width, lm)[0]
+    return _turned_back(_read_quads(rec_model, *stages, quads, None, None, max_batch, width_unit, alphabet, chars, beam_width, lm)[0], page_u8, orientation)
 
 
 def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
              output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, chars: bool = False,
-             beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16) -> list[dict]:
+             beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16, orientation=None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": (4,2) list, "text": str}, ...]`` in the raster order of ``extract_cc_quads_device``.
     A page without components returns ``[]`` without launching the recogniser.  ``chars=True``: every dict also has ``"char_quads"``, the
     rectangle of every character of ``"text"`` on the page, and ``"char_log_probs"``, the recogniser's log-prob of each; the
@@ -107,17 +124,29 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE,
     ``"log_prob"``, the log-mass of its text; None = the greedy decode, unchanged; the same waits.
     ``lm`` (with ``beam_width``): the ``LMGain`` of a character language model (``text.CharLM.gain``); the beam ranks by
     log-prob + gains and every dict also gains ``"lm_score"``, the gains of its text; None = the plain beam, unchanged; the same waits.
-    ``tile``, ``overlap``, ``tile_batch``: detect in overlapping tiles, as ``detect_words`` describes; the same waits."""
+    ``tile``, ``overlap``, ``tile_batch``: detect in overlapping tiles, as ``detect_words`` describes; the same waits.
+    ``orientation``: None, the default, reads the page as it is, unchanged.  An int k in 0..3 -- the quarter turns
+    counter-clockwise that make the page upright -- reads ``turn_page(page, k)`` (``size`` is applied to the turned page as given) and maps
+    every coordinate of the result back to the page that was passed; every dict gains ``"turns": k``; the same three waits.  ``"auto"`` lets
+    ``page_orientation`` decide first (at most three more waits; where it finds 0 its detection is reused, otherwise the turned page is
+    detected again, so the result is what the explicit k gives).  Anything else is an argument error."""
     decode._check_lm_args("ocr_page", beam_width, lm)
-    det = detect.detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
+    det = None
+    if orient._check_orientation("ocr_page", orientation) is not None:
+        probe = dict(size=size, threshold=threshold, expand=expand, output_height=output_height, max_batch=max_batch, width_unit=width_unit, tile=tile,
+                     overlap=overlap, tile_batch=tile_batch)
+        page_u8, orientation, det = orient._upright("ocr_page", det_model, rec_model, page_u8, orientation, probe)
+    if det is None:
+        det = detect.detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
     if det["n"] == 0:
         return []
-    return read_words(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, chars, beam_width, lm)
+    return read_words(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, chars, beam_width, lm, orientation)
 
 
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
                alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0,
-               chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None, rectify: str = "quad") -> list[dict]:
+               chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None, rectify: str = "quad",
+               orientation: int | None = None) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
     ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
@@ -131,20 +160,23 @@ def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_hei
     polyline of its words at one constant height, so the words of a curved line sit upright and at full height in the crop.  With
     ``"chain"`` every dict keeps ``"quad"`` (still the line quad), ``"text"`` and ``"words"`` and gains ``"spine"`` (the 2n knots of its n
     words as ``[x, y]`` lists: the mid-points of each word's left and right edge, in chain order) and ``"height"`` (the crop's height on the
-    page); with ``chars`` the character quads follow the spine; the same waits.  Any other value is an argument error."""
+    page); with ``chars`` the character quads follow the spine; the same waits.  Any other value is an argument error.
+    ``orientation``: as in ``read_words`` -- the page and the quads are the upright page's, an int k maps the results back to
+    the page that ``turn_page(.., k)`` made it from; the mapped keys are ``"quad"``, ``"words"``, ``"char_quads"`` and ``"spine"``."""
     decode._check_lm_args("read_lines", beam_width, lm)
     _check_rectify("read_lines", rectify)
+    _check_upright_turns("read_lines", orientation)
     found = line_stage.find_lines(quads, None, max_gap, min_cos)
     order = line_stage.reading_order(found, block_gap) if reading_order else None
     stages = _crop_stages(rectify, quads, found, output_height, partial(crops.rectify_crops, page_u8), partial(chain.rectify_chain, page_u8))
-    return _read_quads(rec_model, *stages, quads, found, order, max_batch, width_unit, alphabet, chars, beam_width, lm)[0]
+    return _turned_back(_read_quads(rec_model, *stages, quads, found, order, max_batch, width_unit, alphabet, chars, beam_width, lm)[0], page_u8, orientation)
 
 
 def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
               beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16,
-              rectify: str = "quad") -> list[dict]:
+              rectify: str = "quad", orientation=None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
@@ -155,21 +187,29 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE
     of each word in ``"text"``) and ``"word_texts"`` (``text[first:end]``); still three waits.  ``beam_width``: as in
     ``read_lines``; ``lm``: as in ``read_lines``.  ``tile``, ``overlap``, ``tile_batch``: detect in overlapping
     tiles, as ``detect_words`` describes; still three waits.  ``rectify`` (DESIGN.md §21): ``"quad"`` or ``"chain"``, as in ``read_lines``;
-    still three waits."""
+    still three waits.  ``orientation``: None, an int 0..3 or ``"auto"``, as in ``ocr_page``: the page is turned upright, read as
+    it always is, and ``"quad"``, ``"words"``, ``"char_quads"`` and ``"spine"`` are mapped back to the page that was passed; every dict gains
+    ``"turns"``; still three waits for an int, at most three more (and the second detection's) for ``"auto"``."""
     decode._check_lm_args("ocr_lines", beam_width, lm)
     _check_rectify("ocr_lines", rectify)
-    det = detect.detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
+    det = None
+    if orient._check_orientation("ocr_lines", orientation) is not None:
+        probe = dict(size=size, threshold=threshold, expand=expand, output_height=output_height, max_batch=max_batch, width_unit=width_unit, tile=tile,
+                     overlap=overlap, tile_batch=tile_batch)
+        page_u8, orientation, det = orient._upright("ocr_lines", det_model, rec_model, page_u8, orientation, probe)
+    if det is None:
+        det = detect.detect_words(det_model, page_u8, size, threshold, expand, tile, overlap, tile_batch)
     if det["n"] == 0:
         return []
     return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars,
-                      beam_width, lm, rectify)
+                      beam_width, lm, rectify, orientation)
 
 
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
               beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16,
-              rectify: str = "quad") -> list[list[dict]]:
+              rectify: str = "quad", orientation=None) -> list[list[dict]]:
     """A list of (1,H_p,W_p) uint8 device pages of any sizes -> one result list per page, in page order: what ``ocr_lines`` returns for a page
     (``lines=True``: ``quad``, ``text``, ``words`` in chain order, lines in line order) or what ``ocr_page`` returns (``lines=False``: ``quad``,
     ``text`` in raster order).  One detection forward; the crops of ALL pages go through one plan and one set of width-sorted chunks, so a
@@ -185,12 +225,28 @@ def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=detect.MASK_
     ``tile``, ``overlap``, ``tile_batch``: detect every page in overlapping tiles, as ``detect_words`` describes; the tiles of all
     pages are pooled into the same forward chunks and cut from the page store the crops are cut from; the same waits.
     ``rectify`` (with ``lines``): ``"quad"`` or ``"chain"``, as in ``read_lines``; ``"chain"`` with ``lines=False`` is an
-    argument error; the same waits."""
+    argument error; the same waits.
+    ``orientation``: None, an int 0..3 or ``"auto"`` for all pages, or a list with one such entry per page.  Every page is turned
+    upright (``turn_page``), the turned pages go through the one batched path above, and each page's results are mapped back to the page
+    that was passed, every dict with ``"turns"``.  Ints add no wait; ``"auto"`` probes page by page (``page_orientation``), so ITS waits -- one
+    detection's and at most three more -- are per probed page, ahead of the batch's three."""
     decode._check_lm_args("ocr_pages", beam_width, lm)
     _check_rectify("ocr_pages", rectify, lines)
+    pages = list(pages)
+    orientation = orient._check_orientation("ocr_pages", orientation, len(pages))
     pages = _check_pages(pages, "ocr_pages")
     if not pages:
         return []
+    if orientation is not None:
+        turns = orientation if isinstance(orientation, list) else [orientation] * len(pages)
+        for p in pages:
+            orient._check_turn_page(p, "ocr_pages")
+        probe = dict(size=size, threshold=threshold, expand=expand, output_height=output_height, max_batch=max_batch, width_unit=width_unit, tile=tile,
+                     overlap=overlap, tile_batch=tile_batch)
+        turns = [orient.page_orientation(det_model, rec_model, p, **probe)["turns"] if k == "auto" else k for p, k in zip(pages, turns)]
+        read = ocr_pages(det_model, rec_model, [orient.turn_page(p, k) for p, k in zip(pages, turns)], lines, size, threshold, expand, output_height, max_batch,
+                         width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars, beam_width, lm, tile, overlap, tile_batch, rectify)
+        return [orient.turn_results(res, k, p.shape[1], p.shape[2]) for res, k, p in zip(read, turns, pages)]
     B = len(pages)
     store = None if tile is None else detect.pack_pages(pages)
     det = detect.detect_words_batch(det_model, pages, size, threshold, expand, tile, overlap, tile_batch, store)
