@@ -715,6 +715,43 @@ int ocrs_ctc_beam_decode_lm(const float* lp, const long long* in_len, int T, int
 int ocrs_ctc_align_spans(const float* lp, const long long* in_len, int T, int N, int C, long row0, int ld, const int* labels, int* lens, int* t0, int* t1,
                          float* peak, void* ws, long ws_bytes, hipStream_t st);
 
+/* ------------------------------------------------------------------ end-to-end accuracy ------- */
+/* Page OCR scored against annotated words by the rule of DESIGN.md §23 (csrc/ocr_eval.hip; Python: inference/evaluate.py; restated for the
+ * tests in tests/eval_ref.py).  Everything is pooled over the B pages of a call: pred_quads [P][4][2] and gt_quads [G][4][2] fp32 (convex
+ * quads), page b owning rows pred_offs[b] .. pred_offs[b + 1] resp. gt_offs[b] .. gt_offs[b + 1] (both [B + 1] int); gt_ignore [G] bytes
+ * (non-zero = "do not care").  pair_offs [B + 1] int64: the dense (predictions x annotations) IoU matrix of page b, row-major, starts at
+ * element pair_offs[b] of iou [n_pairs] fp64; max_pairs = the largest matrix of the call (it sizes the grid).  The host knows every one of
+ * these numbers from its inputs: nothing synchronises and nothing is allocated, and a dense matrix has no capacity that could overflow.  A page
+ * whose offsets do not describe rows inside the arrays is skipped by every kernel.  B <= 65535.  Only integers are accumulated: equal input
+ * gives equal bytes.
+ *
+ * ocrs_eval_pair_iou: every element of every page's matrix is written: 0.0 where the strict bounding-box test of box_match_metrics fails,
+ * either area is zero or the intersection is not positive, else inter / (pa + ga - inter) with quad_inter and area_of of the validation metrics
+ * (bit for bit the host's quad_intersection_area / _area arithmetic).  ign_hit [P] int: zeroed, then 1 where inter / pa > 0.5 against an
+ * ignored annotation of the prediction's page. */
+int ocrs_eval_pair_iou(const float* pred_quads, const int* pred_offs, const float* gt_quads, const int* gt_offs, const unsigned char* gt_ignore,
+                       const long long* pair_offs, int B, long P, long G, long n_pairs, long max_pairs, double* iou, int* ign_hit, hipStream_t st);
+/* The greedy one-to-one matching of each page: candidates are the pairs with a not ignored annotation and iou > min_iou, totally ordered by
+ * (iou descending, prediction ascending, annotation ascending); a pair is taken when both its ends are free.  One workgroup per page, rounds
+ * of mutually-best pairs (exactly the greedy result, since the order is strict).  gt_of_pred [P] int: the annotation's index WITHIN ITS PAGE,
+ * -1 = unmatched, -2 = unmatched and ign_hit set (ignored); pred_of_gt [G] int likewise (-1 = unmatched); iou_of_pred [P] fp64: the matched
+ * pair's IoU, 0.0 otherwise.  ws: ocrs_eval_match_ws_bytes(P, G) bytes, 4-byte aligned. */
+long ocrs_eval_match_ws_bytes(long P, long G);
+int ocrs_eval_match(const double* iou, const long long* pair_offs, const int* pred_offs, const int* gt_offs, const unsigned char* gt_ignore,
+                    const int* ign_hit, int B, long P, long G, long n_pairs, double min_iou, int* gt_of_pred, int* pred_of_gt, double* iou_of_pred, void* ws,
+                    hipStream_t st);
+/* Texts are Unicode code points: pred_text [n_pred_text] int with pred_text_offs [P + 1] int, gt_text / gt_text_offs [G + 1] likewise.  For
+ * every prediction: dist [P] int = the Levenshtein distance to its matched annotation (the wave routine of ocrs_edit_distance, no code table),
+ * -1 when unmatched; flags [P] int = 1 (equal) | 2 (equal after folding ASCII A-Z to lower case only), 0 when unmatched.  bnd: n_pred_text
+ * ints of scratch.  max_page_preds = the largest number of predictions on one page (it sizes the grid).  state (NULL = no counting): int64
+ * [12], integer atomics ADD to it across calls: pages | predictions not ignored | annotations not ignored | predictions ignored | matched
+ * pairs | exact | exact ignoring ASCII case | edit distance over matched pairs | annotated characters of matched pairs | predicted characters
+ * of unmatched, not ignored predictions | annotated characters of unmatched, not ignored annotations | annotated characters of all not ignored
+ * annotations.  Two launches. */
+int ocrs_eval_text_update(const int* pred_offs, const int* gt_offs, const unsigned char* gt_ignore, int B, long P, long G, int max_page_preds,
+                          const int* gt_of_pred, const int* pred_of_gt, const int* pred_text, const int* pred_text_offs, long n_pred_text,
+                          const int* gt_text, const int* gt_text_offs, long n_gt_text, int* bnd, int* dist, int* flags, long long* state, hipStream_t st);
+
 /* ------------------------------------------------------------------ layout model -------------- */
 /* LayoutModel (ocrs_models/models.py:340-406) and its loss / statistics (train_layout.py:15-171); csrc/layout.hip.  All storage fp32; a row is
  * one (page n, word w) token, row index n * W + w.  The Linear layers run on ocrs_conv_igemm / ocrs_gemm_x3[p] / ocrs_wgrad_*.

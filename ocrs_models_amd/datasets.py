@@ -18,7 +18,7 @@ import json
 import os
 import pickle
 from concurrent.futures import ThreadPoolExecutor
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -513,6 +513,93 @@ def generate_json_lines_annotations(annotations_file: str, lines_file: str):
 def hiertext_word_polygons(annotations: dict) -> list:
     """hiertext.py:77-86: every word of every line of every paragraph, in that order."""
     return [[tuple(coord) for coord in word["vertices"]] for para in annotations["paragraphs"] for line in para["lines"] for word in line["words"]]
+
+
+class WordTruth(NamedTuple):
+    """The annotated words (or lines) of one page, as the end-to-end evaluation reads them (inference/evaluate.py)."""
+    image_id: Optional[str]
+    quads: np.ndarray   # (G, 4, 2) float32: convex quads
+    texts: list         # G strings
+    ignore: np.ndarray  # (G,) bool: "do not care" regions
+
+
+def _truth_region(vertices) -> np.ndarray:
+    """(4, 2) float64 region of an annotated polygon: its own vertices when they are exactly four and form a convex quad of non-zero area,
+    otherwise the minimum-area rectangle of its hull (``postprocess._hull`` / ``_min_area_rect``, which take whole-numbered vertices)."""
+    from .postprocess import _hull, _min_area_rect
+
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 2)
+    if len(v) == 4:
+        e = np.roll(v, -1, axis=0) - v
+        f = np.roll(e, -1, axis=0)
+        turn = e[:, 0] * f[:, 1] - e[:, 1] * f[:, 0]
+        area2 = float(np.dot(v[:, 0], np.roll(v[:, 1], -1)) - np.dot(v[:, 1], np.roll(v[:, 0], -1)))
+        if area2 != 0.0 and ((turn >= 0).all() or (turn <= 0).all()):
+            return v
+    return np.asarray(_min_area_rect(_hull(np.asarray(vertices).reshape(-1, 2))), dtype=np.float64).reshape(4, 2)
+
+
+def _truth_record(image_id, polygons, texts, ignore) -> WordTruth:
+    quads = np.array([_truth_region(p) for p in polygons], dtype=np.float32).reshape(-1, 4, 2)
+    return WordTruth(image_id, quads, [str(t) for t in texts], np.array([bool(i) for i in ignore], dtype=bool).reshape(-1))
+
+
+def from_words(quads, texts, ignore=None, image_ids=None) -> list:
+    """The records of ``hiertext_word_truth`` from lists, one entry per page: ``quads[p]`` = that page's polygons (any vertex count; reduced
+    to convex quads by the same rule), ``texts[p]`` its strings, ``ignore[p]`` its flags (None: nothing is ignored beyond empty texts)."""
+    if len(quads) != len(texts) or (ignore is not None and len(ignore) != len(quads)) or (image_ids is not None and len(image_ids) != len(quads)):
+        raise ValueError("from_words: quads, texts, ignore and image_ids need one entry per page")
+    out = []
+    for p, (q, t) in enumerate(zip(quads, texts)):
+        ig = [False] * len(t) if ignore is None else list(ignore[p])
+        if len(q) != len(t) or len(ig) != len(t):
+            raise ValueError(f"from_words: page {p} has {len(q)} quads, {len(t)} texts and {len(ig)} flags")
+        out.append(_truth_record(None if image_ids is None else image_ids[p], list(q), t, [bool(i) or str(s) == "" for i, s in zip(ig, t)]))
+    return out
+
+
+def _hiertext_annotations(root_dir: str, train: bool, max_images) -> list:
+    """the split's JSON-lines file (written from the annotations when it is missing or older) and the selection ``HierText`` makes from it"""
+    split = "train" if train else "validation"
+    annotations_file = f"{root_dir}/gt/{split}.jsonl.gz"
+    if not os.path.exists(annotations_file):
+        raise Exception(f'Label data file "{annotations_file}" not found')
+    lines_file = annotations_file.replace(".jsonl.gz", ".jsonl")
+    generate_json_lines_annotations(annotations_file, lines_file)
+    with open(lines_file) as fp:
+        annotations = [line for line in fp]
+    if max_images:
+        annotations = annotations[:max_images]
+    return [json.loads(a) for a in annotations]
+
+
+def _truth_ignored(item: dict, ignore_vertical: bool) -> bool:
+    return item.get("legible", True) is False or item.get("text", "") == "" or (ignore_vertical and item.get("vertical", False) is True)
+
+
+def hiertext_word_truth(root_dir: str, train=False, max_images=None, ignore_vertical=False) -> list:
+    """One ``WordTruth`` per image of the split, in ``HierText``'s order, words in the order of ``hiertext_word_polygons``.  A word is ignored
+    when it is illegible, has no text or (``ignore_vertical``) is vertical.  No image is read."""
+    out = []
+    for ann in _hiertext_annotations(root_dir, train, max_images):
+        words = [word for para in ann["paragraphs"] for line in para["lines"] for word in line["words"]]
+        out.append(_truth_record(ann["image_id"], [w["vertices"] for w in words], [w.get("text", "") for w in words],
+                                 [_truth_ignored(w, ignore_vertical) for w in words]))
+    return out
+
+
+def hiertext_line_truth(root_dir: str, train=False, max_images=None, ignore_vertical=False) -> list:
+    """``hiertext_word_truth`` for annotated LINES: the region is the minimum-area rectangle of the hull of the line's word vertices, the text
+    the line's ``text``; ignored as words are."""
+    from .postprocess import _hull, _min_area_rect
+
+    out = []
+    for ann in _hiertext_annotations(root_dir, train, max_images):
+        lines = [line for para in ann["paragraphs"] for line in para["lines"]]
+        quads = [_min_area_rect(_hull(np.array([v for w in line["words"] for v in w["vertices"]]).reshape(-1, 2))) for line in lines]
+        out.append(WordTruth(ann["image_id"], np.array(quads, dtype=np.float32).reshape(-1, 4, 2), [str(line.get("text", "")) for line in lines],
+                             np.array([_truth_ignored(line, ignore_vertical) for line in lines], dtype=bool).reshape(-1)))
+    return out
 
 
 class DDI100Unpickler(pickle.Unpickler):

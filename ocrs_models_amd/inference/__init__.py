@@ -84,7 +84,12 @@ zero-padded mask canvas, one line stage that keeps to each word's own page, one 
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
 per page.  The single-page functions above are what its tests compare it with.
 
-The package, by stage: ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops), ``orient`` (page turns and their detection),
+Accuracy (csrc/ocr_eval.hip, C ABI section "end-to-end accuracy"; restated for the tests in tests/eval_ref.py).  ``evaluate_pages``
+runs ``ocr_pages`` over annotated pages and says how many words were found and how many were read correctly: ``match_words`` assigns predicted
+to annotated words one to one on the device, ``OcrAccuracyStats`` keeps integer counters there across ``update`` calls (no wait) and
+``result()`` is the one wait.  It consumes the drivers' results and changes none of them.
+
+The package, by stage: ``evaluate`` (the accuracy above), ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops), ``orient`` (page turns and their detection),
 ``decode`` (the recogniser, characters, and the ``Decoded`` record every decode is read into), ``assemble`` (record + host lists -> result
 dicts, no GPU) and ``drivers`` (``ocr_page``, ``read_words``, ``read_lines``, ``ocr_lines``, ``ocr_pages``).  Everything is re-exported here.
 """
@@ -97,6 +102,7 @@ from .decode import CharBoxes, CharSpans, Decoded, char_boxes, chars_to_host, de
 from .detect import (MASK_SIZE, SHRINK_DISTANCE, _cc_quads_pages_sizes, binarize_resize, binarize_resize_pages, cc_quads_pages, detect_words,  # noqa: F401
                      detect_words_batch, expand_quads, gather_page_quads, pack_pages)
 from .drivers import _read_crops, ocr_lines, ocr_page, ocr_pages, read_lines, read_words  # noqa: F401
+from .evaluate import Matches, OcrAccuracyStats, evaluate_pages, match_words  # noqa: F401
 from .lines import ReadingOrder, TextLines, find_lines, find_lines_pages, page_text, reading_order, split_by_page  # noqa: F401
 from .orient import orientation_votes, page_orientation, path_confidence, probe_batches, turn_page, turn_quads, turn_results, turn_shape  # noqa: F401
 from .tiles import TILES_AXIS_MAX, AxisPlan, TilePlan, TileTables, binarize_resize_tiles, tile_batch, tile_plan, tile_tables  # noqa: F401
