@@ -206,10 +206,12 @@ int ocrs_dwpw_c1_bwd(const float* img, const float* wdw, const float* wpw, const
 long ocrs_convt_bwd_ws_floats(int Cup, int Cout, int N, int h, int w, int dtype);
 /* saved / gsum (nullable; need ocrs_convt_bwd_stats_supported): x is the raw output of a block consumed ONLY by this ConvTranspose -> its
  * BatchNorm-backward sums [2][Cup] (fp64, ACCUMULATED; saved = the block's [mean | rstd]) come from this pass instead of ocrs_bn_bwd_reduce. */
-/* dbias64 [Cout] fp64 (caller-zeroed): where the generic (deep-level) path accumulates the bias gradient; the caller adds it to dbias.  fp32 with
- * Cup <= 32 (the row-streaming weight-gradient kernel, csrc/det_rs32.hip): the bias gradient goes to dbias and dbias64 is not written.
- * ws: ocrs_convt_bwd_ws_floats() floats.  Inside a deferral window (ocrs_bwd_defer_begin) that kernel queues its reduction of ws into dW / dbias
- * until ocrs_bwd_defer_flush: ws must stay alive until then, and dW / dbias are complete only after it.  The same holds for ocrs_convt_bwd_parts. */
+/* dbias64 [Cout] fp64 (caller-zeroed): where the generic (deep-level) path accumulates the bias gradient; the caller adds it to dbias.  The tiled
+ * bf16 path of levels 0-2 adds the bias gradient to dbias itself, and so does fp32 with a workspace, Cup in {16, 32} and Cout in {8, 16, 32} (the
+ * row-streaming weight-gradient kernel, csrc/det_rs32.hip): dbias64 then stays as the caller zeroed it.
+ * ws: ocrs_convt_bwd_ws_floats() floats.  Inside a deferral window (ocrs_bwd_defer_begin) the row-streaming kernel queues its reduction of ws into
+ * dW / dbias until ocrs_bwd_defer_flush: ws must stay alive until the flush, and dW / dbias are complete only after it.
+ * All of this holds for the weight + bias half (parts & 2) of ocrs_convt_bwd_parts as well. */
 int ocrs_convt_bwd(const void* x, const float* tr, const void* g, const void* wpk_d, void* dx, float* dW, float* dbias, double* dbias64, float* ws,
                    const float* saved, double* gsum, int Cup, int Cout, int N, int h, int w, int H, int W, int dtype, hipStream_t st);
 long ocrs_convt_bwd_stats_supported(int Cup, int Cout, int dtype); /* 1 / 0 */

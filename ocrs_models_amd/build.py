@@ -73,7 +73,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
                 raise RuntimeError(f"{os.path.basename(chk)}: hipcc touched an in-flight asm-load register in {asm_src}:\n" + r.stdout[-3000:])
     objs = [os.path.join(OBJ, src + ".o") for src in sources()]
     if force or jobs or not os.path.exists(LIB):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs]
+        # -z defs: an internal prototype (det_internal.h, rec_internal.h) that has drifted from its definition is an undefined symbol at link time
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", "-o", LIB, *objs]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

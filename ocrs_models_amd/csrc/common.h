@@ -262,7 +262,7 @@ struct Mma;
 
 template <>
 struct Mma<bf16> {
-    // LDS tile row of the chunked detection kernels (det_fwd.hip / det_bwd.hip, outside the bf16 train step): 32 bf16 + 8 pad = 80 B (16-B aligned).
+    // LDS tile row of the chunked detection kernels (det_fwd.hip / det_bwd.hip / det_convt.hip, outside the bf16 train step): 32 bf16 + 8 pad = 80 B (16-B aligned).
     // Under the lane groups described at lds_pitch_bf16 a ds_read_b128 fragment read over 16 such rows takes 8 LDS cycles instead of 4.
     static constexpr int LDS_PITCH = 40;
     // packed weight fragment: 8 bf16 per lane per (chunk, tile) = one 16-B load
@@ -429,6 +429,13 @@ OcrsProf& ocrs_prof();
             hipLaunchKernelGGL(kernel, grid, block, smem, st, __VA_ARGS__);                                 \
         }                                                                                                   \
     } while (0)
+
+// grid of an element-wise pass: one thread per item, at most 8 blocks of 256 per CU (the kernels loop)
+static inline int ew_grid(long items) {
+    long g = (items + 255) / 256;
+    const long cap = (long)kNumCU * 8;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
 
 static inline int persistent_grid(long ntiles, int blocks_per_cu) {
     long cap = (long)kNumCU * blocks_per_cu;

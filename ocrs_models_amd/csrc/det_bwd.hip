@@ -6,9 +6,12 @@
 //   k_pw_bwd           dz tile + recomputed u tile in LDS; MFMA dgrad (du = Wpw^T dz) and wgrad (dWpw += u^T dz): fp32 and the deep
 //                      (Cin or Cout > 32) bf16 levels; bf16 levels 0-2 run k_pw_bwd2 (det_pw2.hip)
 //   k_dw_bwd           dx~ = dw3x3^T(du), dWdw
-// plus ConvTranspose2d dgrad / wgrad, head backward, first-block (1->8) backward.
-#include "det_common.h"
-#include "loss_state.h"
+// plus the ConvTranspose2d backward (k_convt_wgrad_tr, k_convt_dgrad, k_channel_sum) and the first block's per-pixel backward (k_c1_bwd).
+//
+// Those two families stay in this file although their forward halves live in det_convt.hip / det_c1.hip: hipcc optimises the inlined helpers they
+// share with k_pw_bwd per translation unit, and compiled apart the code of k_c1_bwd and of 21 k_pw_bwd instantiations changes (registers, scratch;
+// tools/kernel_diff.py).  The head (det_head.hip) and the deferral queue (det_defer.hip) share nothing of the kind and have their own files.
+#include "det_internal.h"
 
 // ----------------------------------------------------------------------------------------------
 template <class T>
@@ -1188,244 +1191,9 @@ __global__ __launch_bounds__(256) void k_channel_sum(const T* __restrict__ g, do
     }
 }
 
-// head backward: pred = sigmoid(w . x~ + b);  gl = gpred * pred * (1 - pred);  gy[p][c] = gl * w[c];  dw, db.
-template <class T>
-__global__ __launch_bounds__(256) void k_head_bwd(const T* __restrict__ z, const float* __restrict__ tr, const float* __restrict__ w,
-                                                  const float* __restrict__ pred, const float* __restrict__ gpred, T* __restrict__ gy,
-                                                  double* __restrict__ acc64 /*[9]: dw[8] | db*/, const float* __restrict__ saved /*[2][8] or null*/,
-                                                  double* __restrict__ gsum /*[2][8] or null*/, long P, float* __restrict__ gl_out /*[P] or null*/) {
-    // gl_out != null (round 5): instead of the 8-channel gradient gy (16 B per pixel in bf16) only gl = dL/dlogit is written (4 B); the block
-    // backward that consumes it (k_rs_bwd<..., HEAD>) forms gy = round(gl * w[c]) on the fly -- the same values: 12 B per pixel less written here
-    // and 12 B less read there
-    // gsum != null: also the BatchNorm-backward sums (sum ghat, sum ghat*zhat) of the block that produced z -- this kernel is that
-    // block's only consumer and already reads z, so its k_bn_bwd_reduce pass (0.24 ms at 32x1024^2) is not needed
-    __shared__ float s_slots[4 * 25];
-    float wv[8], sc[8], sh[8], lo[8], mu[8], acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st1[8], st2[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        wv[i] = w[i];
-        sc[i] = tr[i];
-        sh[i] = tr[8 + i];
-        lo[i] = tr[16 + i];
-        mu[i] = gsum ? saved[i] : 0.f;
-        st1[i] = st2[i] = 0.f;
-    }
-    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
-        const float pr = pred[p];
-        const float gl = gpred[p] * (1.f - pr) * pr;
-        float v[8], o[8];
-        load8(z + p * 8, v);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float pre = fmaf(v[i], sc[i], sh[i]);
-            const float xv = fmaxf(pre, lo[i]);
-            acc[i] = fmaf(gl, xv, acc[i]);
-            o[i] = gl * wv[i];
-            const float gh = pre > 0.f ? Elem<T>::round(o[i]) : 0.f;  // what the block's pw_bwd will read back
-            st1[i] += gh;
-            st2[i] = fmaf(gh, v[i] - mu[i], st2[i]);
-        }
-        acc[8] += gl;
-        if (gl_out) gl_out[p] = gl;
-        else store8(gy + p * 8, o);
-    }
-    // deterministic block sums (no LDS float atomics), fp64 accumulation across blocks
-    float all[25];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) all[i] = acc[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        all[9 + i] = st1[i];
-        all[17 + i] = st2[i];
-    }
-    const float tot = block_sum_det<25>(all, s_slots);
-    if (threadIdx.x < 9) atomicAdd(&acc64[threadIdx.x], (double)tot);
-    if (gsum && threadIdx.x >= 9 && threadIdx.x < 25) {
-        const int i = threadIdx.x - 9;  // 0..7: sum ghat, 8..15: sum ghat*(z - mean) -> * rstd
-        atomicAdd(&gsum[i], (double)(i < 8 ? tot : tot * saved[8 + (i - 8)]));
-    }
-}
-
-// Balanced-BCE backward + head backward in ONE pass (round 5): dL/dpred is formed on the fly from what the loss forward saved (class map,
-// per-pixel loss, the two radix-select thresholds: the arithmetic of k_bce_bwd in loss_optim.hip, operation for operation) instead of being
-// written by k_bce_bwd (4 B per pixel) and read back here (4 B) -- 33 instead of 45 B per pixel over the two launches, one launch and one
-// 134 MB buffer less per step.  Four pixels per thread and iteration (16-byte loads of pred / target / lpx, one dword of classes, four 16-byte z
-// vectors, one 16-byte gl store).  Only the gl form (k_rs_bwd<..., HEAD> consumes gl); P % 4 == 0.
-template <class T>
-__global__ __launch_bounds__(256) void k_head_bwd_loss(const T* __restrict__ z, const float* __restrict__ tr, const float* __restrict__ w,
-                                                       const float* __restrict__ pred, const float* __restrict__ target,
-                                                       const float* __restrict__ lpx, const unsigned char* __restrict__ cls,
-                                                       const LossState* __restrict__ stt, const float* __restrict__ gout,
-                                                       double* __restrict__ acc64 /*[9]: dw[8] | db*/, const float* __restrict__ saved /*[2][8]*/,
-                                                       double* __restrict__ gsum /*[2][8]*/, long P, float* __restrict__ gl_out /*[P]*/) {
-    __shared__ float s_slots[4 * 25];
-    float wv[8], sc[8], sh[8], lo[8], mu[8], acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st1[8], st2[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        wv[i] = w[i];
-        sc[i] = tr[i];
-        sh[i] = tr[8 + i];
-        lo[i] = tr[16 + i];
-        mu[i] = saved[i];
-        st1[i] = st2[i] = 0.f;
-    }
-    const unsigned t0 = stt->prefix[0], t1 = stt->prefix[1];
-    const float f0 = stt->frac[0], f1 = stt->frac[1];
-    const float s = gout[0] * stt->inv2k;
-    const long nq = P >> 2;
-    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-        const float4 p4 = reinterpret_cast<const float4*>(pred)[q], t4 = reinterpret_cast<const float4*>(target)[q];
-        const float4 l4 = reinterpret_cast<const float4*>(lpx)[q];
-        const unsigned c4 = reinterpret_cast<const unsigned*>(cls)[q];
-        float v[4][8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) load8(z + (q * 4 + e) * 8, v[e]);
-        const float pe[4] = {p4.x, p4.y, p4.z, p4.w}, te[4] = {t4.x, t4.y, t4.z, t4.w}, le[4] = {l4.x, l4.y, l4.z, l4.w};
-        float gle[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned c = (c4 >> (8 * e)) & 0xffu;
-            const float pr = pe[e];
-            float gp = 0.f;  // k_bce_bwd's grad()
-            if (c) {
-                const unsigned key = loss_key(le[e]);
-                const unsigned thr = c == 1 ? t0 : t1;
-                const float wgt = key > thr ? 1.f : (key == thr ? (c == 1 ? f0 : f1) : 0.f);
-                if (wgt != 0.f) {
-                    const float t = fminf(fmaxf(te[e], 0.f), 1.f);
-                    gp = s * wgt * (pr - t) / fmaxf((1.f - pr) * pr, 1e-12f);
-                }
-            }
-            const float gl = gp * (1.f - pr) * pr;
-            gle[e] = gl;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float pre = fmaf(v[e][i], sc[i], sh[i]);
-                const float xv = fmaxf(pre, lo[i]);
-                acc[i] = fmaf(gl, xv, acc[i]);
-                const float gh = pre > 0.f ? Elem<T>::round(gl * wv[i]) : 0.f;  // what the block's backward forms from gl
-                st1[i] += gh;
-                st2[i] = fmaf(gh, v[e][i] - mu[i], st2[i]);
-            }
-            acc[8] += gl;
-        }
-        reinterpret_cast<float4*>(gl_out)[q] = make_float4(gle[0], gle[1], gle[2], gle[3]);
-    }
-    float all[25];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) all[i] = acc[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        all[9 + i] = st1[i];
-        all[17 + i] = st2[i];
-    }
-    const float tot = block_sum_det<25>(all, s_slots);
-    if (threadIdx.x < 9) atomicAdd(&acc64[threadIdx.x], (double)tot);
-    if (threadIdx.x >= 9 && threadIdx.x < 25) {
-        const int i = threadIdx.x - 9;
-        atomicAdd(&gsum[i], (double)(i < 8 ? tot : tot * saved[8 + (i - 8)]));
-    }
-}
-
 // ----------------------------------------------------------------------------------------------
-// Deferred second stage of the block backward's flushes (round 5; see BwdLast in det_common.h).  Between ocrs_bwd_defer_begin and
-// ocrs_bwd_defer_flush the single-writer reductions of weight-gradient partials (k_mm_bwd_reduce's weight part, k_wgrad_partials_reduce,
-// k_dw_partials_reduce's tap rows) are not launched but queued; the flush runs them all as ONE launch (same column-sum order: bit-identical
-// gradients).  Per-device state (one backward at a time per device; `defer_state()` below).
+// host side
 // ----------------------------------------------------------------------------------------------
-struct RedJob {
-    const float* ws;
-    float *d0, *d1;
-    int nb, nelem, n0, cin0, ldw0, n1, blk0;
-};
-constexpr int RED_MAXJOBS = 48;
-struct RedJobs {
-    int njobs;
-    RedJob j[RED_MAXJOBS];
-};
-__global__ __launch_bounds__(256) void k_reduce_multi(RedJobs J) {
-    int k = 0;
-    while (k + 1 < J.njobs && (int)blockIdx.x >= J.j[k + 1].blk0) ++k;
-    const RedJob& q = J.j[k];
-    const long e = (long)((int)blockIdx.x - q.blk0) * 32 + (threadIdx.x & 31);
-    float s;
-    if (!det_column_sum(q.ws, q.nb, q.nelem, e < q.n0 + q.n1 ? e : (long)q.nelem, s)) return;
-    if (e < q.n0)
-        q.d0[(e / q.cin0) * q.ldw0 + e % q.cin0] += s;
-    else
-        q.d1[e - q.n0] += s;
-}
-// One state per DEVICE: a backward of a second model on another GPU of the same process (autograd runs one worker thread per device) has
-// its own queue, scratch and partials workspace -- indexed by the calling thread's current device at every entry.
-struct DeferState {
-    bool on = false;
-    double* scratch = nullptr;
-    long cap = 0, used = 0;
-    int nblocks = 0;
-    RedJobs jobs;
-    // workspace for per-block partials of launches whose entry points take none (the CRNN's bias / first-layer sums: rec_pool.hip, rec_conv0.hip,
-    // rec_gru_seq.hip): a per-device buffer (allocated on that device at first use), bump-allocated between _begin and _flush; null outside that
-    // window, when it is used up, or when the allocation is refused (e.g. inside a stream capture: callers then take their atomic path)
-    float* ws = nullptr;
-    long ws_used = 0;
-};
-constexpr int DEFER_MAXDEV = 16;
-static DeferState g_defer_dev[DEFER_MAXDEV];
-static DeferState& defer_state() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= DEFER_MAXDEV) d = 0;
-    return g_defer_dev[d];
-}
-constexpr long DEFER_WS_FLOATS = 8L << 20;  // 32 MB
-float* bwd_defer_ws(long nfloats) {
-    DeferState& D = defer_state();
-    if (!D.on || nfloats <= 0) return nullptr;
-    if (!D.ws && hipMalloc(reinterpret_cast<void**>(&D.ws), DEFER_WS_FLOATS * sizeof(float)) != hipSuccess) {
-        D.ws = nullptr;
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    const long n = (nfloats + 63) & ~63L;
-    if (D.ws_used + n > DEFER_WS_FLOATS) return nullptr;
-    float* p = D.ws + D.ws_used;
-    D.ws_used += n;
-    return p;
-}
-double* bwd_defer_scratch(int ndoubles) {
-    DeferState& D = defer_state();
-    if (!D.on || D.used + ndoubles > D.cap) return nullptr;
-    double* p = D.scratch + D.used;
-    D.used += (ndoubles + 1) & ~1L;
-    return p;
-}
-bool bwd_defer_reduce(const float* ws, int nb, int nelem, float* d0, int n0, int cin0, int ldw0, float* d1, int n1) {
-    DeferState& D = defer_state();
-    if (!D.on || D.jobs.njobs >= RED_MAXJOBS || n0 + n1 <= 0) return false;
-    RedJob& q = D.jobs.j[D.jobs.njobs++];
-    q = RedJob{ws, d0, d1, nb, nelem, n0, cin0 > 0 ? cin0 : 1, ldw0, n1, D.nblocks};
-    D.nblocks += (n0 + n1 + 31) / 32;
-    return true;
-}
-// queue the reduction (deferral window open) or run it now as a one-job launch of the same kernel (same column-sum order: bit-identical gradients)
-void bwd_reduce_or_defer(const float* ws, int nb, int nelem, float* d0, int n0, int cin0, int ldw0, float* d1, int n1, hipStream_t st) {
-    if (n0 + n1 <= 0 || bwd_defer_reduce(ws, nb, nelem, d0, n0, cin0, ldw0, d1, n1)) return;
-    RedJobs J;
-    J.njobs = 1;
-    J.j[0] = RedJob{ws, d0, d1, nb, nelem, n0, cin0 > 0 ? cin0 : 1, ldw0, n1, 0};
-    hipLaunchKernelGGL(k_reduce_multi, dim3((n0 + n1 + 31) / 32), dim3(256), 0, st, J);
-}
-
-// ----------------------------------------------------------------------------------------------
-// C ABI
-// ----------------------------------------------------------------------------------------------
-static inline int ew_grid(long items) {
-    long g = (items + 255) / 256;
-    const long cap = (long)kNumCU * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-// grid for kernels whose threads keep a fixed channel group: total threads must be a multiple of the group count (<= 64, divides 256)
-static inline int cg_grid(long items) { return ew_grid(items); }
-
 // wgrad-carrying persistent grids: each block flushes a weight-gradient tile with atomics, so make every block
 // chew through >= 8 pixel tiles when there are enough of them.
 static inline int wgrad_grid(long ntiles, int cap_blocks) {
@@ -1435,44 +1203,6 @@ static inline int wgrad_grid(long ntiles, int cap_blocks) {
     if (g >= 8) g &= ~7L;
     return (int)g;
 }
-
-extern "C" int ocrs_wgrad_gather(const void* A, int ldA, int CA, const float* trA, const void* B, int ldB, int CB, float* dW, float* ws, int N, int hA,
-                                 int wA, int HB, int WB, int stride, int padh, int padw, int KH, int KW, int dtype, hipStream_t st);
-
-extern "C" {
-
-// Sum of ghat and ghat*zhat over all pixels (BatchNorm2d backward reductions).  gsum [2][C] double, ACCUMULATED (caller zeroes).
-int ocrs_bn_bwd_reduce(const void* g1, const void* g2, int pooled, const void* z, const float* bn, const float* saved, double* gsum, int C,
-                       int N, int H, int W, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(g1 && z && bn && saved && gsum && C % 8 == 0 && C <= 256);
-    const long P = (long)N * H * W;
-    // every block ends with 2C fp64 atomics onto the same addresses: at the deep levels (tens of thousands of pixels) give each thread
-    // at least 8 items instead of launching 2048 nearly idle blocks (those launches were 60 us of pure flush)
-    long gl = (P * (C / 8) + 256 * 8 - 1) / (256 * 8);
-    const int bpc = 2;  // blocks per CU: every block ends in 2 C same-address fp64 atomics (~11 ns each, serial per address: 73 -> 54 us at level 1)
-    const int grid = (int)(gl < 8 ? 8 : (gl > kNumCU * bpc ? kNumCU * bpc : gl));
-    const size_t smem = (2 * C + 256 * 16) * sizeof(float);
-    if (dtype == 1) {
-        GradSrc<bf16> gs{(const bf16*)g1, (const bf16*)g2, pooled};
-        OCRS_LAUNCH_T(k_bn_bwd_reduce<bf16>, dim3(grid), dim3(256), smem, st, gs, (const bf16*)z, bn, saved, gsum, C, H, W, P);
-    } else {
-        GradSrc<float> gs{(const float*)g1, (const float*)g2, pooled};
-        OCRS_LAUNCH_T(k_bn_bwd_reduce<float>, dim3(grid), dim3(256), smem, st, gs, (const float*)z, bn, saved, gsum, C, H, W, P);
-    }
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-
-int ocrs_bn_bwd_finalize(const double* gsum, long count, int C, const float* gamma, const float* saved, float* coef, float* dgamma,
-                         float* dbeta, hipStream_t st) {
-    OCRS_CHECK_ARG(gsum && gamma && saved && coef && dgamma && dbeta && C > 0 && count > 0);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, st, gsum, count, C, gamma, saved, coef, dgamma, dbeta);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-
-}  // extern "C" (templates need C++ linkage)
-static inline int wgrad_grid(long ntiles, int cap_blocks);
 template <int CIN, int COUT>
 static int pw_bwd_gx(int N, int H, int W) {
     using Cfg = PwBwdCfg<CIN, COUT>;
@@ -1509,53 +1239,117 @@ static int launch_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const f
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-extern "C" {
 
 #define PW_BWD_COMBOS(X) \
     X(8, 8) X(8, 16) X(16, 16) X(16, 32) X(32, 32) X(32, 64) X(64, 64) X(64, 128) X(128, 128) X(128, 256) X(256, 256) X(256, 128) X(128, 64) \
         X(64, 32) X(32, 16) X(16, 8)
 
-// Pointwise-conv backward of a DepthwiseConv block: du = Wpw^T dz (written, [P][Cin]); dwpw += u^T dz (accumulated, master layout
-// [Cout][Cin]); dz is formed on the fly from (g1 [+g2], z, bn, coef), u is recomputed from the block input.
-// wpk_d = ocrs_pack_frags(mode 0, K=Cout, M=Cin) of W^T.
-void k_wgrad_partials_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st) {
+static bool pw_bwd_generic_ok(int Cin, int Cout) {
+#define X(CI, CO) \
+    if (Cin == CI && Cout == CO) return true;
+    PW_BWD_COMBOS(X)
+#undef X
+    return false;
+}
+static int pw_bwd_generic_gx(int Cin, int Cout, int N, int H, int W) {
+#define X(CI, CO) \
+    if (Cin == CI && Cout == CO) return pw_bwd_gx<CI, CO>(N, H, W);
+    PW_BWD_COMBOS(X)
+#undef X
+    return 0;
+}
+// The kernel that takes the pointwise backward of a block shape, stated once for the launch, the workspace size and ocrs_pw_bwd_kernel:
+// 1 = k_pwb (det_pwb.hip), 2 = k_pw_bwd2 (det_pw2.hip), 3 = k_pw_bwd2 once per source of a 32 | 32 concat, 4 = the generic k_pw_bwd, 0 = none.
+// (k_pwb needs Cout >= 64 and k_pw_bwd2 Cout <= 32: at most one of 1-3 applies, the order of the questions decides nothing.)
+static int pw_bwd_route(int Ca, int Cb, int Cout, int dtype) {
+    const int Cin = Ca + Cb;
+    if (det_pwb_supported(Cin, Cout, dtype)) return 1;
+    if (det_pw2_supported(Cin, Cout, dtype)) return 2;
+    if (Ca == 32 && Cb == 32 && det_pw2_supported(32, Cout, dtype)) return 3;
+    return pw_bwd_generic_ok(Cin, Cout) ? 4 : 0;
+}
+// workspace floats of a route: one weight-gradient partial per block of its launch
+static long pw_bwd_route_ws(int route, int Cin, int Cout, int N, int H, int W) {
+    switch (route) {
+    case 1: return (long)det_pwb_gx(Cin, Cout, N, H, W, 0) * Cin * Cout;  // (the not-pooled grid is the larger one)
+    case 2: return det_pw2_ws_floats(Cin, Cout, N, H, W);
+    case 3: return det_pw2_ws_floats(32, Cout, N, H, W);  // (the two launches run one after the other on the same partials)
+    case 4: return (long)pw_bwd_generic_gx(Cin, Cout, N, H, W) * Cin * Cout;
+    }
+    return 0;
+}
+
+void det_wgrad_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st) {
     if (bwd_defer_reduce(ws, nb, nelem, dw, nelem, cin, ldw, nullptr, 0)) return;  // (ocrs_bwd_defer_begin .. _flush: one launch for all of them)
     OCRS_LAUNCH_T(k_wgrad_partials_reduce, dim3((nelem + 31) / 32), dim3(256), 0, st, ws, nb, nelem, dw, cin, ldw);
 }
-// det_pw2.hip: two-pixel-per-thread pipelined kernel for bf16, Cin, Cout <= 32 (levels 0-2)
-long det_pw2_supported(int Cin, int Cout, int dtype);
-long det_pw2_ws_floats(int Cin, int Cout, int N, int H, int W);
-int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
-                   int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
-                   int H, int W, int ldu, int ldw, hipStream_t st);
-long det_pwb_supported(int Cin, int Cout, int dtype);  // det_pwb.hip
-int det_pwb_gx(int Cin, int Cout, int N, int H, int W, int pooled);
-int det_pwb_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
-                   int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
-                   int H, int W, const BnFin* fin, hipStream_t st);
-// a 64-channel concat input (32 | 32) is handled as two k_pw_bwd2<32, Cout> launches, one per source (see ocrs_pw_bwd)
-static bool pw2_split_ok(int Ca, int Cb, int Cout, int dtype) { return Ca == 32 && Cb == 32 && det_pw2_supported(32, Cout, dtype); }
 
+static void dw_bwd_grid(int C, int N, int H, int W, int& gx, int& gy, int& cg) {
+    cg = C / 8 < 4 ? C / 8 : 4;  // channel groups (of 8) per block: 4 -> 8x4-pixel tiles, 2 -> 8x8, 1 -> 8x16
+    gy = C / (cg * 8);
+    const Tiling2 tg = make_tiling2(N, H, W, 32 / cg, 8);
+    // 3 blocks per CU are resident (k_dw_bwd's launch bounds): a grid of exactly that many blocks (all y-slabs together) has no partial last
+    // round -- with 8 per CU the 2048 blocks ran as 2.67 rounds of 768
+    gx = persistent_grid(tg.ntiles, 3 / gy > 0 ? 3 / gy : 1);
+}
+static bool convt_wgrad_tr_ok(int Cup, int Cout, int dtype) {
+    return dtype == 1 && ((Cup == 16 && Cout == 8) || (Cup == 32 && Cout == 16) || (Cup == 32 && Cout == 32));
+}
+static int convt_wgrad_tr_grid(int Cout, int N, int h, int w) {
+    const int TH = Cout >= 32 ? 4 : 8;
+    // resident blocks only (register-bound: 3 per CU for Cout = 8, 2 for Cout >= 16): every block ends with a full weight-gradient partial
+    // (5-37 KB) that the reduce kernel reads back
+    return persistent_grid((long)N * ((w + 15) / 16) * ((h + TH - 1) / TH), Cout >= 16 ? 2 : 3);
+}
+
+// ----------------------------------------------------------------------------------------------
+// C ABI
+// ----------------------------------------------------------------------------------------------
+extern "C" {
+
+// Sum of ghat and ghat*zhat over all pixels (BatchNorm2d backward reductions).  gsum [2][C] double, ACCUMULATED (caller zeroes).
+int ocrs_bn_bwd_reduce(const void* g1, const void* g2, int pooled, const void* z, const float* bn, const float* saved, double* gsum, int C,
+                       int N, int H, int W, int dtype, hipStream_t st) {
+    OCRS_CHECK_ARG(g1 && z && bn && saved && gsum && C % 8 == 0 && C <= 256);
+    const long P = (long)N * H * W;
+    // every block ends with 2C fp64 atomics onto the same addresses: at the deep levels (tens of thousands of pixels) give each thread
+    // at least 8 items instead of launching 2048 nearly idle blocks (those launches were 60 us of pure flush)
+    long gl = (P * (C / 8) + 256 * 8 - 1) / (256 * 8);
+    const int bpc = 2;  // blocks per CU: every block ends in 2 C same-address fp64 atomics (~11 ns each, serial per address: 73 -> 54 us at level 1)
+    const int grid = (int)(gl < 8 ? 8 : (gl > kNumCU * bpc ? kNumCU * bpc : gl));
+    const size_t smem = (2 * C + 256 * 16) * sizeof(float);
+    if (dtype == 1) {
+        GradSrc<bf16> gs{(const bf16*)g1, (const bf16*)g2, pooled};
+        OCRS_LAUNCH_T(k_bn_bwd_reduce<bf16>, dim3(grid), dim3(256), smem, st, gs, (const bf16*)z, bn, saved, gsum, C, H, W, P);
+    } else {
+        GradSrc<float> gs{(const float*)g1, (const float*)g2, pooled};
+        OCRS_LAUNCH_T(k_bn_bwd_reduce<float>, dim3(grid), dim3(256), smem, st, gs, (const float*)z, bn, saved, gsum, C, H, W, P);
+    }
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+int ocrs_bn_bwd_finalize(const double* gsum, long count, int C, const float* gamma, const float* saved, float* coef, float* dgamma,
+                         float* dbeta, hipStream_t st) {
+    OCRS_CHECK_ARG(gsum && gamma && saved && coef && dgamma && dbeta && C > 0 && count > 0);
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, st, gsum, count, C, gamma, saved, coef, dgamma, dbeta);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+// Pointwise-conv backward of a DepthwiseConv block: du = Wpw^T dz (written, [P][Cin]); dwpw += u^T dz (accumulated, master layout
+// [Cout][Cin]); dz is formed on the fly from (g1 [+g2], z, bn, coef), u is recomputed from the block input.
+// wpk_d = ocrs_pack_frags(mode 0, K=Cout, M=Cin) of W^T.
 // ws: workspace of ocrs_pw_bwd_ws_floats() floats (deterministic two-stage weight-gradient reduction) or null (float atomics).
 long ocrs_pw_bwd_ws_floats(int Cin, int Cout, int N, int H, int W) {
-    if (det_pw2_supported(Cin, Cout, 1)) {  // (dtype is not known here: cover both kernels)
-        const long a = det_pw2_ws_floats(Cin, Cout, N, H, W);
-#define X(CI, CO) \
-    if (Cin == CI && Cout == CO) { const long b = (long)pw_bwd_gx<CI, CO>(N, H, W) * CI * CO; return a > b ? a : b; }
-        PW_BWD_COMBOS(X)
-#undef X
-        return a;
+    // (neither the dtype nor the split of a concat is known here: the largest need of the kernels either dtype, or a 32 | 32 concat, could take)
+    const int routes[3] = {pw_bwd_route(Cin, 0, Cout, 1), Cin == 64 ? pw_bwd_route(32, 32, Cout, 1) : 0, pw_bwd_route(Cin, 0, Cout, 0)};
+    long m = 0;
+    for (const int r : routes) {
+        const long v = pw_bwd_route_ws(r, Cin, Cout, N, H, W);
+        m = v > m ? v : m;
     }
-    long half = (Cin == 64 && det_pw2_supported(32, Cout, 1)) ? det_pw2_ws_floats(32, Cout, N, H, W) : 0;  // two-launch split (32 | 32)
-    if (det_pwb_supported(Cin, Cout, 1)) {
-        const long c = (long)det_pwb_gx(Cin, Cout, N, H, W, 0) * Cin * Cout;  // (the not-pooled grid is the larger one)
-        half = c > half ? c : half;
-    }
-#define X(CI, CO) \
-    if (Cin == CI && Cout == CO) { const long b = (long)pw_bwd_gx<CI, CO>(N, H, W) * CI * CO; return b > half ? b : half; }
-    PW_BWD_COMBOS(X)
-#undef X
-    return half;
+    return m;
 }
 int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2, int pooled,
                 const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N, int H, int W,
@@ -1564,9 +1358,12 @@ int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
     OCRS_CHECK_ARG((Cb == 0) == (xb == nullptr));
     const int Cin = Ca + Cb;
     OCRS_CHECK_ARG((long)N * H * W < (1L << 31));
-    if (det_pw2_supported(Cin, Cout, dtype))
+    switch (pw_bwd_route(Ca, Cb, Cout, dtype)) {
+    case 1:  // deep levels, up to 64 input channels: a whole tile in three barriers (det_pwb.hip)
+        return det_pwb_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, nullptr, st);
+    case 2:
         return det_pw2_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, Cin, Cin, st);
-    if (pw2_split_ok(Ca, Cb, Cout, dtype)) {
+    case 3: {
         // cat(32 | 32) -> Cout: z = Wpw[:, :32] u_a + Wpw[:, 32:] u_b, so du and dWpw separate by source; dz is the same for both.  Two launches of the
         // tuned two-pixel kernel (each re-reads g and z: 512 instead of 384 B per pixel) beat the generic 64-channel path (392 -> ~270 us at
         // level 2).  Per half: depthwise weights [32][9], packed W^T fragments (M tiles 2h, 2h+1), du / dWpw columns 32h.., row strides 64.
@@ -1578,14 +1375,14 @@ int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
         return det_pw2_launch(xb, nullptr, 32, 0, trb, nullptr, wdw + 32 * 9, g1, g2, pooled, z, bn, coef, wp + half_frag_bytes,
                               static_cast<bf16*>(du) + 32, dwpw + 32, ws, Cout, N, H, W, 64, 64, st);
     }
-    if (det_pwb_supported(Cin, Cout, dtype))  // deep levels, up to 64 input channels: a whole tile in three barriers (det_pwb.hip)
-        return det_pwb_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, nullptr, st);
+    case 4:
 #define X(CI, CO)                                                                                                                         \
     if (Cin == CI && Cout == CO)                                                                                                          \
         return dtype == 1 ? launch_pw_bwd<bf16, CI, CO>(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, N, H, W, st) \
                           : launch_pw_bwd<float, CI, CO>(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, N, H, W, st);
-    PW_BWD_COMBOS(X)
+        PW_BWD_COMBOS(X)
 #undef X
+    }
     return OCRS_ERR_ARG;
 }
 
@@ -1596,8 +1393,7 @@ int ocrs_pw_bwd_fin(const void* xa, const void* xb, int Ca, int Cb, const float*
                     int pooled, const void* z, const float* bn, float* coef, const double* gsum, const float* gamma, const float* saved, float* dgamma,
                     float* dbeta, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N, int H, int W, int dtype, hipStream_t st) {
     OCRS_CHECK_ARG(coef && gsum && gamma && saved && dgamma && dbeta && xa && tra && wdw && g1 && z && bn && wpk_d && du && dwpw);
-    const int Cin = Ca + Cb;
-    if (det_pwb_supported(Cin, Cout, dtype) && ws) {
+    if (ws && pw_bwd_route(Ca, Cb, Cout, dtype) == 1) {
         const BnFin fin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W};
         return det_pwb_launch(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, nullptr, wpk_d, du, dwpw, ws, Cout, N, H, W, &fin, st);
     }
@@ -1606,30 +1402,10 @@ int ocrs_pw_bwd_fin(const void* xa, const void* xb, int Ca, int Cb, const float*
     return ocrs_pw_bwd(xa, xb, Ca, Cb, tra, trb, wdw, g1, g2, pooled, z, bn, coef, wpk_d, du, dwpw, ws, Cout, N, H, W, dtype, st);
 }
 
-// The kernel ocrs_pw_bwd_fin runs for a block shape when it is given a workspace (the dispatch above and in ocrs_pw_bwd, restated for callers
-// that must know what they exercised): 1 = k_pwb (det_pwb.hip), 2 = k_pw_bwd2 (det_pw2.hip), 3 = k_pw_bwd2 once per source of a 32 | 32 concat,
-// 4 = the generic k_pw_bwd, 0 = none (OCRS_ERR_ARG).
-long ocrs_pw_bwd_kernel(int Ca, int Cb, int Cout, int dtype) {
-    const int Cin = Ca + Cb;
-    if (det_pwb_supported(Cin, Cout, dtype)) return 1;
-    if (det_pw2_supported(Cin, Cout, dtype)) return 2;
-    if (pw2_split_ok(Ca, Cb, Cout, dtype)) return 3;
-#define X(CI, CO) \
-    if (Cin == CI && Cout == CO) return 4;
-    PW_BWD_COMBOS(X)
-#undef X
-    return 0;
-}
+// The kernel ocrs_pw_bwd_fin runs for a block shape when it is given a workspace, for callers that must know what they exercised: pw_bwd_route's value.
+long ocrs_pw_bwd_kernel(int Ca, int Cb, int Cout, int dtype) { return pw_bwd_route(Ca, Cb, Cout, dtype); }
 
 // Depthwise-conv backward: gxa/gxb (either may be null) receive dL/dx~ split at channel Ca; dwdw accumulated in master layout [C][1][3][3].
-static void dw_bwd_grid(int C, int N, int H, int W, int& gx, int& gy, int& cg) {
-    cg = C / 8 < 4 ? C / 8 : 4;  // channel groups (of 8) per block: 4 -> 8x4-pixel tiles, 2 -> 8x8, 1 -> 8x16
-    gy = C / (cg * 8);
-    const Tiling2 tg = make_tiling2(N, H, W, 32 / cg, 8);
-    // 3 blocks per CU are resident (k_dw_bwd's launch bounds): a grid of exactly that many blocks (all y-slabs together) has no partial last
-    // round -- with 8 per CU the 2048 blocks ran as 2.67 rounds of 768
-    gx = persistent_grid(tg.ntiles, 3 / gy > 0 ? 3 / gy : 1);
-}
 // ws: ocrs_dw_bwd_ws_floats() floats (per-block partials of dwdw, summed by a second kernel) or null (float atomics).
 long ocrs_dw_bwd_ws_floats(int C, int N, int H, int W) {
     int gx, gy, cg;
@@ -1689,9 +1465,6 @@ int ocrs_dw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
     return OCRS_OK;
 }
 
-extern "C" long det_c1v2_supported(int N, int H, int W);  // det_c1.hip
-extern "C" int det_c1v2_bwd_launch(const float* img, const float* wdw, const float* wpw, const void* g, const void* z, const float* bn, const float* coef,
-                                   double* acc64, int N, int H, int W, int dtype, hipStream_t st);
 // First block (1->8) backward.  acc64 [17] fp64 = dWpw [8] | dWdw [9], ACCUMULATED (caller-zeroed; the caller adds it to the fp32 gradients: fp64
 // accumulation of the per-block fp32 partials is exact, hence order-independent -- float atomics were not).  The input image gets no gradient.
 int ocrs_dwpw_c1_bwd(const float* img, const float* wdw, const float* wpw, const void* g1, const void* g2, int pooled, const void* z,
@@ -1717,21 +1490,6 @@ int ocrs_dwpw_c1_bwd(const float* img, const float* wdw, const float* wpw, const
 
 // ConvTranspose2d backward.  g [N][H][W][Cout] = gradient of the (cropped) output; dx [N][h][w][Cup] written;
 // dW [Cup][Cout][3][3] and dbias [Cout] accumulated; ws = workspace of ocrs_convt_bwd_ws_floats() floats (or null: float atomics).  wpk_d = ocrs_pack_frags(mode 0, K=9*Cout, M=Cup, K2=Cout, s1=1, s2=9, sm=9*Cout).
-extern "C" long ocrs_wgrad_gather_ws_floats(int CA, int CB, int ntaps, long P, int dtype);
-static bool convt_wgrad_tr_ok(int Cup, int Cout, int dtype) {
-    return dtype == 1 && ((Cup == 16 && Cout == 8) || (Cup == 32 && Cout == 16) || (Cup == 32 && Cout == 32));
-}
-static int convt_wgrad_tr_grid(int Cout, int N, int h, int w) {
-    const int TH = Cout >= 32 ? 4 : 8;
-    // resident blocks only (register-bound: 3 per CU for Cout = 8, 2 for Cout >= 16): every block ends with a full weight-gradient partial
-    // (5-37 KB) that the reduce kernel reads back
-    return persistent_grid((long)N * ((w + 15) / 16) * ((h + TH - 1) / TH), Cout >= 16 ? 2 : 3);
-}
-// det_rs32.hip: the fp32 weight / bias gradient of the wide levels as row-streaming waves (round 6)
-long det_rs32_ctw_supported(int Cup, int Cout, int dtype);
-long det_rs32_ctw_ws_floats(int Cup, int Cout, int N, int h, int w, int dtype);
-int det_rs32_ctw_launch(const float* x, const float* tr, const float* g, float* dW, float* dbias, float* ws, int Cup, int Cout, int N, int h, int w, int H,
-                        int W, hipStream_t st);
 long ocrs_convt_bwd_ws_floats(int Cup, int Cout, int N, int h, int w, int dtype) {
     const long a = ocrs_wgrad_gather_ws_floats(Cup, Cout, 9, (long)N * h * w, dtype);
     const long b = convt_wgrad_tr_ok(Cup, Cout, dtype) ? (long)convt_wgrad_tr_grid(Cout, N, h, w) * (Cup * ((9 * Cout + 15) / 16 * 16) + Cout + 2 * Cup) : 0;
@@ -1742,18 +1500,11 @@ long ocrs_convt_bwd_ws_floats(int Cup, int Cout, int N, int h, int w, int dtype)
 // 1 if ocrs_convt_bwd can also produce the BatchNorm-backward sums of the block that produced x (saved / gsum arguments)
 // (not for (32, 16): with the sums that instantiation needs 208 + 80 registers -> one block per CU, 122 -> 225 us; its block keeps the
 // 86-us ocrs_bn_bwd_reduce pass)
-long det_ctd_supported(int Cup, int Cout, int dtype);  // det_ctd.hip
 long ocrs_convt_bwd_stats_supported(int Cup, int Cout, int dtype) {
     if (det_ctd_supported(Cup, Cout, dtype)) return 1;  // the deep-level input-gradient kernel also produces the sums (round 5)
     return convt_wgrad_tr_ok(Cup, Cout, dtype) && !(Cup == 32 && Cout == 16) ? 1 : 0;
 }
 
-// saved / gsum (nullable, need ws and ocrs_convt_bwd_stats_supported): x is the raw output of a block consumed ONLY by this ConvTranspose;
-// its BatchNorm-backward sums [sum ghat | sum ghat*zhat] ([2][Cup] fp64, ACCUMULATED) come from this pass instead of ocrs_bn_bwd_reduce.
-int ocrs_convt_bwd_parts(const void* x, const float* tr, const void* g, const void* wpk_d, void* dx, float* dW, float* dbias, double* dbias64, float* ws,
-                         const float* saved, double* gsum, int Cup, int Cout, int N, int h, int w, int H, int W, int parts, int dtype, hipStream_t st);
-int det_ctd_launch(const void* g, const void* wpk, void* dx, int Cup, int Cout, int N, int h, int w, int H, int W, hipStream_t st, const void* x,
-                   const float* tr, const float* saved, double* gsum);
 // 1 if ocrs_convt_bwd_parts can run the input gradient and the weight / bias gradients of this shape as separate calls (the generic deep-level path)
 long ocrs_convt_bwd_splittable(int Cup, int Cout, int dtype) { return convt_wgrad_tr_ok(Cup, Cout, dtype) ? 0 : 1; }
 
@@ -1762,6 +1513,8 @@ int ocrs_convt_bwd(const void* x, const float* tr, const void* g, const void* wp
     return ocrs_convt_bwd_parts(x, tr, g, wpk_d, dx, dW, dbias, dbias64, ws, saved, gsum, Cup, Cout, N, h, w, H, W, 3, dtype, st);
 }
 
+// saved / gsum (nullable, need ws and ocrs_convt_bwd_stats_supported): x is the raw output of a block consumed ONLY by this ConvTranspose;
+// its BatchNorm-backward sums [sum ghat | sum ghat*zhat] ([2][Cup] fp64, ACCUMULATED) come from this pass instead of ocrs_bn_bwd_reduce.
 // parts: bit 0 = input gradient dx, bit 1 = weight + bias gradients.  Separate calls only where ocrs_convt_bwd_splittable(): the weight-gradient
 // half is off the backward's critical path (nothing downstream reads it), so the caller may put it on another stream, where it overlaps the
 // latency-bound deep-level kernels that follow.  The tiled path (levels 0-2) computes everything from one staged tile and needs parts == 3.
@@ -1835,81 +1588,12 @@ int ocrs_convt_bwd_parts(const void* x, const float* tr, const void* g, const vo
     const long Pout = (long)N * H * W;
     // every block ends in Cout same-address global atomics (~15 ns each, serialised): 2048 blocks cost 30 us of atomics on a tensor that
     // streams in 10 us -> at most 2 blocks per CU, each thread keeping 4 loads in flight
-    int gs = cg_grid((Pout * (Cout / 8) + 3) / 4);
+    int gs = ew_grid((Pout * (Cout / 8) + 3) / 4);
     if (gs > 2 * kNumCU) gs = 2 * kNumCU;
     if (dtype == 1)
         hipLaunchKernelGGL(k_channel_sum<bf16>, dim3(gs), dim3(256), (Cout + 256 * 8) * sizeof(float), st, (const bf16*)g, dbias64, Cout, Pout);
     else
         hipLaunchKernelGGL(k_channel_sum<float>, dim3(gs), dim3(256), (Cout + 256 * 8) * sizeof(float), st, (const float*)g, dbias64, Cout, Pout);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-
-// Head backward: gy [P][8] written (dtype T); acc64 [9] fp64 = dw [8] | db, ACCUMULATED (caller-zeroed, caller adds it to the fp32 gradients).  saved / gsum (nullable): also accumulate the BatchNorm-backward
-// sums [2][8] (fp64, caller-zeroed) of the block that produced z (saved = its [mean | rstd]) -- replaces that block's ocrs_bn_bwd_reduce.
-static int head_bwd_impl(const void* z, const float* tr, const float* w, const float* pred, const float* gpred, void* gy, float* gl, double* acc64,
-                         const float* saved, double* gsum, long P, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(z && tr && w && pred && gpred && (gy || gl) && acc64 && P > 0 && (!gsum || saved));
-    int grid = ew_grid(P);
-    if (grid > 1024) grid = 1024;  // streaming kernel ending in same-address atomics: 4 blocks per CU are plenty
-    if (dtype == 1)
-        hipLaunchKernelGGL(k_head_bwd<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)z, tr, w, pred, gpred, (bf16*)gy, acc64, saved, gsum, P, gl);
-    else
-        hipLaunchKernelGGL(k_head_bwd<float>, dim3(grid), dim3(256), 0, st, (const float*)z, tr, w, pred, gpred, (float*)gy, acc64, saved, gsum, P, gl);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-int ocrs_head_bwd(const void* z, const float* tr, const float* w, const float* pred, const float* gpred, void* gy, double* acc64,
-                  const float* saved, double* gsum, long P, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(gy);
-    return head_bwd_impl(z, tr, w, pred, gpred, gy, nullptr, acc64, saved, gsum, P, dtype, st);
-}
-// ocrs_head_bwd that writes gl [P] fp32 = dL/dlogit instead of the 8-channel gradient gy: for ocrs_mm_bwd_fin_head, which forms gy on the fly
-int ocrs_head_bwd_gl(const void* z, const float* tr, const float* w, const float* pred, const float* gpred, float* gl, double* acc64,
-                     const float* saved, double* gsum, long P, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(gl);
-    return head_bwd_impl(z, tr, w, pred, gpred, nullptr, gl, acc64, saved, gsum, P, dtype, st);
-}
-// ocrs_balanced_bce_bwd + ocrs_head_bwd_gl in one pass: dL/dpred is formed on the fly from the loss forward's saved tensors (pred, target, lpx, cls,
-// state: ocrs_balanced_bce_fwd) and gout [1] (the upstream gradient of the scalar loss) -- reference: the autograd of train_detection.py:225-263
-// followed by models.py:143's 1x1 conv + sigmoid backward.  P % 4 == 0, saved / gsum required.
-int ocrs_head_bwd_loss(const void* z, const float* tr, const float* w, const float* pred, const float* target, const float* lpx, const unsigned char* cls,
-                       const void* state, const float* gout, float* gl, double* acc64, const float* saved, double* gsum, long P, int dtype,
-                       hipStream_t st) {
-    OCRS_CHECK_ARG(z && tr && w && pred && target && lpx && cls && state && gout && gl && acc64 && saved && gsum && P > 0 && P % 4 == 0);
-    int grid = ew_grid(P / 4);  // (ew_grid caps at 8 blocks per CU)
-    if (dtype == 1)
-        hipLaunchKernelGGL(k_head_bwd_loss<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)z, tr, w, pred, target, lpx, cls, (const LossState*)state,
-                           gout, acc64, saved, gsum, P, gl);
-    else
-        hipLaunchKernelGGL(k_head_bwd_loss<float>, dim3(grid), dim3(256), 0, st, (const float*)z, tr, w, pred, target, lpx, cls,
-                           (const LossState*)state, gout, acc64, saved, gsum, P, gl);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-
-// Deferred second stage (see the queue above).  scratch: ndoubles zeroed fp64 values the block-backward launches carve their last-workgroup
-// finalisation state from (16 Cin + 2 each; left zeroed), valid -- like every workspace `ws` passed meanwhile -- until ocrs_bwd_defer_flush, which
-// launches the queued weight-gradient reductions as one kernel on `st` (the stream of the launches that produced the partials) and ends the mode.
-int ocrs_bwd_defer_begin(double* scratch, long ndoubles) {
-    DeferState& D = defer_state();
-    OCRS_CHECK_ARG(!D.on && (scratch || ndoubles == 0) && ndoubles >= 0);
-    D.on = true;
-    D.scratch = scratch;
-    D.cap = ndoubles;
-    D.used = 0;
-    D.nblocks = 0;
-    D.jobs.njobs = 0;
-    D.ws_used = 0;
-    return OCRS_OK;
-}
-int ocrs_bwd_defer_flush(hipStream_t st) {
-    DeferState& D = defer_state();
-    const bool was = D.on;
-    D.on = false;
-    if (!was || D.jobs.njobs == 0) return OCRS_OK;
-    hipLaunchKernelGGL(k_reduce_multi, dim3(D.nblocks), dim3(256), 0, st, D.jobs);
-    D.jobs.njobs = 0;
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

@@ -1,5 +1,5 @@
 // First block of the detection net (DepthwiseConv 1 -> 8 on the greyscale image, ocrs_models/models.py:115 in_conv.seq.0), forward and backward,
-// in the "wave = 64 columns x 2 rows" form (gfx950; W % 64 == 0, H % 2 == 0; other shapes keep k_dwpw_c1_fwd / k_c1_bwd).
+// in the "wave = 64 columns x 2 rows" form (gfx950; W % 64 == 0, H % 2 == 0; other shapes keep the per-pixel k_dwpw_c1_fwd below / k_c1_bwd in det_bwd.hip).
 //
 // The per-pixel kernels issue 9 image loads (+ up to 6 sixteen-byte loads in the backward, four of them redundant re-reads of the generic
 // gradient-source form) for every 16 / 32 useful bytes: 168 VGPRs, 3 waves per SIMD, 3.2 TB/s.  Here a wave owns 64 consecutive columns of a
@@ -7,7 +7,7 @@
 // lanes with DPP wave shifts (the two columns outside the segment come from ONE extra load by lanes 0..7 and are handed to lanes 0 / 63 as
 // the shifts' out-of-range value), and streams the two pixels' z / gradient vectors with fully coalesced 16-byte loads: 4.5 instead of 15
 // load instructions per pixel, half the registers, the same per-pixel arithmetic (same tap order, same roundings) as the per-pixel kernels.
-#include "det_common.h"
+#include "det_internal.h"
 
 namespace {
 constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138;  // result[i] = src[i + 1] / src[i - 1]; lanes without a source keep `old`
@@ -248,8 +248,67 @@ __global__ __launch_bounds__(256) void k_c1_bwd2(const float* __restrict__ img, 
     if (threadIdx.x < 17) atomicAdd(&acc64[threadIdx.x], (double)tot);
 }
 
-extern "C" {
+// ----------------------------------------------------------------------------------------------
+// first block of the net: 1 -> 8 channels (models.py:115 in_conv.seq.0), input = the greyscale image itself.
+template <class T>
+__global__ __launch_bounds__(256) void k_dwpw_c1_fwd(const float* __restrict__ img, const float* __restrict__ wdw /*[9]*/,
+                                                     const float* __restrict__ wpw /*[8]*/, T* __restrict__ z, double* __restrict__ gstat,
+                                                     int H, int W, long P) {
+    __shared__ float s_slots[4 * 16];
+    float wd[9], wp[8];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) wd[i] = wdw[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) wp[i] = wpw[i];
+    float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // software pipeline over the grid-stride loop: the neighbourhood of iteration i+1 is in flight while iteration i is computed and
+    // stored; two buffers, loop unrolled by two (a buffer that a load is still filling cannot be copied without waiting for it)
+    const long stride = (long)gridDim.x * 256;
+    PixIter pit((long)blockIdx.x * 256 + threadIdx.x, stride, H, W);
+    long p = (long)blockIdx.x * 256 + threadIdx.x;
+    auto compute = [&](const Nb9& nbr, long pp) {
+        float nb[9];
+        nb9_finish(nbr, nb);
+        float u = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) u = fmaf(wd[k], nb[k], u);
+        u = Elem<T>::round(u);
+        float o[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            o[i] = wp[i] * u;
+            const float q = Elem<T>::round(o[i]);
+            s1[i] += q;
+            s2[i] = fmaf(q, q, s2[i]);
+        }
+        store8(z + pp * 8, o);
+    };
+    Nb9 bufA, bufB;
+    nb9_issue(bufA, img, pit.cur(), H, W, p < P);
+    while (p < P) {
+        pit.next();
+        nb9_issue(bufB, img, pit.cur(), H, W, p + stride < P);
+        compute(bufA, p);
+        p += stride;
+        if (p >= P) break;
+        pit.next();
+        nb9_issue(bufA, img, pit.cur(), H, W, p + stride < P);
+        compute(bufB, p);
+        p += stride;
+    }
+    float all[16];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        all[i] = s1[i];
+        all[8 + i] = s2[i];
+    }
+    const float tot = block_sum_det<16>(all, s_slots);  // fixed-order block sum; fp64 across blocks (exact for comparable fp32 partials)
+    if (threadIdx.x < 16) atomicAdd(&gstat[threadIdx.x], (double)tot);
+}
 
+// ----------------------------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------------------------
 long det_c1v2_supported(int N, int H, int W) {
     return N > 0 && H >= 2 && H % 2 == 0 && W >= 64 && W % 64 == 0 && (long)N * (H / 2) * (W / 64) < (1L << 30);
 }
@@ -260,7 +319,7 @@ static int c1v2_grid(int N, int H, int W, int bpc) {
     return (int)(g < cap ? g : cap);
 }
 
-int det_c1v2_fwd_launch(const float* img, const float* wdw, const float* wpw, void* z, double* gstat, int N, int H, int W, int dtype, hipStream_t st,
+static int c1v2_fwd_launch(const float* img, const float* wdw, const float* wpw, void* z, double* gstat, int N, int H, int W, int dtype, hipStream_t st,
                         void* uplane, double* fsum) {
     const int grid = c1v2_grid(N, H, W, 8);
     if (dtype == 1 && fsum)
@@ -272,11 +331,6 @@ int det_c1v2_fwd_launch(const float* img, const float* wdw, const float* wpw, vo
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-int det_c1_bwd_fin_launch(const double* c1acc, const double* fsum, const float* coef, const float* wexp, double* acc64, hipStream_t st) {
-    hipLaunchKernelGGL(k_c1_bwd_fin, dim3(1), dim3(64), 0, st, c1acc, fsum, coef, wexp, acc64);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
 
 int det_c1v2_bwd_launch(const float* img, const float* wdw, const float* wpw, const void* g, const void* z, const float* bn, const float* coef,
                         double* acc64, int N, int H, int W, int dtype, hipStream_t st) {
@@ -285,6 +339,50 @@ int det_c1v2_bwd_launch(const float* img, const float* wdw, const float* wpw, co
         hipLaunchKernelGGL((k_c1_bwd2<bf16, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const bf16*)g, (const bf16*)z, bn, coef, acc64, N, H, W);
     else
         hipLaunchKernelGGL((k_c1_bwd2<float, true>), dim3(grid), dim3(256), 0, st, img, wdw, wpw, (const float*)g, (const float*)z, bn, coef, acc64, N, H, W);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// C ABI
+// ----------------------------------------------------------------------------------------------
+extern "C" {
+
+// First block (1 -> 8): img fp32 (N,1,H,W); wdw [9]; wpw [8]; z [P][8]; gstat [2][8] accumulated (caller zeroes).
+int ocrs_dwpw_c1_fwd(const float* img, const float* wdw, const float* wpw, void* z, double* gstat, int N, int H, int W, int dtype,
+                     hipStream_t st) {
+    OCRS_CHECK_ARG(img && wdw && wpw && z && gstat);
+    if (det_c1v2_supported(N, H, W)) return c1v2_fwd_launch(img, wdw, wpw, z, gstat, N, H, W, dtype, st, nullptr, nullptr);
+    const long P = (long)N * H * W;
+    const int grid = ew_grid(P);
+    if (dtype == 1)
+        hipLaunchKernelGGL(k_dwpw_c1_fwd<bf16>, dim3(grid), dim3(256), 0, st, img, wdw, wpw, (bf16*)z, gstat, H, W, P);
+    else
+        hipLaunchKernelGGL(k_dwpw_c1_fwd<float>, dim3(grid), dim3(256), 0, st, img, wdw, wpw, (float*)z, gstat, H, W, P);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
+}
+
+// The same, additionally writing the block output's rank-one generator: uplane [N][H][W] bf16 = the rounded depthwise output u, z[p][c] = round(Wpw[c] * u[p])
+// (see k_c1_fwd2).  ocrs_dwpw_c1_u_supported: 1 if this shape / dtype has the form (bf16, the 64-column x 2-row kernel).
+long ocrs_dwpw_c1_u_supported(int N, int H, int W, int dtype) { return dtype == 1 && det_c1v2_supported(N, H, W) ? 1 : 0; }
+int ocrs_dwpw_c1_fwd_u(const float* img, const float* wdw, const float* wpw, void* z, void* uplane, double* gstat, int N, int H, int W, int dtype,
+                       hipStream_t st) {
+    OCRS_CHECK_ARG(img && wdw && wpw && uplane && gstat && ocrs_dwpw_c1_u_supported(N, H, W, dtype));  // (z may be null: only the u plane is written)
+    return c1v2_fwd_launch(img, wdw, wpw, z, gstat, N, H, W, dtype, st, uplane, nullptr);
+}
+// ocrs_dwpw_c1_fwd_u that also accumulates the forward-only sums of the fused first-block backward (ocrs_mm_bwd_fin_xu_c1 + ocrs_c1_bwd_fin):
+// fsum [20] fp64 (zeroed by the caller) += sum u | sum u^2 | sum u img(tap) [9] | sum img(tap) [9]
+int ocrs_dwpw_c1_fwd_us(const float* img, const float* wdw, const float* wpw, void* z, void* uplane, double* gstat, double* fsum, int N, int H, int W, int dtype,
+                        hipStream_t st) {
+    OCRS_CHECK_ARG(img && wdw && wpw && uplane && gstat && fsum && dtype == 1 && ocrs_dwpw_c1_u_supported(N, H, W, dtype));
+    return c1v2_fwd_launch(img, wdw, wpw, z, gstat, N, H, W, dtype, st, uplane, fsum);
+}
+// The first block's weight gradient from the sums of ocrs_dwpw_c1_fwd_us (fsum) and ocrs_mm_bwd_fin_xu_c1 (c1acc [8][32] fp64) and the block's
+// BatchNorm-backward coefficients coef [3][8] (ocrs_bn_bwd_finalize): acc64 [17] += dWpw [8] | dWdw [9], as ocrs_dwpw_c1_bwd.
+int ocrs_c1_bwd_fin(const double* c1acc, const double* fsum, const float* coef, const float* wexp, double* acc64, hipStream_t st) {
+    OCRS_CHECK_ARG(c1acc && fsum && coef && wexp && acc64);
+    hipLaunchKernelGGL(k_c1_bwd_fin, dim3(1), dim3(64), 0, st, c1acc, fsum, coef, wexp, acc64);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

@@ -563,7 +563,7 @@ __device__ __forceinline__ void bn_fin_coef(const BnFin& fin, int COUT, float* s
 // drains them (s_waitcnt vmcnt(0), not __threadfence: see bn_finalize_last_block) and takes a ticket; the workgroup that draws the last ticket
 // converts the totals exactly as the reduce kernel does, adds them to gsum_a / gsum_b and re-zeroes raw / counter (ready for a replay).  What is
 // left for the reduce kernel -- the weight gradients, which nothing in the backward reads -- is queued and runs as ONE launch at the end of the
-// backward (ocrs_bwd_defer_begin / ocrs_bwd_defer_flush in det_bwd.hip).
+// backward (ocrs_bwd_defer_begin / ocrs_bwd_defer_flush in det_defer.hip).
 struct BwdLast {
     double* raw;        // [BWD_LAST_SLOTS][2][CIN] fp64, zeroed (null: off -- the launcher runs the reduce kernel in line)
     unsigned* counter;  // one zeroed word
@@ -611,12 +611,7 @@ __device__ __forceinline__ void bwd_last_finish(const BwdLast& bl, int CIN, cons
     }
     if (tid == 0) __hip_atomic_store(bl.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// host side (det_bwd.hip): scratch for one launch (null outside ocrs_bwd_defer_begin .. _flush or when it is used up), and the queue of deferred
-// weight-gradient reductions: columns [0, n0) of ws[nb][nelem] += into d0[(e / cin0) * ldw0 + e % cin0], columns [n0, n0 + n1) into d1[e - n0]
-double* bwd_defer_scratch(int ndoubles);
-float* bwd_defer_ws(long nfloats);  // per-block-partial workspace for launches whose entry points take none (null: not deferring / used up)
-bool bwd_defer_reduce(const float* ws, int nb, int nelem, float* d0, int n0, int cin0, int ldw0, float* d1, int n1);
-void bwd_reduce_or_defer(const float* ws, int nb, int nelem, float* d0, int n0, int cin0, int ldw0, float* d1, int n1, hipStream_t st);  // queue, or one-job launch now
+// (host side: the scratch and the queue of deferred reductions are declared in det_internal.h and live in det_defer.hip)
 
 // ---- BatchNorm2d training statistics finalised by the LAST workgroup of the forward launch that produced them (one launch less per block)
 struct FwdFin {

@@ -4,7 +4,7 @@
 // exposed round trips and 72 barriers per tile at Cout = 128).  Here the (2*8+1) x (2*8+1) output-gradient pixels under an 8 x 8 tile of input
 // pixels are staged ONCE, all channels, in bf16 LDS; the K loop streams packed weight fragments from L2 one chunk ahead against gradient
 // fragments read at the tap's (stride-2) offset.
-#include "det_common.h"
+#include "det_internal.h"
 
 namespace {
 template <int CUP, int COUT>
@@ -153,8 +153,6 @@ __global__ __launch_bounds__(512) void k_ctd(const bf16* __restrict__ g, const v
     }
 }
 
-extern "C" {
-
 long det_ctd_supported(int Cup, int Cout, int dtype) {
     return dtype == 1 && ((Cup == 256 && Cout == 128) || (Cup == 128 && Cout == 64) || (Cup == 64 && Cout == 32));
 }
@@ -191,5 +189,3 @@ int det_ctd_launch(const void* g, const void* wpk, void* dx, int Cup, int Cout, 
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-
-}  // extern "C"

@@ -1,11 +1,11 @@
 // ConvTranspose2d(Cup -> Cout, k3, s2, bias) + crop, forward, at the DEEP U-Net levels (gfx950, bf16, Cup in {64, 128, 256}) -- same GEMM as
-// k_convt_fwd (det_fwd.hip: a GEMM "pixel" = an input-aligned position (i, j), i in [0, h], j in [0, w], producing the output quad
+// k_convt_fwd (det_convt.hip: a GEMM "pixel" = an input-aligned position (i, j), i in [0, h], j in [0, w], producing the output quad
 // (2i + py, 2j + px) from the four inputs x~[i - dy][j - dx]; K = (d, c) = 4 Cup, M = (q, o) = 4 Cout; reference ocrs_models/models.py:76-87),
 // restructured like det_dwf.hip: k_convt_fwd re-loads a 32-channel slice of the pixel operand from global memory for each of its 4 Cup / 32
 // K chunks (32 exposed round trips and 64 barriers per tile at Cup = 256: 110 us for a launch of 8.6 GFLOP).  Here the (8 + 1) x (8 + 1) input
 // pixels of an 8 x 8 tile of positions are staged ONCE, all channels, as x~ in bf16 LDS; the K loop then only streams packed weight fragments
 // from L2 (double-buffered in registers) against pixel fragments read at the neighbour's offset.  One barrier pair per tile.
-#include "det_common.h"
+#include "det_internal.h"
 
 namespace {
 template <int CUP, int COUT>
@@ -131,8 +131,6 @@ __global__ __launch_bounds__(512) void k_ctf(const bf16* __restrict__ x, const f
     }
 }
 
-extern "C" {
-
 long det_ctf_supported(int Cup, int Cout, int dtype) {
     return dtype == 1 && ((Cup == 256 && Cout == 128) || (Cup == 128 && Cout == 64) || (Cup == 64 && Cout == 32));
 }
@@ -161,5 +159,3 @@ int det_ctf_launch(const void* x, const float* tr, const void* wpk, const float*
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-
-}  // extern "C"

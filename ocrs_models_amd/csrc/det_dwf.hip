@@ -7,7 +7,7 @@
 //      weight fragments -- vector loads retire in order) and staged as x~ in bf16 LDS,
 //   B  u = dw3x3(x~) on the VALU for all channels -> uN [pixels][Cin] (bf16),
 //   C  z = Wpw u on MFMA (K = Cin from uN, packed weight fragments preloaded), store + per-channel sums in registers.
-#include "det_common.h"
+#include "det_internal.h"
 
 namespace {
 template <int CIN, int COUT>
@@ -208,8 +208,6 @@ __global__ __launch_bounds__(512) void k_dwf(Src2<bf16> x, const float* __restri
     bn_finalize_last_block(fin, gstat, COUT, tid, NT, reinterpret_cast<int*>(smem));  // (the tiles are dead; s_st lives behind them)
 }
 
-extern "C" {
-
 long det_dwf_supported(int Cin, int Cout, int dtype) {
     return dtype == 1 && (Cin == 32 || Cin == 64 || Cin == 128 || Cin == 256) && (Cout == 64 || Cout == 128 || Cout == 256) && Cin * 8 >= Cout;
 }
@@ -244,5 +242,3 @@ int det_dwf_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-
-}  // extern "C"

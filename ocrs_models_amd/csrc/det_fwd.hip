@@ -1,12 +1,10 @@
 // Detection U-Net forward kernels (gfx950).  Reference semantics: ocrs_models/models.py:7-143.
 //
 //  k_dwpw_fwd      fused [producer BN+ReLU on load] -> depthwise 3x3 -> pointwise 1x1 (MFMA) -> z + BN batch sums
-//  k_dwpw_c1_fwd   the 1->8 first block (VALU)
 //  k_bn_finalize   batch sums -> (scale, shift, lo) + saved mean/rstd + running-stat update
 //  k_maxpool_fwd   2x2 max-pool of relu(bn(z))
-//  k_convt_fwd     ConvTranspose2d k3 s2 (+bias, +crop) as a 4-pixel-gather MFMA GEMM
-//  k_head_fwd      1x1 conv 8->1 + bias + sigmoid
-#include "det_common.h"
+// The first block, the ConvTranspose2d forward and the head have their own files (det_c1 / det_convt / det_head.hip).
+#include "det_internal.h"
 
 // ----------------------------------------------------------------------------------------------
 // generic weight-fragment packer:  W[k][m]  ->  MFMA fragments [kc][mt][lane][8]
@@ -271,64 +269,6 @@ __global__ __launch_bounds__(256, (ONE && Elem<T>::is_bf16) ? 3 : (MT <= 4 ? 4 :
     }
 }
 
-// ----------------------------------------------------------------------------------------------
-// first block of the net: 1 -> 8 channels (models.py:115 in_conv.seq.0), input = the greyscale image itself.
-template <class T>
-__global__ __launch_bounds__(256) void k_dwpw_c1_fwd(const float* __restrict__ img, const float* __restrict__ wdw /*[9]*/,
-                                                     const float* __restrict__ wpw /*[8]*/, T* __restrict__ z, double* __restrict__ gstat,
-                                                     int H, int W, long P) {
-    __shared__ float s_slots[4 * 16];
-    float wd[9], wp[8];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) wd[i] = wdw[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) wp[i] = wpw[i];
-    float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // software pipeline over the grid-stride loop: the neighbourhood of iteration i+1 is in flight while iteration i is computed and
-    // stored; two buffers, loop unrolled by two (a buffer that a load is still filling cannot be copied without waiting for it)
-    const long stride = (long)gridDim.x * 256;
-    PixIter pit((long)blockIdx.x * 256 + threadIdx.x, stride, H, W);
-    long p = (long)blockIdx.x * 256 + threadIdx.x;
-    auto compute = [&](const Nb9& nbr, long pp) {
-        float nb[9];
-        nb9_finish(nbr, nb);
-        float u = 0.f;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) u = fmaf(wd[k], nb[k], u);
-        u = Elem<T>::round(u);
-        float o[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            o[i] = wp[i] * u;
-            const float q = Elem<T>::round(o[i]);
-            s1[i] += q;
-            s2[i] = fmaf(q, q, s2[i]);
-        }
-        store8(z + pp * 8, o);
-    };
-    Nb9 bufA, bufB;
-    nb9_issue(bufA, img, pit.cur(), H, W, p < P);
-    while (p < P) {
-        pit.next();
-        nb9_issue(bufB, img, pit.cur(), H, W, p + stride < P);
-        compute(bufA, p);
-        p += stride;
-        if (p >= P) break;
-        pit.next();
-        nb9_issue(bufA, img, pit.cur(), H, W, p + stride < P);
-        compute(bufB, p);
-        p += stride;
-    }
-    float all[16];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        all[i] = s1[i];
-        all[8 + i] = s2[i];
-    }
-    const float tot = block_sum_det<16>(all, s_slots);  // fixed-order block sum; fp64 across blocks (exact for comparable fp32 partials)
-    if (threadIdx.x < 16) atomicAdd(&gstat[threadIdx.x], (double)tot);
-}
-
 // BatchNorm2d training-mode statistics (biased var for normalisation, unbiased into running_var, eps 1e-5,
 // momentum 0.1)  ->  per-channel load transform + saved mean/rstd.
 __global__ void k_bn_finalize(const double* __restrict__ gstat, long count, int C, const float* __restrict__ gamma,
@@ -392,101 +332,57 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd(const T* __restrict__ z, co
     }
 }
 
-// ConvTranspose2d(Cup -> Cout, k3, s2, bias) + crop to (H, W)  (models.py:76-78, 82-87).
-// One GEMM "pixel" = an input-aligned position (i, j), i in [0, h], j in [0, w]; it produces the 2x2 output quad
-// (2i+py, 2j+px) from the four inputs x~[i-dy][j-dx]:   K = (d, c) = 4*Cup,  M = (q, o) = 4*Cout.
-// grid.y selects a block of MT*16 rows of M.
-template <class T, int MT>
-__global__ __launch_bounds__(256) void k_convt_fwd(const T* __restrict__ x, const float* __restrict__ tr, const void* __restrict__ wpk,
-                                                   const float* __restrict__ bias, T* __restrict__ out, int Cup, int Cout, int h, int w,
-                                                   int H, int W, int N, int MT_total) {
-    constexpr int TP = 64, PITCH = Mma<T>::LDS_PITCH;
-    __shared__ __attribute__((aligned(16))) T tile[TP * PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int pxl = tid >> 2, cg = tid & 3;
-    const int hp = h + 1, wp = w + 1;
-    const long P = (long)N * hp * wp;
-    const long ntiles = (P + TP - 1) / TP;
-    const int nkc = (4 * Cup) / 32;
-    const int mt0 = blockIdx.y * MT;
-    TileSched ts(ntiles);
-    for (long t = ts.first; t < ts.end; t += ts.step) {
-        const long p = t * TP + pxl;
-        const bool pv = p < P;
-        const PixIdx px = decode_pixel(pv ? p : 0, hp, wp);
-        f32x4 acc[MT];
-#pragma unroll
-        for (int b = 0; b < MT; ++b) acc[b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int kc = 0; kc < nkc; ++kc) {
-            const int k0 = kc * 32 + cg * 8;
-            const int d = k0 / Cup, c0 = k0 - d * Cup;
-            const int ii = px.h - (d >> 1), jj = px.w - (d & 1);
-            float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (pv && ii >= 0 && ii < h && jj >= 0 && jj < w) {
-                load8(x + (((long)px.n * h + ii) * w + jj) * Cup + c0, v);
-                apply_tr8(v, tr, Cup, c0);
-            }
-            if (kc) __syncthreads();
-            store8(tile + pxl * PITCH + cg * 8, v);
-            __syncthreads();
-            const typename Mma<T>::Frag pf = Mma<T>::load_p(tile, PITCH, wave * 16, lane, 32);
-#pragma unroll
-            for (int b = 0; b < MT; ++b) {
-                const typename Mma<T>::Frag wf = Mma<T>::load_w(wpk, (long)kc * MT_total + mt0 + b, lane);
-                acc[b] = Mma<T>::template mma<8>(wf, pf, acc[b]);
-            }
-        }
-        const long po = t * TP + wave * 16 + (lane & 15);
-        if (po < P) {
-            const PixIdx q = decode_pixel(po, hp, wp);
-#pragma unroll
-            for (int b = 0; b < MT; ++b) {
-                const int m0 = (mt0 + b) * 16 + (lane >> 4) * 4;
-                const int par = m0 / Cout, o0 = m0 - par * Cout;
-                const int Y = 2 * q.h + (par >> 1), X = 2 * q.w + (par & 1);
-                if (par < 4 && Y < H && X < W) {
-                    const f32x4 a = acc[b];
-                    store4(out + (((long)q.n * H + Y) * W + X) * Cout + o0, a[0] + bias[o0], a[1] + bias[o0 + 1], a[2] + bias[o0 + 2],
-                           a[3] + bias[o0 + 3]);
-                }
-            }
-        }
-        __syncthreads();
-    }
+// ----------------------------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------------------------
+template <class T, int CG, int MT, bool ONE>
+static int launch_dwpw_fwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* wpk, void* z,
+                           double* gstat, int COUT, int N, int H, int W, const float* gamma, void* pooled, hipStream_t st) {
+    using FT = FwdTile<CG, FwdPx<MT>::PX>;
+    constexpr int TP = FT::TP;
+    const int CIN = Ca + Cb;
+    Src2<T> x{(const T*)xa, (const T*)xb, Ca, Cb};
+    const Tiling2 tg = make_tiling2(N, H, W, FT::TW, FT::TH);
+    const size_t smem = ((TP * FwdPitch<T, CG>::V * sizeof(T) + 15) & ~15) +
+                        (HaloTile<FT::TW, FT::TH>::HP * CG * 8 + 12 * CIN + 4 * 2 * MT * 16) * sizeof(float);
+    // every block ends with 2*COUT same-address fp64 atomics (~15 ns each, serialised): at the middle levels (a few thousand tiles)
+    // two tiles per block halve that tail; below that parallelism matters more (measured: tiles-per-block sweep, profiles/README.md)
+    const int tpb = tg.ntiles >= 2048 ? 2 : 1;
+    // 4 blocks per CU are resident (registers <= 128, LDS 36 KB): a grid of exactly the resident blocks runs as ONE round (8 per CU = two rounds, each
+    // block with its own prologue and 2*COUT fp64 atomics at the end: 4.66 -> 4.52 ms per step over all forward launches)
+    const int grid = persistent_grid(tg.ntiles / tpb > 0 ? tg.ntiles / tpb : 1, 4);
+    if (pooled) {
+        if constexpr (FwdPx<MT>::PX == 2 && FT::TW >= 16)
+            hipLaunchKernelGGL((k_dwpw_fwd<T, CG, MT, ONE, true>), dim3(grid), dim3(256), smem, st, x, tra, trb, wdw, wpk, (T*)z, gstat, CIN, COUT, tg,
+                               gamma, (T*)pooled);
+        else
+            return OCRS_ERR_ARG;  // (ocrs_dwpw_fwd_pool_supported)
+    } else
+        hipLaunchKernelGGL((k_dwpw_fwd<T, CG, MT, ONE, false>), dim3(grid), dim3(256), smem, st, x, tra, trb, wdw, wpk, (T*)z, gstat, CIN, COUT, tg,
+                           gamma, (T*)pooled);
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
 }
 
-// out_conv: Conv2d(8 -> 1, 1x1, bias) + Sigmoid (models.py:125-129) on relu(bn(z)).  pred is fp32 (B,1,H,W).
 template <class T>
-__global__ __launch_bounds__(256) void k_head_fwd(const T* __restrict__ z, const float* __restrict__ tr, const float* __restrict__ w,
-                                                  const float* __restrict__ b, float* __restrict__ pred, long P) {
-    float wv[8], sc[8], sh[8], lo[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        wv[i] = w[i];
-        sc[i] = tr[i];
-        sh[i] = tr[8 + i];
-        lo[i] = tr[16 + i];
-    }
-    const float bias = b[0];
-    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
-        float v[8];
-        load8(z + p * 8, v);
-        float s = bias;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s = fmaf(wv[i], fmaxf(fmaf(v[i], sc[i], sh[i]), lo[i]), s);
-        pred[p] = 1.f / (1.f + __expf(-s));
-    }
+static int dispatch_dwpw_fwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* wpk, void* z,
+                             double* gstat, int COUT, int N, int H, int W, const float* gamma, void* pooled, hipStream_t st) {
+    const int CIN = Ca + Cb;
+    const int cg = CIN >= 32 ? 4 : CIN / 8;
+    const int mt = (COUT + 15) / 16;
+#define DWPW_CASE(CG_, MT_, ONE_) \
+    if (cg == CG_ && mt == MT_ && (CIN == CG_ * 8) == ONE_) \
+        return launch_dwpw_fwd<T, CG_, MT_, ONE_>(xa, xb, Ca, Cb, tra, trb, wdw, wpk, z, gstat, COUT, N, H, W, gamma, pooled, st);
+    DWPW_CASE(1, 1, true) DWPW_CASE(2, 1, true) DWPW_CASE(2, 2, true)
+    DWPW_CASE(4, 1, true) DWPW_CASE(4, 2, true) DWPW_CASE(4, 4, true)  // Cin == 32: pipelined single-chunk variants
+    DWPW_CASE(4, 1, false) DWPW_CASE(4, 2, false) DWPW_CASE(4, 4, false) DWPW_CASE(4, 8, false) DWPW_CASE(4, 16, false)
+#undef DWPW_CASE
+    return OCRS_ERR_ARG;
 }
 
 // ----------------------------------------------------------------------------------------------
 // C ABI
 // ----------------------------------------------------------------------------------------------
-static inline int ew_grid(long items) {
-    long g = (items + 255) / 256;
-    const long cap = (long)kNumCU * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 extern "C" {
 
 int ocrs_pack_frags(const float* src, int mode, int K, int M, int K2, long s1, long s2, long sm, void* out, int dtype, hipStream_t st) {
@@ -517,56 +413,6 @@ int ocrs_pack_frags_multi(const long long* table, int n, long max_frag_threads, 
 // number of bytes a packed fragment buffer needs
 long ocrs_pack_frags_bytes(int K, int M, int dtype) { return (long)((K + 31) / 32) * ((M + 15) / 16) * 64 * 8 * (dtype == 1 ? 2 : 4); }
 
-}  // extern "C" (templates need C++ linkage)
-template <class T, int CG, int MT, bool ONE>
-static int launch_dwpw_fwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* wpk, void* z,
-                           double* gstat, int COUT, int N, int H, int W, const float* gamma, void* pooled, hipStream_t st) {
-    using FT = FwdTile<CG, FwdPx<MT>::PX>;
-    constexpr int TP = FT::TP;
-    const int CIN = Ca + Cb;
-    Src2<T> x{(const T*)xa, (const T*)xb, Ca, Cb};
-    const Tiling2 tg = make_tiling2(N, H, W, FT::TW, FT::TH);
-    const size_t smem = ((TP * FwdPitch<T, CG>::V * sizeof(T) + 15) & ~15) +
-                        (HaloTile<FT::TW, FT::TH>::HP * CG * 8 + 12 * CIN + 4 * 2 * MT * 16) * sizeof(float);
-    // every block ends with 2*COUT same-address fp64 atomics (~15 ns each, serialised): at the middle levels (a few thousand tiles)
-    // two tiles per block halve that tail; below that parallelism matters more (measured: tiles-per-block sweep, profiles/README.md)
-    const int tpb = tg.ntiles >= 2048 ? 2 : 1;
-    // 4 blocks per CU are resident (registers <= 128, LDS 36 KB): a grid of exactly the resident blocks runs as ONE round (8 per CU = two rounds, each
-    // block with its own prologue and 2*COUT fp64 atomics at the end: 4.66 -> 4.52 ms per step over all forward launches)
-    const int grid = persistent_grid(tg.ntiles / tpb > 0 ? tg.ntiles / tpb : 1, 4);
-    if (pooled) {
-        if constexpr (FwdPx<MT>::PX == 2 && FT::TW >= 16)
-            hipLaunchKernelGGL((k_dwpw_fwd<T, CG, MT, ONE, true>), dim3(grid), dim3(256), smem, st, x, tra, trb, wdw, wpk, (T*)z, gstat, CIN, COUT, tg,
-                               gamma, (T*)pooled);
-        else
-            return OCRS_ERR_ARG;  // (ocrs_dwpw_fwd_pool_supported)
-    } else
-        hipLaunchKernelGGL((k_dwpw_fwd<T, CG, MT, ONE, false>), dim3(grid), dim3(256), smem, st, x, tra, trb, wdw, wpk, (T*)z, gstat, CIN, COUT, tg,
-                           gamma, (T*)pooled);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-extern "C" {
-
-}  // extern "C" (templates need C++ linkage)
-
-template <class T>
-static int dispatch_dwpw_fwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* wpk, void* z,
-                             double* gstat, int COUT, int N, int H, int W, const float* gamma, void* pooled, hipStream_t st) {
-    const int CIN = Ca + Cb;
-    const int cg = CIN >= 32 ? 4 : CIN / 8;
-    const int mt = (COUT + 15) / 16;
-#define DWPW_CASE(CG_, MT_, ONE_) \
-    if (cg == CG_ && mt == MT_ && (CIN == CG_ * 8) == ONE_) \
-        return launch_dwpw_fwd<T, CG_, MT_, ONE_>(xa, xb, Ca, Cb, tra, trb, wdw, wpk, z, gstat, COUT, N, H, W, gamma, pooled, st);
-    DWPW_CASE(1, 1, true) DWPW_CASE(2, 1, true) DWPW_CASE(2, 2, true)
-    DWPW_CASE(4, 1, true) DWPW_CASE(4, 2, true) DWPW_CASE(4, 4, true)  // Cin == 32: pipelined single-chunk variants
-    DWPW_CASE(4, 1, false) DWPW_CASE(4, 2, false) DWPW_CASE(4, 4, false) DWPW_CASE(4, 8, false) DWPW_CASE(4, 16, false)
-#undef DWPW_CASE
-    return OCRS_ERR_ARG;
-}
-extern "C" {
-
 // Fused DepthwiseConv block forward up to the pre-BatchNorm output (reference: ocrs_models/models.py:11-23).
 //   xa/xb : NHWC inputs (xb may be null; channel concat [xa | xb] as torch.cat at models.py:89), Ca, Cb multiples of 8
 //   tra/trb : [3][Ca] / [3][Cb] load transforms of the inputs (producer BN+ReLU, or identity)
@@ -574,13 +420,6 @@ extern "C" {
 //   z     : [P][Cout] pre-BN output; gstat: [2][Cout] double, sum z and sum z^2 ACCUMULATED (the caller zeroes it: one
 //           memset for all layers of a step instead of one per launch)
 // 1 if ocrs_dwpw_fwd can also write the 2x2-max-pooled (pre-BatchNorm) output: two-pixel tile configurations, Cout <= 64
-long det_dwf_supported(int Cin, int Cout, int dtype);  // det_dwf.hip: deep-level forward, a whole tile at once (no fused max-pool)
-long det_c1v2_supported(int N, int H, int W);  // det_c1.hip
-int det_c1v2_fwd_launch(const float* img, const float* wdw, const float* wpw, void* z, double* gstat, int N, int H, int W, int dtype, hipStream_t st,
-                        void* uplane, double* fsum);
-int det_c1_bwd_fin_launch(const double* c1acc, const double* fsum, const float* coef, const float* wexp, double* acc64, hipStream_t st);
-int det_dwf_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* wpk, void* z,
-                   double* gstat, int Cout, int N, int H, int W, hipStream_t st, const FwdFin& fin);
 long ocrs_dwpw_fwd_pool_supported(int Cin, int Cout) {
     if (det_dwf_supported(Cin, Cout, 1)) return 0;  // (the deep-level kernel is faster than the fusion saves: the max-pool stays its own pass there)
     return Cout <= 64 && (Cin < 32 || Cin % 32 == 0) ? 1 : 0;
@@ -615,43 +454,6 @@ int ocrs_dwpw_fwd_fin(const void* xa, const void* xb, int Ca, int Cb, const floa
                           FwdFin{counter, count, bn_w, bn_b, eps, momentum, tr, saved, run_mean, run_var, nbt, lo});
 }
 
-// First block (1 -> 8): img fp32 (N,1,H,W); wdw [9]; wpw [8]; z [P][8]; gstat [2][8] accumulated (caller zeroes).
-int ocrs_dwpw_c1_fwd(const float* img, const float* wdw, const float* wpw, void* z, double* gstat, int N, int H, int W, int dtype,
-                     hipStream_t st) {
-    OCRS_CHECK_ARG(img && wdw && wpw && z && gstat);
-    if (det_c1v2_supported(N, H, W)) return det_c1v2_fwd_launch(img, wdw, wpw, z, gstat, N, H, W, dtype, st, nullptr, nullptr);  // det_c1.hip
-    const long P = (long)N * H * W;
-    const int grid = ew_grid(P);
-    if (dtype == 1)
-        hipLaunchKernelGGL(k_dwpw_c1_fwd<bf16>, dim3(grid), dim3(256), 0, st, img, wdw, wpw, (bf16*)z, gstat, H, W, P);
-    else
-        hipLaunchKernelGGL(k_dwpw_c1_fwd<float>, dim3(grid), dim3(256), 0, st, img, wdw, wpw, (float*)z, gstat, H, W, P);
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-
-// The same, additionally writing the block output's rank-one generator: uplane [N][H][W] bf16 = the rounded depthwise output u, z[p][c] = round(Wpw[c] * u[p])
-// (see k_c1_fwd2).  ocrs_dwpw_c1_u_supported: 1 if this shape / dtype has the form (bf16, the 64-column x 2-row kernel).
-long ocrs_dwpw_c1_u_supported(int N, int H, int W, int dtype) { return dtype == 1 && det_c1v2_supported(N, H, W) ? 1 : 0; }
-int ocrs_dwpw_c1_fwd_u(const float* img, const float* wdw, const float* wpw, void* z, void* uplane, double* gstat, int N, int H, int W, int dtype,
-                       hipStream_t st) {
-    OCRS_CHECK_ARG(img && wdw && wpw && uplane && gstat && ocrs_dwpw_c1_u_supported(N, H, W, dtype));  // (z may be null: only the u plane is written)
-    return det_c1v2_fwd_launch(img, wdw, wpw, z, gstat, N, H, W, dtype, st, uplane, nullptr);
-}
-// ocrs_dwpw_c1_fwd_u that also accumulates the forward-only sums of the fused first-block backward (ocrs_mm_bwd_fin_xu_c1 + ocrs_c1_bwd_fin):
-// fsum [20] fp64 (zeroed by the caller) += sum u | sum u^2 | sum u img(tap) [9] | sum img(tap) [9]
-int ocrs_dwpw_c1_fwd_us(const float* img, const float* wdw, const float* wpw, void* z, void* uplane, double* gstat, double* fsum, int N, int H, int W, int dtype,
-                        hipStream_t st) {
-    OCRS_CHECK_ARG(img && wdw && wpw && uplane && gstat && fsum && dtype == 1 && ocrs_dwpw_c1_u_supported(N, H, W, dtype));
-    return det_c1v2_fwd_launch(img, wdw, wpw, z, gstat, N, H, W, dtype, st, uplane, fsum);
-}
-// The first block's weight gradient from the sums of ocrs_dwpw_c1_fwd_us (fsum) and ocrs_mm_bwd_fin_xu_c1 (c1acc [8][32] fp64) and the block's
-// BatchNorm-backward coefficients coef [3][8] (ocrs_bn_bwd_finalize): acc64 [17] += dWpw [8] | dWdw [9], as ocrs_dwpw_c1_bwd.
-int ocrs_c1_bwd_fin(const double* c1acc, const double* fsum, const float* coef, const float* wexp, double* acc64, hipStream_t st) {
-    OCRS_CHECK_ARG(c1acc && fsum && coef && wexp && acc64);
-    return det_c1_bwd_fin_launch(c1acc, fsum, coef, wexp, acc64, st);
-}
-
 // BatchNorm2d batch statistics -> load transform (reference: nn.BatchNorm2d at models.py:23, training mode).
 int ocrs_bn_finalize(const double* gstat, long count, int C, const float* gamma, const float* beta, float eps, float momentum, float* tr,
                      float* saved, float* run_mean, float* run_var, long long* nbt, float lo, hipStream_t st) {
@@ -676,196 +478,6 @@ int ocrs_maxpool_fwd(const void* z, const float* tr, void* out, int C, int N, in
         else OCRS_POOL(float, false);
     }
 #undef OCRS_POOL
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-
-}  // extern "C" (templates need C++ linkage)
-// ConvTranspose2d forward for the top levels (bf16, Cup = 16 / 32): 2-D tiles of 8 x 16 quad positions.  The transformed input tile
-// (+1 halo row / column: a quad position (qy, qx) reads inputs (qy - dy, qx - dx), dy, dx in {0,1}) is staged ONCE in LDS in bf16
-// NHWC order and every MFMA pixel-operand fragment is a single ds_read_b128 straight from it (k = d*Cup + c: 8 consecutive channels of one
-// neighbour); packed weight fragments are cached in LDS; the next tile's input is register-prefetched.  Replaces per-chunk
-// global gathers (each input pixel fetched 4x) + two barriers per 32-wide K chunk: level 0 0.52 -> 0.25 ms.
-template <int CUP, int COUT>
-struct CtfCfg {
-    static constexpr int TH = 8, TW = 16, TPOS = TH * TW;                 // quad positions per tile
-    static constexpr int XH = TH + 1, XW = TW + 1, XP = XH * XW;           // input tile with the top / left halo
-    static constexpr int NKC = 4 * CUP / 32, MT = 4 * COUT / 16;           // K chunks of 32, M tiles of 16 (M = (parity, cout))
-    static constexpr int XI = XP * CUP / 8, NXI = (XI + 255) / 256;       // 16-byte staging items
-    static constexpr int XPITCH = CUP + 8;                                 // elements: rows of 48 / 80 B keep the b128 reads spread over banks
-    static constexpr int SMEM = (XP * XPITCH + NKC * MT * 64 * 8) * 2 + 3 * CUP * 4 + 4 * COUT * 4;
-};
-template <int CUP, int COUT>
-__global__ __launch_bounds__(256) void k_convt_fwd_tile(const bf16* __restrict__ x, const float* __restrict__ tr, const void* __restrict__ wpk,
-                                                        const float* __restrict__ bias, bf16* __restrict__ out, int h, int w, int H, int W,
-                                                        Tiling2 tg) {
-    using C = CtfCfg<CUP, COUT>;
-    constexpr int TW = C::TW, TH = C::TH, XW = C::XW, MT = C::MT, NKC = C::NKC, XPITCH = C::XPITCH;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    bf16* xs = reinterpret_cast<bf16*>(smem);                              // [XP][XPITCH]
-    uint4* s_wf = reinterpret_cast<uint4*>(xs + C::XP * XPITCH);           // [NKC*MT][64] packed weight fragments
-    float* s_tr = reinterpret_cast<float*>(s_wf + NKC * MT * 64);          // [CUP/8][3][8]
-    float* s_bias = s_tr + 3 * CUP;                                        // [4*COUT] bias per M row
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {
-        Src2<bf16> xsrc{x, nullptr, CUP, 0};
-        fill_tr8(s_tr, xsrc, tr, nullptr, CUP, tid);
-        for (int i = tid; i < NKC * MT * 64; i += 256) s_wf[i] = reinterpret_cast<const uint4*>(wpk)[i];
-        for (int i = tid; i < 4 * COUT; i += 256) s_bias[i] = bias[i % COUT];
-    }
-    // tile-invariant staging descriptors: item it -> halo pixel (hy, hx), channel group
-    int xoff[C::NXI], xyx[C::NXI];
-#pragma unroll
-    for (int j = 0; j < C::NXI; ++j) {
-        const int it = tid + j * 256, hp = it / (CUP / 8), cg8 = it % (CUP / 8);
-        const int hy = hp / XW, hx = hp % XW;
-        xoff[j] = (hy * w + hx) * CUP + cg8 * 8;
-        xyx[j] = hy | (hx << 16);
-    }
-    Raw8<bf16> xr[C::NXI];
-    unsigned okx = 0;
-    auto issue = [&](const TileOrg& o) {  // o = (n, qy0, qx0); halo corner = input pixel (qy0 - 1, qx0 - 1)
-        const bf16* xb = x + (((long)o.n * h + (o.h0 - 1)) * w + (o.w0 - 1)) * CUP;
-        okx = 0;
-#pragma unroll
-        for (int j = 0; j < C::NXI; ++j) {
-            const int iy = o.h0 - 1 + (xyx[j] & 0xffff), ix = o.w0 - 1 + (xyx[j] >> 16);
-            const bool ok = (C::XI % 256 == 0 || tid + j * 256 < C::XI) && (unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w;
-            xr[j] = load8_raw(ok ? xb + xoff[j] : x);
-            okx |= ok ? 1u << j : 0u;
-        }
-    };
-    // this lane's two N tiles (pixels) per wave: quad position q = (wave*2 + a)*16 + (lane & 15); operand k-group kg = lane >> 4
-    const int kg = lane >> 4;
-    TileSched ts(tg.ntiles);
-    TileOrg org_next = tile_origin2<TW, TH>(tg, (int)(ts.first < ts.end ? ts.first : 0));
-    if (ts.first < ts.end) issue(org_next);
-    __syncthreads();
-    for (long t = ts.first; t < ts.end; t += ts.step) {
-        const TileOrg org = org_next;
-#pragma unroll
-        for (int j = 0; j < C::NXI; ++j) {
-            const int it = tid + j * 256;
-            if (C::XI % 256 == 0 || it < C::XI) {
-                float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                if (okx & (1u << j)) {
-                    const float* tp = s_tr + (it % (CUP / 8)) * 24;
-                    float sc[8], sh[8], lo[8];
-                    unpack8(xr[j], v);
-                    load8(tp, sc);
-                    load8(tp + 8, sh);
-                    load8(tp + 16, lo);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = max_lo(fmaf(v[i], sc[i], sh[i]), lo[i]);
-                }
-                store8_opaque(xs + (it / (CUP / 8)) * XPITCH + (it % (CUP / 8)) * 8, v);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (t + ts.step < ts.end) {
-            org_next = tile_origin2<TW, TH>(tg, (int)(t + ts.step));
-            issue(org_next);
-        }
-        lds_barrier();
-        f32x4 acc[2][MT];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < MT; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kc = 0; kc < NKC; ++kc) {
-            const int k0 = kc * 32 + kg * 8, d = k0 / CUP, c0 = k0 % CUP;  // neighbour d = dy*2 + dx, channels c0..c0+7
-            uint4 pf[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const int q = (wave * 2 + a) * 16 + (lane & 15), qy = q / TW, qx = q % TW;
-                // input (qy - dy, qx - dx) = halo pixel (qy + 1 - dy, qx + 1 - dx)
-                pf[a] = *reinterpret_cast<const uint4*>(xs + ((qy + 1 - (d >> 1)) * XW + (qx + 1 - (d & 1))) * XPITCH + c0);
-            }
-#pragma unroll
-            for (int b = 0; b < MT; ++b) {
-                const uint4 wf = s_wf[(kc * MT + b) * 64 + lane];
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, pf[a]), acc[a][b], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int q = (wave * 2 + a) * 16 + (lane & 15), qy = org.h0 + q / TW, qx = org.w0 + q % TW;
-#pragma unroll
-            for (int b = 0; b < MT; ++b) {
-                const int m0 = b * 16 + kg * 4, par = m0 / COUT, o0 = m0 % COUT;
-                const int Y = 2 * qy + (par >> 1), X = 2 * qx + (par & 1);
-                if (qy <= h && qx <= w && Y < H && X < W) {
-                    const f32x4 v = acc[a][b];
-                    store4(out + (((long)org.n * H + Y) * W + X) * COUT + o0, v[0] + s_bias[m0], v[1] + s_bias[m0 + 1], v[2] + s_bias[m0 + 2],
-                           v[3] + s_bias[m0 + 3]);
-                }
-            }
-        }
-        lds_barrier();  // all fragment reads done before the next commit overwrites xs
-    }
-}
-
-template <class T>
-static int dispatch_convt_fwd(const void* x, const float* tr, const void* wpk, const float* bias, void* out, int Cup, int Cout, int N, int h,
-                              int w, int H, int W, hipStream_t st) {
-    const int MT_total = (4 * Cout) / 16;
-    const long P = (long)N * (h + 1) * (w + 1);
-    const long ntiles = (P + 63) / 64;
-#define CONVT_CASE(MT_)                                                                                                                  \
-    {                                                                                                                                    \
-        const int gy = MT_total / MT_;                                                                                                   \
-        int gx = persistent_grid(ntiles, 8);                                                                                             \
-        hipLaunchKernelGGL((k_convt_fwd<T, MT_>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, tr, wpk, bias, (T*)out, Cup, Cout, h, w, \
-                           H, W, N, MT_total);                                                                                           \
-    }
-    if (MT_total % 8 == 0)
-        CONVT_CASE(8)
-    else if (MT_total % 4 == 0)
-        CONVT_CASE(4)
-    else
-        CONVT_CASE(2)
-#undef CONVT_CASE
-    OCRS_LAUNCH_CHECK();
-    return OCRS_OK;
-}
-extern "C" {
-
-long det_ctf_supported(int Cup, int Cout, int dtype);  // det_ctf.hip
-int det_ctf_launch(const void* x, const float* tr, const void* wpk, const float* bias, void* out, int Cup, int Cout, int N, int h, int w, int H, int W,
-                   hipStream_t st);
-// ConvTranspose2d(Cup->Cout, k=3, s=2, bias) cropped to (H, W)  (models.py:76-78,82-87).
-//   x [N][h][w][Cup] with load transform tr [3][Cup]; wpk = ocrs_pack_frags(mode 1, K=4*Cup, M=4*Cout); out [N][H][W][Cout]
-int ocrs_convt_fwd(const void* x, const float* tr, const void* wpk, const float* bias, void* out, int Cup, int Cout, int N, int h, int w,
-                   int H, int W, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(x && tr && wpk && bias && out);
-    OCRS_CHECK_ARG(Cup % 8 == 0 && Cout % 8 == 0 && (H == 2 * h || H == 2 * h + 1) && (W == 2 * w || W == 2 * w + 1));
-#define CTF_CASE(CU_, CO_)                                                                                                                \
-    if (dtype == 1 && Cup == CU_ && Cout == CO_) {                                                                                       \
-        using CC = CtfCfg<CU_, CO_>;                                                                                                      \
-        const Tiling2 tg = make_tiling2(N, h + 1, w + 1, CC::TW, CC::TH); /* quad positions: (h+1) x (w+1) */                             \
-        hipLaunchKernelGGL((k_convt_fwd_tile<CU_, CO_>), dim3(persistent_grid(tg.ntiles, 4)), dim3(256), CC::SMEM, st, (const bf16*)x, tr, wpk, bias, \
-                           (bf16*)out, h, w, H, W, tg);                                                                                   \
-        OCRS_LAUNCH_CHECK();                                                                                                              \
-        return OCRS_OK;                                                                                                                   \
-    }
-    CTF_CASE(16, 8) CTF_CASE(32, 16) CTF_CASE(32, 32)
-#undef CTF_CASE
-    if (det_ctf_supported(Cup, Cout, dtype)) return det_ctf_launch(x, tr, wpk, bias, out, Cup, Cout, N, h, w, H, W, st);  // deep levels (det_ctf.hip)
-    return dtype == 1 ? dispatch_convt_fwd<bf16>(x, tr, wpk, bias, out, Cup, Cout, N, h, w, H, W, st)
-                      : dispatch_convt_fwd<float>(x, tr, wpk, bias, out, Cup, Cout, N, h, w, H, W, st);
-}
-
-// out_conv 1x1 (8->1) + bias + sigmoid (models.py:125-129).  pred fp32 [N][1][H][W].
-int ocrs_head_fwd(const void* z, const float* tr, const float* w, const float* b, float* pred, long P, int dtype, hipStream_t st) {
-    OCRS_CHECK_ARG(z && tr && w && b && pred && P > 0);
-    const int grid = ew_grid(P);
-    if (dtype == 1)
-        hipLaunchKernelGGL(k_head_fwd<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)z, tr, w, b, pred, P);
-    else
-        hipLaunchKernelGGL(k_head_fwd<float>, dim3(grid), dim3(256), 0, st, (const float*)z, tr, w, b, pred, P);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }

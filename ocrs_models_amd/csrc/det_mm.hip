@@ -14,8 +14,7 @@
 //     [+ the BatchNorm-backward sums of the block(s) that produced x:  sum ghat', sum ghat' x~  with ghat' = dx~ [x~ > 0]]
 // HBM bytes per pixel: x (Cin) + z, g (Cout, 1.1-1.3x with the ring, mostly L2 hits) in, dx~ (Cin) out -- the 2 (Cin + Cout) of
 // SURVEY.md 8(d); du is never formed.  All flushes are per-block partials reduced by ONE deterministic kernel (no atomics).
-#include "det_common.h"
-#include "det_rs.h"
+#include "det_internal.h"
 #include <type_traits>
 
 // Tile shapes and residency are the measured optimum (profiles/README.md; other shapes are measured on patched copies: tools/build_variant.sh).

@@ -8,7 +8,7 @@
 // max-pool-routed case the horizontal window neighbour is the thread's own second pixel (the vertical one is lane ^ 16), so the
 // first-maximum test costs 16 instead of 36 VALU per (pixel, channel) and 8 instead of 12 lane shuffles per pair.
 // Software pipeline as in the other tiled kernels: the next tile's raw x / z / g vectors are register-prefetched, barriers order LDS only.
-#include "det_common.h"
+#include "det_internal.h"
 
 template <int CIN, int COUT>
 struct Pw2Cfg {
@@ -257,8 +257,6 @@ __global__ __launch_bounds__(256, 3) void k_pw_bwd2(Src2<bf16> x, const float* _
     }
 }
 
-extern "C" {
-
 static int pw2_grid(int Cin, int Cout, int N, int H, int W) {
     const int cgm = (Cin > Cout ? Cin : Cout) / 8, tw = (512 / cgm) / 16;
     const long ntiles = (long)N * ((W + tw - 1) / tw) * ((H + 15) / 16);
@@ -271,8 +269,6 @@ long det_pw2_supported(int Cin, int Cout, int dtype) {
                           (Cin == 32 && (Cout == 16 || Cout == 32)));
 }
 long det_pw2_ws_floats(int Cin, int Cout, int N, int H, int W) { return (long)pw2_grid(Cin, Cout, N, H, W) * Cin * Cout; }
-
-void k_wgrad_partials_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st);  // det_bwd.hip
 
 int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
                  int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
@@ -297,9 +293,7 @@ int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
     }
     PW2_CASE(8, 8) PW2_CASE(8, 16) PW2_CASE(16, 8) PW2_CASE(16, 16) PW2_CASE(16, 32) PW2_CASE(32, 16) PW2_CASE(32, 32)
 #undef PW2_CASE
-    if (ws) k_wgrad_partials_reduce_launch(ws, nb, Cin * Cout, dwpw, Cin, ldw, st);
+    if (ws) det_wgrad_reduce_launch(ws, nb, Cin * Cout, dwpw, Cin, ldw, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-
-}  // extern "C"

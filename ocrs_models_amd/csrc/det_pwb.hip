@@ -11,7 +11,7 @@
 //   C  du = Wpw^T dz on MFMA (K = Cout from dzN, packed weight fragments from L2 double-buffered), u = dw3x3(x~) on the VALU -> uN [64][Cin],
 //   E  dWpw += u^T dz on MFMA (K = the 64 pixels, both operands by LDS transpose reads), the full Cin x Cout gradient in registers
 //      (128 per wave at 256 x 256), flushed once per block as a partial for the deterministic reducer.
-#include "det_common.h"
+#include "det_internal.h"
 
 namespace {
 template <int CIN, int COUT>
@@ -373,10 +373,6 @@ __global__ __launch_bounds__(512, (pwb_bpc(CIN, COUT, PPOOL) * 2)) void k_pwb(Sr
     }
 }
 
-extern "C" {
-
-void k_wgrad_partials_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st);  // det_bwd.hip
-
 // blocks of the launch (= workspace slots of Cin * Cout floats each)
 static int pwb_th(int Cin, int Cout) { return (Cin >= 128 || Cout > 128) ? 4 : 8; }
 static int pwb_ny(int Cin) { return Cin == 256 ? 2 : 1; }  // 256 input channels: two channel ranges of the 128-channel kernel (grid.y)
@@ -430,9 +426,7 @@ int det_pwb_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
 #undef PWB_CASE
 #undef PWB_LAUNCH
     OCRS_CHECK_ARG(done);
-    k_wgrad_partials_reduce_launch(ws, gx, Cin * Cout, dwpw, Cin, Cin, st);
+    det_wgrad_reduce_launch(ws, gx, Cin * Cout, dwpw, Cin, Cin, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
-
-}  // extern "C"

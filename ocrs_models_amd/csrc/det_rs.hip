@@ -24,7 +24,7 @@
 //   * Work split: the (image, strip, row pair) steps are cut into equal contiguous ranges, one per wave (two warm-up ticks per range start /
 //     strip change): no tail, no tile scheduler.
 // HBM bytes per pixel: x (Cin) + z, g (Cout) in, dx~ (Cin) out = the 2 (Cin + Cout) of SURVEY.md 8(d), x 32/30 for the halo columns of the reads.
-#include "det_rs.h"
+#include "det_internal.h"
 #include <type_traits>
 
 // Waves per SIMD the kernel is compiled for (register cap 512 / WPS) = resident 4-wave workgroups per CU.  The memory side prefers fewer, more

@@ -18,7 +18,7 @@
 //   ahead into a register ring; there is no LDS traffic and no barrier in the loop.  BatchNorm batch statistics: per-lane fp32 partials ->
 //   DPP row sums -> one fp64 atomic per (workgroup, channel) (an fp64 sum of fp32 values is exact, hence order-independent: bit-reproducible),
 //   finalised by the launch's last workgroup (bn_finalize_last_block).  Fused MaxPool2d(2) in its pre-BatchNorm form as in k_dwpw_fwd<.., POOL>.
-#include "det_common.h"
+#include "det_internal.h"
 
 namespace {
 
@@ -1488,7 +1488,6 @@ static double* rs32_last_scratch(int ndoubles, hipStream_t st) {
 }
 }  // namespace
 
-extern "C" {
 // ---- ConvTranspose weight / bias gradient launcher for ocrs_convt_bwd_parts (det_bwd.hip): fp32, Cup in {16, 32}, Cout in {8, 16, 32}
 long det_rs32_ctw_supported(int Cup, int Cout, int dtype) {
     return (dtype == 0 && (Cup == 16 || Cup == 32) && (Cout == 8 || Cout == 16 || Cout == 32)) ? 1 : 0;
@@ -1529,6 +1528,8 @@ int det_rs32_ctw_launch(const float* x, const float* tr, const float* g, float* 
     }
     return OCRS_OK;
 }
+
+extern "C" {
 
 // 1 if ocrs_rs32_fwd runs this block shape: fp32 storage; Cin = Ca + Cb in {8, 16, 32}, a concat split only as 8 | 8 or 16 | 16; Cout in {8, 16, 32}.
 long ocrs_rs32_fwd_supported(int Ca, int Cb, int Cout, int dtype) {

@@ -469,12 +469,6 @@ __global__ void k_fold64_multi(const int* __restrict__ table, float* __restrict_
     for (int i = threadIdx.x; i < n; i += 64) dst[d + i] = (float)((double)dst[d + i] + src[s0 + i]);
 }
 
-static inline int ew_grid(long items) {
-    long g = (items + 255) / 256;
-    const long cap = (long)kNumCU * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 extern "C" {
 
 long ocrs_loss_state_bytes() { return (long)sizeof(LossState); }

@@ -1,5 +1,5 @@
 // Device-resident state of one balanced-BCE loss call (ocrs_models/train_detection.py:225-263), shared by the loss kernels (loss_optim.hip) and by the
-// head backward that forms dL/dpred on the fly from it (det_bwd.hip: k_head_bwd_loss).
+// head backward that forms dL/dpred on the fly from it (det_head.hip: k_head_bwd_loss).
 #pragma once
 struct LossState {            // device-resident, one per loss call
     unsigned long long cnt[2];   // #pos, #neg

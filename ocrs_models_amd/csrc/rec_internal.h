@@ -1,14 +1,7 @@
 // Host-side internals the recogniser's files share (C++ linkage; the C ABI is include/ocrs_hip.h).  Included by the file that defines each
 // function and by every file that calls it.
 #pragma once
-#include "det_common.h"
-
-// grid of an element-wise pass: one thread per item, at most 8 blocks of 256 per CU (the kernels loop)
-static inline int ew_grid(long items) {
-    long g = (items + 255) / 256;
-    const long cap = (long)kNumCU * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+#include "det_internal.h"  // the deferral queue (bwd_defer_*, det_defer.hip)
 
 // rec_pool.hip: partial buffer [nb][n] + queued fixed-order column sum into out [n] (null: not deferring -- the launch keeps its atomics)
 float* rec_defer_partials(int nb, int n, float* out);

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void k_avgpool_dz(const float* __restrict__ gs
 
 // per-column sum of a [rows][ld] fp32/bf16 matrix (bias gradients)
 // ws (nullable, round 5): per-block partials [gridDim.x][C] instead of the cross-block float atomics -- summed in a fixed order by the deferred
-// reduce launch (ocrs_bwd_defer_begin / _flush, det_bwd.hip).  The in-block sums are fixed-order slots (no LDS float atomics) either way.
+// reduce launch (ocrs_bwd_defer_begin / _flush, det_defer.hip).  The in-block sums are fixed-order slots (no LDS float atomics) either way.
 template <class T>
 __global__ __launch_bounds__(256) void k_col_sum(const T* __restrict__ a, int ld, int C, float* __restrict__ out, long rows, float* __restrict__ ws) {
     extern __shared__ float s_acc[];  // [2 row phases][C]
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void k_col_sum4(const T* __restrict__ a, int l
 }
 
 // Deferred mode (ocrs_bwd_defer_begin .. _flush): a launch that would end in cross-block float atomics onto out [n] writes per-block partials
-// [nb][n] instead and queues their fixed-order column sum (k_reduce_multi, det_bwd.hip) -- the sums become bit-reproducible.  Returns the partial
+// [nb][n] instead and queues their fixed-order column sum (k_reduce_multi, det_defer.hip) -- the sums become bit-reproducible.  Returns the partial
 // buffer, or null (not deferring / pool or queue full): the launch then falls back to the atomics.
 float* rec_defer_partials(int nb, int n, float* out) {
     float* ws = bwd_defer_ws((long)nb * n);

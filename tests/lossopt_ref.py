@@ -1,5 +1,5 @@
 """Float64 references, CPU emulations and the cases of the loss / optimiser kernel tests (csrc/loss_optim.hip and the fused k_head_bwd_loss of
-csrc/det_bwd.hip), stated once for tests/test_lossopt_host.py (CPU: proves what the GPU test rests on) and tests/test_lossopt_gpu.py.
+csrc/det_head.hip), stated once for tests/test_lossopt_host.py (CPU: proves what the GPU test rests on) and tests/test_lossopt_gpu.py.
 
 Balanced BCE.  The kernel's tie rule is deterministic (every tie at the k-th largest loss is weighted need / ties), so given the per-pixel loss
 the kernel itself stored, the whole selection -- counts, k, threshold bits, need, ties, frac, 1/(2k) and the weight of every pixel -- has exactly

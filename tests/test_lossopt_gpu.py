@@ -1,4 +1,4 @@
-"""The detection loss and the optimiser kernels (csrc/loss_optim.hip, and k_head_bwd_loss of csrc/det_bwd.hip, which restates the loss
+"""The detection loss and the optimiser kernels (csrc/loss_optim.hip, and k_head_bwd_loss of csrc/det_head.hip, which restates the loss
 backward) against float64 on the CPU.  tests/lossopt_ref.py states the references and the cases once; tests/test_lossopt_host.py proves on the
 CPU what these tests rest on (each case's property, that select_ref states the radix select's rule, that the tie rule is visible, the bounds).
 
