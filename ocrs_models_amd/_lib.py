@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("OCRS_LIB_PATH") or os.path.join(_HERE, "libocrs_hip.s
 
 _T = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "d": ctypes.c_double, "s": ctypes.c_void_p}
 
+DT = {torch.float32: 0, torch.bfloat16: 1}  # the dtype codes of the ABI's ``dt`` arguments
+
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ocrs_hip.h")
 
 

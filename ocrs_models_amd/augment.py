@@ -19,9 +19,8 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ._lib import lib, ptr
-from .input_pipeline import _DT, line_output_width
-from .text import ctc_input_and_target_compatible, round_up
+from ._lib import DT, lib, ptr
+from .text import collate_plan, line_output_width
 
 MASK_SIZE = (800, 600)  # train_detection.py's mask_size
 CROP_SIZE = 600  # RandomCrop(size=600)
@@ -161,7 +160,7 @@ def sample_line_params(sizes, generator: torch.Generator | None = None, rng: ran
 
 
 # ---- device records ---------------------------------------------------------------------------------------------------------------
-def _records(params: list[AugParams], line: bool, widths=None) -> np.ndarray:
+def records(params: list[AugParams], line: bool, widths=None) -> np.ndarray:
     """AugParams -> [B][REC_WORDS] int32 device records (layout in include/ocrs_hip.h)."""
     rec = np.zeros((len(params), REC_WORDS), dtype=np.int32)
     f = rec[:, 16:].view(np.float32)
@@ -195,7 +194,7 @@ def _records(params: list[AugParams], line: bool, widths=None) -> np.ndarray:
     return rec
 
 
-def _check_sizes(sizes, what: str):
+def check_sizes(sizes, what: str):
     for h, w in sizes:
         if not (0 < h <= 65535 and 0 < w <= 65535 and h * w < 2**31):
             raise RuntimeError(f"{what}: unsupported sample size {(h, w)} (each side 1..65535, H*W < 2^31)")
@@ -209,7 +208,7 @@ def _nbytes(part) -> int:
     return part.nbytes if isinstance(part, np.ndarray) else sum(t.numel() * t.element_size() for t in part)
 
 
-def _pin(parts: list) -> tuple[torch.Tensor, list[int]]:
+def pin(parts: list) -> tuple[torch.Tensor, list[int]]:
     """Host sections (numpy arrays, or lists of host tensors packed back to back) -> one pinned uint8 buffer with 16-byte aligned sections
     and their offsets.  Every sample is copied once, straight into the buffer."""
     offs, n = [], 0
@@ -229,7 +228,7 @@ def _pin(parts: list) -> tuple[torch.Tensor, list[int]]:
     return host, offs
 
 
-def _upload(parts: list, device, what: str) -> list[torch.Tensor]:
+def upload(parts: list, device, what: str) -> list[torch.Tensor]:
     """Sections -> packed device tensors, in order.  numpy arrays and lists of host tensors go through one pinned buffer and one H2D copy;
     a list of GPU tensors is packed by one torch.cat on the device.  Each list may live on either side, independently of the others."""
     on_dev = []
@@ -242,7 +241,7 @@ def _upload(parts: list, device, what: str) -> list[torch.Tensor]:
             raise RuntimeError(f"{what}: the tensors of one list must be all on the host or all on the GPU")
         on_dev.append(kinds.pop())
     host_parts = [part for part, d in zip(parts, on_dev) if not d]
-    host, offs = _pin(host_parts)
+    host, offs = pin(host_parts)
     staged = host.to(device, non_blocking=True)
     ups = iter((staged[o : o + _nbytes(part)], part) for part, o in zip(host_parts, offs))
     out = []
@@ -253,6 +252,24 @@ def _upload(parts: list, device, what: str) -> list[torch.Tensor]:
         raw, part = next(ups)
         out.append(raw.view(torch.from_numpy(part[:0]).dtype if isinstance(part, np.ndarray) else _flat(part[0]).dtype))
     return out
+
+
+def resolve_params(params, sizes: list, augment: bool, sample, who: str, what: str, generator=None, rng=None) -> list[AugParams]:
+    """The draws of a batch: ``params`` when given, else one ``sample`` draw per (H, W) of ``sizes`` (``augment``) or the identity; checked
+    against ``sizes`` either way (``who`` and ``what`` name the caller and its samples in the error)."""
+    if params is None:
+        params = sample(sizes, generator, rng) if augment else [AugParams(-1, s, s) for s in sizes]
+    if [tuple(p.size) for p in params] != sizes:
+        raise RuntimeError(f"{who}: params do not match the {what} sizes")
+    return params
+
+
+def launch_det(pages_d, masks_d, offs_d, rec_d, sizes: list, image, text_mask, mask_kind: int):
+    """The three launches of ocrs_augment_det on packed device pages and masks (0 = uint8 0/1, 1 = fp32) into ``image`` and ``text_mask``."""
+    B, (oh, ow) = image.shape[0], image.shape[-2:]
+    ws = torch.empty(lib().augment_det_ws_floats(B), dtype=torch.float32, device=image.device)
+    lib().augment_det(ptr(pages_d), ptr(masks_d), ptr(offs_d), ptr(rec_d), ptr(ws), ptr(image), ptr(text_mask), B, max(h for h, _ in sizes),
+                      max(w for _, w in sizes), oh, ow, mask_kind, DT[image.dtype])
 
 
 def detection_batch(images, masks, device, augment: bool, dtype: torch.dtype = torch.float32, generator: torch.Generator | None = None,
@@ -271,11 +288,8 @@ def detection_batch(images, masks, device, augment: bool, dtype: torch.dtype = t
     sizes = [tuple(im.shape[-2:]) for im in images]
     if any(im.dim() != 3 or im.shape[0] != 1 or tuple(m.shape) != tuple(im.shape) for im, m in zip(images, masks)):
         raise RuntimeError("detection_batch: every image and its mask must be (1, H, W) of the same size")
-    _check_sizes(sizes, "detection_batch")
-    if params is None:
-        params = sample_detection_params(sizes, generator, rng) if augment else [AugParams(-1, s, s) for s in sizes]
-    if [tuple(p.size) for p in params] != sizes:
-        raise RuntimeError("detection_batch: params do not match the image sizes")
+    check_sizes(sizes, "detection_batch")
+    params = resolve_params(params, sizes, augment, sample_detection_params, "detection_batch", "image", generator, rng)
     oh, ow = mask_size
     image = torch.empty(B, 1, oh, ow, dtype=dtype, device=device)
     text_mask = torch.empty(B, 1, oh, ow, dtype=torch.float32, device=device)
@@ -283,51 +297,36 @@ def detection_batch(images, masks, device, augment: bool, dtype: torch.dtype = t
         return {"image": image, "text_mask": text_mask}
     n = np.array([h * w for h, w in sizes], dtype=np.int64)
     offs = np.cumsum(n) - n
-    rec = _records(params, line=False)
-    rec_d, offs_d, img_d, msk_d = _upload([rec, offs, list(images), list(masks)], device, "detection_batch")
-    ws = torch.empty(lib().augment_det_ws_floats(B), dtype=torch.float32, device=device)
-    lib().augment_det(ptr(img_d), ptr(msk_d), ptr(offs_d), ptr(rec_d), ptr(ws), ptr(image), ptr(text_mask), B, max(h for h, _ in sizes),
-                      max(w for _, w in sizes), oh, ow, 1 if msk_d.dtype == torch.float32 else 0, _DT[dtype])
+    rec_d, offs_d, img_d, msk_d = upload([records(params, line=False), offs, list(images), list(masks)], device, "detection_batch")
+    launch_det(img_d, msk_d, offs_d, rec_d, sizes, image, text_mask, 1 if msk_d.dtype == torch.float32 else 0)
     return {"image": image, "text_mask": text_mask}
 
 
-def _line_batch_plan(text_seqs, params: list[AugParams], output_height: int, dtype, device):
-    """collate_samples' metadata rules on the resized widths (round_up quirk, bucket over every sample, infeasible-sample drop) ->
-    (empty (n, 1, output_height, wmax) image on ``device``, {"text_seq", "text_len", "image_width"} host tensors, kept positions)."""
-    ows = [line_output_width(p.out_size[0], p.out_size[1], output_height) for p in params]
-    wmax = round_up(max(ows), 256)
-    lmax = round_up(max(t.shape[0] for t in text_seqs), 64)
-    keep = [k for k, t in enumerate(text_seqs) if ctc_input_and_target_compatible(ows[k] // 4, t)]
-    n = len(keep)
-    text = torch.zeros(n, lmax, dtype=torch.int32)
-    tl = torch.zeros(n, dtype=torch.int64)
-    iw = torch.zeros(n, dtype=torch.int64)
-    for i, k in enumerate(keep):
-        L = text_seqs[k].shape[0]
-        text[i, :L] = text_seqs[k]
-        tl[i], iw[i] = L, ows[k]
-    image = torch.empty(n, 1, output_height, wmax, dtype=dtype, device=device)
-    return image, {"text_seq": text, "text_len": tl, "image_width": iw}, keep
+def line_batch_plan(text_seqs, params: list[AugParams], output_height: int, dtype, device):
+    """``text.collate_plan`` on the resized widths -> (empty (n, 1, output_height, wmax) image on ``device``, {"text_seq", "text_len",
+    "image_width"} host tensors, kept positions)."""
+    wmax, keep, meta = collate_plan([line_output_width(p.out_size[0], p.out_size[1], output_height) for p in params], text_seqs)
+    return torch.empty(len(keep), 1, output_height, wmax, dtype=dtype, device=device), meta, keep
 
 
-def _line_records(kp: list[AugParams], output_height: int):
+def line_records(kp: list[AugParams], output_height: int):
     """The kept samples' device records and the [n][3] offsets (source, intermediate, horizontal pass) of ocrs_augment_lines."""
     ows = [line_output_width(p.out_size[0], p.out_size[1], output_height) for p in kp]
-    rec = _records(kp, line=True, widths=ows)
+    rec = records(kp, line=True, widths=ows)
     src = np.array([p.size[0] * p.size[1] for p in kp], dtype=np.int64)
     inter = np.array([p.out_size[0] * p.out_size[1] for p in kp], dtype=np.int64)
     hp = np.array([p.out_size[0] * w for p, w in zip(kp, ows)], dtype=np.int64)
     return rec, np.stack([np.cumsum(a) - a for a in (src, inter, hp)], axis=1)
 
 
-def _launch_lines(crops_d, masks_d, offs_d, rec_d, kp: list[AugParams], image, output_height: int, kind: int, augment: bool):
+def launch_lines(crops_d, masks_d, offs_d, rec_d, kp: list[AugParams], image, output_height: int, kind: int, augment: bool):
     """The five launches of ocrs_augment_lines on packed device crops (and masks) into ``image``."""
     inter = sum(p.out_size[0] * p.out_size[1] for p in kp)
     hp = sum(p.out_size[0] * line_output_width(p.out_size[0], p.out_size[1], output_height) for p in kp)
     n = len(kp)
     ws = torch.empty(lib().augment_lines_ws_floats(n, inter, hp), dtype=torch.float32, device=image.device)
     lib().augment_lines(ptr(crops_d), ptr(masks_d), ptr(offs_d), ptr(rec_d), ptr(ws), inter, ptr(image), n, max(p.out_size[0] for p in kp),
-                        max(p.out_size[1] for p in kp), output_height, image.shape[-1], kind, int(augment), _DT[image.dtype])
+                        max(p.out_size[1] for p in kp), output_height, image.shape[-1], kind, int(augment), DT[image.dtype])
 
 
 def collate_lines(samples: list[dict], device, augment: bool, output_height: int = 64, dtype: torch.dtype = torch.float32,
@@ -341,12 +340,9 @@ def collate_lines(samples: list[dict], device, augment: bool, output_height: int
     sizes = [tuple(s["image"].shape[-2:]) for s in samples]
     if any(s["image"].dim() != 3 or s["image"].shape[0] != 1 for s in samples):
         raise RuntimeError("collate_lines: every image must be (1, h, w)")
-    _check_sizes(sizes, "collate_lines")
-    if params is None:
-        params = sample_line_params(sizes, generator, rng) if augment else [AugParams(-1, s, s) for s in sizes]
-    if [tuple(p.size) for p in params] != sizes:
-        raise RuntimeError("collate_lines: params do not match the image sizes")
-    image, meta, keep = _line_batch_plan([s["text_seq"] for s in samples], params, output_height, dtype, device)
+    check_sizes(sizes, "collate_lines")
+    params = resolve_params(params, sizes, augment, sample_line_params, "collate_lines", "image", generator, rng)
+    image, meta, keep = line_batch_plan([s["text_seq"] for s in samples], params, output_height, dtype, device)
     if keep:
         ks = [samples[k] for k in keep]
         kinds = {s["image"].dtype for s in ks}
@@ -357,13 +353,13 @@ def collate_lines(samples: list[dict], device, augment: bool, output_height: int
             raise RuntimeError("collate_lines: give a mask for every sample or for none")
         if any(has_mask) and any(tuple(s["mask"].shape) != tuple(s["image"].shape) for s in ks):
             raise RuntimeError("collate_lines: a mask must have its image's shape")
-        rec, offs = _line_records([params[k] for k in keep], output_height)
+        rec, offs = line_records([params[k] for k in keep], output_height)
         if all(has_mask) and any(s["mask"].dtype not in (torch.uint8, torch.bool) for s in ks):
             raise RuntimeError("collate_lines: masks must be uint8 or bool")
         parts = [rec, offs, [s["image"] for s in ks]] + ([[s["mask"] for s in ks]] if all(has_mask) else [])
-        up = _upload(parts, device, "collate_lines")
+        up = upload(parts, device, "collate_lines")
         rec_d, offs_d, crops_d = up[:3]
         masks_d = up[3] if len(up) > 3 else None
-        _launch_lines(crops_d, masks_d, offs_d, rec_d, [params[k] for k in keep], image, output_height, 0 if torch.uint8 in kinds else 1,
-                      augment)
+        launch_lines(crops_d, masks_d, offs_d, rec_d, [params[k] for k in keep], image, output_height, 0 if torch.uint8 in kinds else 1,
+                     augment)
     return {"image": image, **meta}

@@ -8,7 +8,7 @@ reads the split's annotated words (``datasets.hiertext_word_truth``; ``--level l
 ``inference.evaluate_pages`` -- ``ocr_pages`` in batches of ``--batch-pages``, matched and scored on the device -- and prints ONE JSON line:
 the options used and the result dict (detection precision / recall / f1, the end-to-end ones that also ask for the right text, the two
 character error rates and the raw counters).  The option flags have the names and meanings of ``eval_detection``'s.  Pages are decoded on the
-host (``datasets._read_gray``); that is not a hot path.
+host (``datasets.read_gray``); that is not a hot path.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ import torch
 
 from . import inference
 from .checkpoint import load_model_state
-from .datasets import _decode_pages, _read_gray, hiertext_line_truth, hiertext_word_truth
+from .datasets import decode_pages, hiertext_line_truth, hiertext_word_truth, read_gray
 from .models import DetectionModel
 from .recognition import RecognitionModel
 from .text import DEFAULT_ALPHABET, CharLM
@@ -72,7 +72,7 @@ def main(argv=None):
     with contextlib.redirect_stdout(sys.stderr):  # (the JSON-lines conversion reports itself on stdout, which here carries the one result line)
         truth = read(args.data_dir, train=args.train, max_images=args.max_images, ignore_vertical=args.ignore_vertical)
     split = "train" if args.train else "validation"
-    pages_h = _decode_pages([f"{args.data_dir}/{split}/{t.image_id}.jpg" for t in truth], _read_gray)
+    pages_h = decode_pages([f"{args.data_dir}/{split}/{t.image_id}.jpg" for t in truth], read_gray)
 
     det = DetectionModel().to(device)
     load_model_state(args.det_model, det, device)

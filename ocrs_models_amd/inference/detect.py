@@ -80,7 +80,7 @@ def detect_words(model, page_u8: torch.Tensor, size=MASK_SIZE, threshold: float 
 def pack_pages(pages):
     """A list of (1,H_p,W_p) uint8 device pages -> ``(pages_packed, page_offs, page_sizes)``: the pages back to back in one uint8 buffer
     (one device-to-device copy each), their byte offsets (B,) int64 and their ``(h, w)`` (B,2) int32 on the device -- the layout of the page
-    stores of ``datasets.py``.  No synchronisation."""
+    stores of ``datasets/pages.py``.  No synchronisation."""
     pages = _check_pages(pages, "pack_pages")
     if not pages:
         raise RuntimeError("pack_pages: expected at least one page")

@@ -13,10 +13,9 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import lib, ptr
-from .text import ctc_input_and_target_compatible, round_up
-
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+from ._lib import DT, lib, ptr
+from .augment import AugParams, collate_lines, detection_batch, sample_detection_params, sample_line_params  # noqa: F401
+from .text import collate_plan, line_output_width  # noqa: F401
 
 
 def _need_cuda(t: torch.Tensor, what: str):
@@ -31,13 +30,8 @@ def transform_image(img: torch.Tensor, dtype: torch.dtype = torch.float32) -> to
         raise RuntimeError("transform_image: expected a uint8 image")
     img = img.contiguous()
     out = torch.empty(img.shape, dtype=dtype, device=img.device)
-    lib().transform_image_u8(ptr(img), ptr(out), img.numel(), _DT[dtype])
+    lib().transform_image_u8(ptr(img), ptr(out), img.numel(), DT[dtype])
     return out
-
-
-def line_output_width(line_height: int, line_width: int, output_height: int = 64) -> int:
-    """Width rule of hiertext.py:288-292: scale with the height, at least 10 (never zero-width), at most 800 (bounds batch memory)."""
-    return min(800, max(10, int(output_height * (line_width / line_height))))
 
 
 def resize(img: torch.Tensor, size) -> torch.Tensor:
@@ -68,18 +62,10 @@ def collate_samples(samples: list[dict], device, dtype: torch.dtype = torch.floa
     uint8 images are raw pixels (the kernel applies ``transform_image`` while it pads); float32 images are the reference's
     already-transformed samples.  One packed H2D copy + one kernel, instead of B strided host copies into a 4-byte-per-pixel batch.
     """
-    wmax = round_up(max(s["image"].shape[-1] for s in samples), 256)
-    lmax = round_up(max(s["text_seq"].shape[0] for s in samples), 64)
-    keep = [s for s in samples if ctc_input_and_target_compatible(s["image"].shape[-1] // 4, s["text_seq"])]
+    wmax, kept, meta = collate_plan([s["image"].shape[-1] for s in samples], [s["text_seq"] for s in samples])
+    keep = [samples[k] for k in kept]
     n = len(keep)
     h = keep[0]["image"].shape[1] if keep else 64
-    text = torch.zeros(n, lmax, dtype=torch.int32)
-    tl = torch.zeros(n, dtype=torch.int64)
-    iw = torch.zeros(n, dtype=torch.int64)
-    for i, s in enumerate(keep):
-        L = s["text_seq"].shape[0]
-        text[i, :L] = s["text_seq"]
-        tl[i], iw[i] = L, s["image"].shape[-1]
     image = torch.empty(n, 1, h, wmax, dtype=dtype, device=device)
     if n:
         kinds = {s["image"].dtype for s in keep}
@@ -92,9 +78,6 @@ def collate_samples(samples: list[dict], device, dtype: torch.dtype = torch.floa
         offs = torch.cumsum(sizes, 0) - sizes
         packed_d = packed.to(device, non_blocking=True)
         offs_d = offs.to(device, non_blocking=True)
-        widths_d = iw.to(torch.int32).to(device, non_blocking=True)
-        lib().collate_pad(ptr(packed_d), ptr(offs_d), ptr(widths_d), ptr(image), n, h, wmax, 0 if torch.uint8 in kinds else 1, _DT[dtype])
-    return {"image": image, "text_seq": text, "text_len": tl, "image_width": iw}
-
-
-from .augment import AugParams, collate_lines, detection_batch, sample_detection_params, sample_line_params  # noqa: E402,F401
+        widths_d = meta["image_width"].to(torch.int32).to(device, non_blocking=True)
+        lib().collate_pad(ptr(packed_d), ptr(offs_d), ptr(widths_d), ptr(image), n, h, wmax, 0 if torch.uint8 in kinds else 1, DT[dtype])
+    return {"image": image, **meta}

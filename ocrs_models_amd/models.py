@@ -17,11 +17,11 @@ import math
 import torch
 from torch import nn
 
-from ._lib import lib, ptr
+from ._lib import DT, lib, ptr
 from .packs import EMPTY as EMPTY_PACKS, PackRow, cached_table, dgrad_row, fwd_row
 
 DEPTH_SCALE = [8, 16, 32, 32, 64, 128, 256]  # models.py:112
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = DT  # (the kernel tests read the table under this name)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -137,7 +137,7 @@ class _DetRun:
         whole-network pass (forward / backward need them; the op tests drive single stages without)."""
         self.L = lib()
         self.P, self.Bf, self.names = P, Bf, list(P)
-        self.dev, self.dtype, self.dt, self.N, self.train = dev, dtype, _DT[dtype], N, train
+        self.dev, self.dtype, self.dt, self.N, self.train = dev, dtype, DT[dtype], N, train
         self.mod, self.x = mod, x
         self.recs = {}
         self.fused = {}  # block prefix -> fp64 [2][C] BatchNorm-backward sums accumulated by its consumers' dw_bwd

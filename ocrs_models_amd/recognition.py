@@ -16,8 +16,8 @@ import os
 import torch
 from torch import nn
 
-from ._lib import lib, ptr
-from .models import _DT, _check_versions, _identity_tr
+from ._lib import DT, lib, ptr
+from .models import _check_versions, _identity_tr
 from .packs import EMPTY as EMPTY_PACKS, PackRow, cached_table, conv_dgrad_row, conv_row, dgrad_row, fwd_row
 
 _coef_cache: dict = {}
@@ -56,7 +56,7 @@ class _RecRun:
         whole-network pass (forward / backward need them; the op tests drive single stages without)."""
         self.L = lib()
         self.P, self.Bf, self.names = P, Bf, list(P)
-        self.dev, self.dtype, self.dt, self.N, self.H, self.W, self.train = dev, dtype, _DT[dtype], N, H, W, train
+        self.dev, self.dtype, self.dt, self.N, self.H, self.W, self.train = dev, dtype, DT[dtype], N, H, W, train
         self.mod, self.x = mod, x
         # split-bf16 GEMMs for the fp32 GRU weight gradients in throughput mode, the projections on the pipelined kernel (rec_gemm.hip)
         self.x3 = os.environ.get("OCRS_GRU_X3", "1") != "0"

@@ -640,24 +640,37 @@ def ctc_input_and_target_compatible(input_len: int, target) -> bool:
     return input_len >= need
 
 
-def collate_samples(samples: list[dict], pad_to: int | None = None) -> dict:
-    """list of {'image': (1,64,w) float, 'text_seq': (L,) int32} -> padded batch dict (train_rec.py:248-304).
+def line_output_width(line_height: int, line_width: int, output_height: int = 64) -> int:
+    """Width rule of hiertext.py:288-292: scale with the height, at least 10 (never zero-width), at most 800 (bounds batch memory)."""
+    return min(800, max(10, int(output_height * (line_width / line_height))))
+
+
+def collate_plan(widths, text_seqs, pad_to: int | None = None):
+    """The batch rule of train_rec.py:248-304 without the pixels, for every collate of this package: per-sample image widths and
+    ``text_seq``s -> (padded width, kept positions, {"text_seq", "text_len", "image_width"} host tensors of the kept samples).  The widths
+    are bucketed over every sample (``round_up`` quirk included), then the samples the CTC loss cannot align are dropped.
     ``pad_to`` (extension for the data-parallel path, default None = the reference's behaviour): pad the width at least to this bucket width,
     so that every rank of a step runs the same sequence length (sampler.WidthBucketedDistributedSampler)."""
-    wmax = round_up(max(s["image"].shape[-1] for s in samples), 256)
+    wmax = round_up(max(widths), 256)
     if pad_to is not None:
         wmax = max(wmax, int(pad_to))
-    lmax = round_up(max(s["text_seq"].shape[0] for s in samples), 64)
-    keep = [s for s in samples if ctc_input_and_target_compatible(s["image"].shape[-1] // 4, s["text_seq"])]
+    lmax = round_up(max(t.shape[0] for t in text_seqs), 64)
+    keep = [k for k, t in enumerate(text_seqs) if ctc_input_and_target_compatible(widths[k] // 4, t)]
     n = len(keep)
-    h = keep[0]["image"].shape[1] if keep else 64
-    image = torch.zeros(n, 1, h, wmax, dtype=torch.float32)
     text = torch.zeros(n, lmax, dtype=torch.int32)
     tl = torch.zeros(n, dtype=torch.int64)
     iw = torch.zeros(n, dtype=torch.int64)
-    for i, s in enumerate(keep):
-        w, L = s["image"].shape[-1], s["text_seq"].shape[0]
-        image[i, :, :, :w] = s["image"]
-        text[i, :L] = s["text_seq"]
-        tl[i], iw[i] = L, w
-    return {"image": image, "text_seq": text, "text_len": tl, "image_width": iw}
+    for i, k in enumerate(keep):
+        L = text_seqs[k].shape[0]
+        text[i, :L] = text_seqs[k]
+        tl[i], iw[i] = L, widths[k]
+    return wmax, keep, {"text_seq": text, "text_len": tl, "image_width": iw}
+
+
+def collate_samples(samples: list[dict], pad_to: int | None = None) -> dict:
+    """list of {'image': (1,64,w) float, 'text_seq': (L,) int32} -> padded batch dict (train_rec.py:248-304); ``pad_to``: see ``collate_plan``."""
+    wmax, keep, meta = collate_plan([s["image"].shape[-1] for s in samples], [s["text_seq"] for s in samples], pad_to)
+    image = torch.zeros(len(keep), 1, samples[keep[0]]["image"].shape[1] if keep else 64, wmax, dtype=torch.float32)
+    for i, k in enumerate(keep):
+        image[i, :, :, :samples[k]["image"].shape[-1]] = samples[k]["image"]
+    return {"image": image, **meta}

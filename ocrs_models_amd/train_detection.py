@@ -2,7 +2,7 @@
 H2D copy, forward, balanced BCE, zero_grad, backward, Adam step -- without the per-step ``loss.item()`` host syncs
 (the loss stays a device scalar; callers read it when they need it) -- and the validation loop ``test()``
 (ocrs_models/train_detection.py:144-195): eval-mode forward (running-statistics BatchNorm) + the same loss.  ``main`` is the reference's
-training script (train_detection.py:293-489) on the device-resident datasets of ocrs_models_amd/datasets.py."""
+training script (train_detection.py:293-489) on the device-resident datasets of ocrs_models_amd/datasets/."""
 from __future__ import annotations
 
 import os

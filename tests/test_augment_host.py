@@ -81,9 +81,9 @@ def test_fixed_seed_gives_identical_records():
         a = sampler(sizes, torch.Generator().manual_seed(5), random.Random(5))
         b = sampler(sizes, torch.Generator().manual_seed(5), random.Random(5))
         w = [100] * len(sizes)
-        assert np.array_equal(A._records(a, line, w), A._records(b, line, w))
+        assert np.array_equal(A.records(a, line, w), A.records(b, line, w))
         c = sampler(sizes, torch.Generator().manual_seed(6), random.Random(6))
-        assert not np.array_equal(A._records(a, line, w), A._records(c, line, w))
+        assert not np.array_equal(A.records(a, line, w), A.records(c, line, w))
 
 
 def test_default_generators_are_used():
@@ -125,7 +125,7 @@ def test_host_maths_match_comparand():
 
 def test_records_layout():
     p = A.sample_detection_params([(1200, 1600)], torch.Generator().manual_seed(0), random.Random(0))
-    rec = A._records(p, False)
+    rec = A.records(p, False)
     assert rec.shape == (1, A.REC_WORDS) and rec.dtype == np.int32
     from ocrs_models_amd._lib import SIGNATURES
 

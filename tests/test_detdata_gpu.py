@@ -1,4 +1,4 @@
-"""The detection datasets on the GPU (ocrs_models_amd/datasets.py, csrc/page_data.hip): the shrink kernel against its host restatement, page
+"""The detection datasets on the GPU (ocrs_models_amd/datasets/pages.py, csrc/page_data.hip): the shrink kernel against its host restatement, page
 masks against PIL fed the restatement's float vertices (tests/detdata_ref.py), batches and items against the existing ``detection_batch``
 fed host pages and reference masks, train steps from the loader, and the training command line end to end on a tiny tree.  Everything
 short of the model runs at ``mask_size=(64, 48)``; the train steps run at (64, 64), the smallest size ``DetectionModel`` accepts.

@@ -1,4 +1,4 @@
-"""The detection datasets without a GPU (ocrs_models_amd/datasets.py HierText / DDI100 / DevicePageLoader, train_detection.main): the shrink
+"""The detection datasets without a GPU (ocrs_models_amd/datasets/ HierText / DDI100 / DevicePageLoader, train_detection.main): the shrink
 rule's known answers on the host restatement the kernel mirrors (tests/detdata_ref.py), PIL's conversion of float vertices, the dataset
 files and selection rules, and the command line.  The shrink tests run on the restatement alone: they pin, by answers derivable by hand,
 the rule that tests/test_detdata_gpu.py holds the kernel to, case by case."""

@@ -1,4 +1,4 @@
-"""The recognition dataset on the GPU (ocrs_models_amd/datasets.py, csrc/line_data.hip): the polygon-mask kernel against PIL, items and
+"""The recognition dataset on the GPU (ocrs_models_amd/datasets/hiertext.py, csrc/line_data.hip): the polygon-mask kernel against PIL, items and
 batches against the host restatement (tests/hiertext_ref.py) fed through the existing ``collate_lines``, the crop cache, the bucketed
 sampler, the training CLI end to end on a tiny tree, and the data-parallel hook on a 1-rank RCCL group.
 

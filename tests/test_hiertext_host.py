@@ -1,4 +1,4 @@
-"""CPU-only checks of the recognition dataset's host side (ocrs_models_amd/datasets.py): the line-annotation filter against a hand-written
+"""CPU-only checks of the recognition dataset's host side (ocrs_models_amd/datasets/hiertext.py): the line-annotation filter against a hand-written
 lines file, the regeneration rule, and the pin of tests/hiertext_ref.polygon_mask -- the restatement csrc/line_data.hip was ported from --
 to the installed PIL on the polygon families the GPU test uses."""
 from __future__ import annotations

@@ -1,4 +1,4 @@
-"""The device-resident layout dataset on the GPU (ocrs_models_amd/datasets.py, csrc/layout_data.hip): items against the reference's recorded
+"""The device-resident layout dataset on the GPU (ocrs_models_amd/datasets/web_layout.py, csrc/layout_data.hip): items against the reference's recorded
 outputs, batches against a stock DataLoader over the CPU restatement (tests/weblayout_ref.py), the training CLI end to end on a small
 directory, and the data-parallel hook of the layout backward on a 1-rank RCCL group.
 

@@ -1,4 +1,4 @@
-"""CPU checks of the layout dataset (ocrs_models_amd/datasets.py): the restatement the GPU tests compare against equals the reference's
+"""CPU checks of the layout dataset (ocrs_models_amd/datasets/web_layout.py): the restatement the GPU tests compare against equals the reference's
 recorded items; file selection, load-time refusals and the random stream of DeviceWebLayoutLoader need no GPU; the CLI parses and refuses
 to run without one."""
 import itertools
