@@ -392,43 +392,7 @@ struct TileSched {
     }
 };
 
-#include <stdlib.h>
-#include <atomic>
-// "done once per device" flag for hipFuncSetAttribute(MaxDynamicSharedMemorySize): the attribute is per device, launchers run on the forward
-// and on the autograd thread (setting it twice is harmless, skipping it on a second device is not)
-struct DevOnce {
-    std::atomic<unsigned long long> mask{0};
-    static unsigned long long bit() {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        return 1ull << (dev & 63);
-    }
-    bool need() const { return !(mask.load(std::memory_order_relaxed) & bit()); }
-    void done() { mask.fetch_or(bit(), std::memory_order_relaxed); }
-};
-// The ABI's dtype (0 = fp32, 1 = bf16) as a type: f(T{}) with T = float or bf16, for launchers whose two branches differ in nothing else
-//   with_dtype(dtype, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(k<T>, ..., (const T*)x, ...); });
-template <class F>
-static inline auto with_dtype(int dtype, F&& f) {
-    return dtype == 1 ? f(bf16{}) : f(float{});
-}
-// Per-launch timestamps from the dispatch packet (csrc/prof.hip): OCRS_LAUNCH_T == hipLaunchKernelGGL unless ocrs_prof_enable(1)
-struct OcrsProf {
-    int on, used, cap;
-    hipEvent_t* ev;  // [2 * cap]: start / stop pairs
-};
-OcrsProf& ocrs_prof();
-#define OCRS_LAUNCH_T(kernel, grid, block, smem, st, ...)                                                   \
-    do {                                                                                                    \
-        OcrsProf& pf_ = ocrs_prof();                                                                        \
-        if (pf_.on && pf_.used < pf_.cap) {                                                                 \
-            hipEvent_t e0_ = pf_.ev[2 * pf_.used], e1_ = pf_.ev[2 * pf_.used + 1];                          \
-            ++pf_.used;                                                                                     \
-            hipExtLaunchKernelGGL(kernel, grid, block, smem, st, e0_, e1_, 0, __VA_ARGS__);                 \
-        } else {                                                                                            \
-            hipLaunchKernelGGL(kernel, grid, block, smem, st, __VA_ARGS__);                                 \
-        }                                                                                                   \
-    } while (0)
+#include "launch.h"
 
 // grid of an element-wise pass: one thread per item, at most 8 blocks of 256 per CU (the kernels loop)
 static inline int ew_grid(long items) {

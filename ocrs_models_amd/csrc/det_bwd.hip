@@ -1219,13 +1219,7 @@ static int launch_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const f
     constexpr int TPP = Elem<T>::is_bf16 ? Cfg::TPP_BF : Cfg::TPP_F;
     const size_t smem = (((Cfg::TP * Mma<T>::LDS_PITCH + Cfg::mid_el(TPP)) * sizeof(T) + 15) & ~15) +
                         (Cfg::HP * Cfg::CGI * 8 + 12 * CIN + 6 * COUT) * sizeof(float);
-    static DevOnce attr_set;
-    if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pw_bwd<T, CIN, COUT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-            hipSuccess)
-            return OCRS_ERR_HIP;
-        attr_set.done();
-    }
+    if (int rc = dyn_lds<&k_pw_bwd<T, CIN, COUT>>(160 * 1024)) return rc;
     Src2<T> x{(const T*)xa, (const T*)xb, Ca, Cb};
     GradSrc<T> gs{(const T*)g1, (const T*)g2, pooled};
     const Tiling2 tg = make_tiling2(N, H, W, Cfg::TW, Cfg::TH);
@@ -1527,23 +1521,21 @@ int ocrs_convt_bwd_parts(const void* x, const float* tr, const void* g, const vo
     OCRS_CHECK_ARG(!gsum || (saved && ws && ocrs_convt_bwd_stats_supported(Cup, Cout, dtype)));
     if (ws && convt_wgrad_tr_ok(Cup, Cout, dtype)) {
         // levels 0-2 (bf16): ONE tiled kernel produces dx, the weight-gradient partials and the bias-gradient partials; one reduce
-#define CTW_CASE(CU_, CO_)                                                                                                                   \
-    if (Cup == CU_ && Cout == CO_) {                                                                                                         \
-        using CC = CtwCfg<CU_, CO_>;                                                                                                         \
-        const Tiling2 tg = make_tiling2(N, h, w, CC::TW, CC::TH);                                                                            \
-        const int nb = convt_wgrad_tr_grid(Cout, N, h, w);                                                                                   \
-        if (gsum)                                                                                                                            \
-            hipLaunchKernelGGL((k_convt_wgrad_tr<CU_, CO_, true>), dim3(nb), dim3(256), CC::SMEM, st, (const bf16*)x, tr, (const bf16*)g, wpk_d,   \
-                               (bf16*)dx, ws, saved, h, w, H, W, tg);                                                                        \
-        else                                                                                                                                 \
-            hipLaunchKernelGGL((k_convt_wgrad_tr<CU_, CO_, false>), dim3(nb), dim3(256), CC::SMEM, st, (const bf16*)x, tr, (const bf16*)g, wpk_d,  \
-                               (bf16*)dx, ws, saved, h, w, H, W, tg);                                                                        \
-        const int ne = CU_ * 9 * CO_ + CO_ + (gsum ? 2 * CU_ : 0);                                                                           \
-        hipLaunchKernelGGL(k_convt_wgrad_reduce, dim3((ne + 31) / 32), dim3(256), 0, st, ws, nb, CU_, CO_, CC::NT * 16, dW, \
-                           dbias, saved, gsum);                                                                                              \
-    }
-        CTW_CASE(16, 8) CTW_CASE(32, 16) CTW_CASE(32, 32)
-#undef CTW_CASE
+        const bool hit = with_int<1608, 3216, 3232>(100 * Cup + Cout, [&](auto k) {  // (Cup, Cout)
+            constexpr int CU = k() / 100, CO = k() % 100;
+            using CC = CtwCfg<CU, CO>;
+            const Tiling2 tg = make_tiling2(N, h, w, CC::TW, CC::TH);
+            const int nb = convt_wgrad_tr_grid(Cout, N, h, w);
+            with_bools(
+                [&](auto stats) {
+                    hipLaunchKernelGGL((k_convt_wgrad_tr<CU, CO, stats()>), dim3(nb), dim3(256), CC::SMEM, st, (const bf16*)x, tr, (const bf16*)g, wpk_d, (bf16*)dx, ws,
+                                       saved, h, w, H, W, tg);
+                },
+                gsum != nullptr);
+            const int ne = CU * 9 * CO + CO + (gsum ? 2 * CU : 0);
+            hipLaunchKernelGGL(k_convt_wgrad_reduce, dim3((ne + 31) / 32), dim3(256), 0, st, ws, nb, CU, CO, CC::NT * 16, dW, dbias, saved, gsum);
+        });
+        if (!hit) return OCRS_ERR_ARG;
         OCRS_LAUNCH_CHECK();
         return OCRS_OK;
     }
@@ -1555,27 +1547,14 @@ int ocrs_convt_bwd_parts(const void* x, const float* tr, const void* g, const vo
         const int rc = det_ctd_launch(g, wpk_d, dx, Cup, Cout, N, h, w, H, W, st, x, tr, saved, gsum);  // (gsum: + the producer block's BatchNorm-backward sums)
         if (rc != OCRS_OK) return rc;
     } else if (parts & 1) {
-#define DG_CASE(T_, MT_)                                                                                                                     \
-    hipLaunchKernelGGL((k_convt_dgrad<T_, MT_>), dim3(gx, MT_total / MT_), dim3(256), 0, st, (const T_*)g, wpk_d, (T_*)dx, Cup, Cout, h, w, H, \
-                       W, N, MT_total);
-#define DG_DISPATCH(T_)               \
-    if (MT_total % 8 == 0) {          \
-        DG_CASE(T_, 8)                \
-    } else if (MT_total % 4 == 0) {   \
-        DG_CASE(T_, 4)                \
-    } else if (MT_total % 2 == 0) {   \
-        DG_CASE(T_, 2)                \
-    } else {                          \
-        DG_CASE(T_, 1)                \
-    }
-    if (dtype == 1) {
-        DG_DISPATCH(bf16)
-    } else {
-        DG_DISPATCH(float)
-    }
-#undef DG_DISPATCH
-#undef DG_CASE
-    OCRS_LAUNCH_CHECK();
+        const int mt = MT_total % 8 == 0 ? 8 : (MT_total % 4 == 0 ? 4 : (MT_total % 2 == 0 ? 2 : 1));  // 16-channel tiles per block
+        with_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            with_int<8, 4, 2, 1>(mt, [&](auto m) {
+                hipLaunchKernelGGL((k_convt_dgrad<T, m()>), dim3(gx, MT_total / m()), dim3(256), 0, st, (const T*)g, wpk_d, (T*)dx, Cup, Cout, h, w, H, W, N, MT_total);
+            });
+        });
+        OCRS_LAUNCH_CHECK();
     }
     if (!(parts & 2)) return OCRS_OK;
     if (ws && det_rs32_ctw_supported(Cup, Cout, dtype) && (long)N * H * W * Cout * 4 < (1L << 32) && (long)N * h * w * Cup * 4 < (1L << 32))

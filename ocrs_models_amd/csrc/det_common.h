@@ -574,6 +574,17 @@ struct BwdLast {
 };
 constexpr int BWD_LAST_SLOTS = 8;  // replicas of the raw sums, by workgroup index: same-address atomics serialise at the memory side (~15 ns each; 768 workgroups
                                    // finishing together on one replica cost as much as the launch this replaces)
+// The scratch of one launch (zeroed fp64, left zeroed): the replicated sums, the counter word behind them.  bwd_last() carves it; scratch == null or
+// !want: off.  (mode 0; where the scratch comes from, and what a launcher does without one, is the launcher's business)
+constexpr int bwd_last_doubles(int Cin) { return BWD_LAST_SLOTS * 2 * Cin + 2; }
+static inline BwdLast bwd_last(bool want, int Cin, int Ca, double* gsA, double* gsB, const float* svA, const float* svB, double* scratch) {
+    BwdLast bl{nullptr, nullptr, gsA, gsB, svA, svB, Ca, 0};
+    if (want && scratch) {
+        bl.raw = scratch;
+        bl.counter = reinterpret_cast<unsigned*>(scratch + BWD_LAST_SLOTS * 2 * Cin);
+    }
+    return bl;
+}
 __device__ __forceinline__ void bwd_last_add(const BwdLast& bl, int CIN, int c, int which, float v) {
     atomicAdd(bl.raw + ((blockIdx.x + blockIdx.y) & (BWD_LAST_SLOTS - 1)) * 2 * CIN + which * CIN + c, (double)v);
 }

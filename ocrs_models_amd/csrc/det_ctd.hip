@@ -168,15 +168,8 @@ int det_ctd_launch(const void* g, const void* wpk, void* dx, int Cup, int Cout, 
 #define CTD_CASE(CU_, CO_)                                                                                                                  \
     if (Cup == CU_ && Cout == CO_) {                                                                                                        \
         using CC = CtdCfg<CU_, CO_>;                                                                                                        \
-        static DevOnce attr_set;                                                                                                       \
-        if (attr_set.need()) {                                                                                                                    \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctd<CU_, CO_, false>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM) != \
-                    hipSuccess ||                                                                                                           \
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctd<CU_, CO_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM) != \
-                    hipSuccess)                                                                                                             \
-                return OCRS_ERR_HIP;                                                                                                        \
-            attr_set.done();                                                                                                                \
-        }                                                                                                                                   \
+        if (int rc = dyn_lds<&k_ctd<CU_, CO_, false>>(CC::SMEM)) return rc;                                                                 \
+        if (int rc = dyn_lds<&k_ctd<CU_, CO_, true>>(CC::SMEM)) return rc;                                                                  \
         if (gsum)                                                                                                                           \
             hipLaunchKernelGGL((k_ctd<CU_, CO_, true>), dim3((int)gsz), dim3(512), CC::SMEM, st, (const bf16*)g, wpk, (bf16*)dx, h, w, H, W, N, \
                                (const bf16*)x, tr, saved, gsum);                                                                            \

@@ -145,13 +145,7 @@ int det_ctf_launch(const void* x, const float* tr, const void* wpk, const float*
 #define CTF2_CASE(CU_, CO_)                                                                                                                 \
     if (Cup == CU_ && Cout == CO_) {                                                                                                        \
         using CC = CtfCfg<CU_, CO_>;                                                                                                        \
-        static DevOnce attr_set;                                                                                                       \
-        if (attr_set.need()) {                                                                                                                    \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ctf<CU_, CO_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM) != \
-                hipSuccess)                                                                                                                 \
-                return OCRS_ERR_HIP;                                                                                                        \
-            attr_set.done();                                                                                                                \
-        }                                                                                                                                   \
+        if (int rc = dyn_lds<&k_ctf<CU_, CO_>>(CC::SMEM)) return rc;                                                                        \
         hipLaunchKernelGGL((k_ctf<CU_, CO_>), dim3((int)g), dim3(512), CC::SMEM, st, (const bf16*)x, tr, wpk, bias, (bf16*)out, h, w, H, W, N); \
     }
     CTF2_CASE(256, 128) CTF2_CASE(128, 64) CTF2_CASE(64, 32)

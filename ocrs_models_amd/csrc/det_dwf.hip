@@ -221,13 +221,7 @@ int det_dwf_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
 #define DWF_CASE(CI_, CO_)                                                                                                                   \
     if (!done && Cin == CI_ && Cout == CO_) {                                                                                                \
         using CC = DwfCfg<CI_, CO_>;                                                                                                         \
-        static DevOnce attr_set;                                                                                                        \
-        if (attr_set.need()) {                                                                                                                     \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dwf<CI_, CO_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM) != \
-                hipSuccess)                                                                                                                  \
-                return OCRS_ERR_HIP;                                                                                                         \
-            attr_set.done();                                                                                                                 \
-        }                                                                                                                                    \
+        if (int rc = dyn_lds<&k_dwf<CI_, CO_>>(CC::SMEM)) return rc;                                                                         \
         const Tiling2 tg = make_tiling2(N, H, W, CC::TW, CC::TH);                                                                            \
         long g = tg.ntiles;                                                                                                                  \
         const long cap = (long)kNumCU * (CI_ <= 128 ? 2 : 1); /* resident blocks (<= 128 registers up to 128 input channels) */                                                                \

@@ -841,53 +841,34 @@ static int mm_bwd_th(int Cin, int Cout, int pooled) {  // = MmCfg<Cin, Cout, poo
     return (Cin == 16 && Cout == 16 && !pooled) ? 8 : 12;
 }
 
-template <int CIN, int COUT, bool PPOOL, bool G2, bool STATS>
-static void mm_bwd_launch1(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, int ldw, const bf16* g1, const bf16* g2,
-                           const bf16* z, const float* bn, const float* coef, bf16* gxa, bf16* gxb, float* ws, int N, int H, int W, int nb, const BnFin& fin,
-                           const BwdLast& bl, hipStream_t st) {
-    using CC = MmCfg<CIN, COUT, PPOOL>;
-    Tiling2 tg = make_tiling2(N, H + (PPOOL ? 1 : 0), W + (PPOOL ? 1 : 0), CC::TW, CC::TH);  // pooled: origins shifted by -1 -> one more row / column of tiles may be needed
-    tg.H = H;
-    tg.W = W;
-    // (the attribute is set per call: it is per device, this runs on any thread, and it is a cheap host-side update -- ADVICE r02)
-    if constexpr (!PPOOL) {
-        if (W % CC::TW == 0) {  // every tile COLUMN inside the image: unconditional stores + hand-written prefetch waits
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);
-            OCRS_LAUNCH_T((k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, ldw, g1, g2, z, bn, coef,
-                          gxa, gxb, ws, tg, fin, bl);
-            return;
-        }
-    }
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);
-    OCRS_LAUNCH_T((k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, false>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, ldw, g1, g2, z, bn, coef, gxa, gxb,
-                  ws, tg, fin, bl);
-}
-
+// one k_mm_bwd launch; FULL (never with pooling): every tile COLUMN inside the image -> unconditional stores + hand-written prefetch waits
 template <int CIN, int COUT>
-static void mm_bwd_dispatch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, int ldw, const bf16* g1, const bf16* g2,
-                            int pooled, const bf16* z, const float* bn, const float* coef, bf16* gxa, bf16* gxb, float* ws, bool stats, int N, int H, int W,
-                            int nb, const BnFin& fin, const BwdLast& bl, hipStream_t st) {
-#define MMB(PP, GG, SS) mm_bwd_launch1<CIN, COUT, PP, GG, SS>(x, tra, trb, wdw, wpw, ldw, g1, g2, z, bn, coef, gxa, gxb, ws, N, H, W, nb, fin, bl, st)
-    if (pooled) {
-        if (g2) { if (stats) MMB(true, true, true); else MMB(true, true, false); }
-        else    { if (stats) MMB(true, false, true); else MMB(true, false, false); }
-    } else {
-        if (g2) { if (stats) MMB(false, true, true); else MMB(false, true, false); }
-        else    { if (stats) MMB(false, false, true); else MMB(false, false, false); }
-    }
-#undef MMB
+static int mm_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, int ldw, const bf16* g1, const bf16* g2,
+                         int pooled, const bf16* z, const float* bn, const float* coef, bf16* gxa, bf16* gxb, float* ws, bool stats, int N, int H, int W, int nb,
+                         const BnFin& fin, const BwdLast& bl, hipStream_t st) {
+    const bool full = !pooled && W % MmCfg<CIN, COUT, false>::TW == 0;
+    return with_bools(
+        [&](auto pp, auto gg, auto ss, auto fu) {
+            constexpr bool PPOOL = pp(), G2 = gg(), STATS = ss(), FULL = fu();
+            if constexpr (PPOOL && FULL) {
+                return OCRS_ERR_ARG;
+            } else {
+                using CC = MmCfg<CIN, COUT, PPOOL>;
+                Tiling2 tg = make_tiling2(N, H + (PPOOL ? 1 : 0), W + (PPOOL ? 1 : 0), CC::TW, CC::TH);  // pooled: origins shifted by -1 -> one more row / column of tiles may be needed
+                tg.H = H;
+                tg.W = W;
+                if (int rc = dyn_lds<&k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, FULL>>(CC::SMEM)) return rc;
+                OCRS_LAUNCH_T((k_mm_bwd<CIN, COUT, PPOOL, G2, STATS, FULL>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, ldw, g1, g2, z, bn, coef,
+                              gxa, gxb, ws, tg, fin, bl);
+                return OCRS_OK;
+            }
+        },
+        pooled != 0, g2 != nullptr, stats, full);
 }
 
 // in-kernel finalisation state for one block-backward launch (off: raw = null) and the launch's second stage
 static BwdLast mm_bwd_last(bool want, int Cin, int Ca, double* gsA, double* gsB, const float* svA, const float* svB) {
-    BwdLast bl{nullptr, nullptr, gsA, gsB, svA, svB, Ca, 0};
-    if (!want) return bl;
-    double* p = bwd_defer_scratch(BWD_LAST_SLOTS * 2 * Cin + 2);
-    if (p) {
-        bl.raw = p;
-        bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
-    }
-    return bl;
+    return bwd_last(want, Cin, Ca, gsA, gsB, svA, svB, want ? bwd_defer_scratch(bwd_last_doubles(Cin)) : nullptr);  // (no window: the reduce runs in line)
 }
 static void mm_bwd_second_stage(const float* ws, int nb, int Cin, int Cout, int Ca, float* dwpw, int ldw, float* dwdw, double* gsA, double* gsB, const float* svA,
                                 const float* svB, const float* tA, const float* tB, const BwdLast& bl, bool may_defer, hipStream_t st) {
@@ -959,13 +940,16 @@ static int mm_bwd_impl(const void* xa, const void* xb, int Ca, int Cb, const flo
         float* const ws_full = ws;
         ws = ws_full + (size_t)part * nb * (Cout * Cin + 11 * Cin + 1024);
         const BwdLast bl = mm_bwd_last(stats, Cin, x.Ca, gsA, gsB, svA, svB);
-        if (rs) rs_bwd_launch(x, tA, tB, wd, wp, CinTot, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, coef, ga, gb, ws, stats, Cout, N, H, W, fin, st, nullptr, nullptr,
-                              nullptr, nullptr, bl);
-#define MM_CASE(CI_, CO_)                                                                                                             \
-    if (!rs && Cin == CI_ && Cout == CO_)                                                                                             \
-        mm_bwd_dispatch<CI_, CO_>(x, tA, tB, wd, wp, CinTot, (const bf16*)g1, (const bf16*)g2, pooled, (const bf16*)z, bn, coef, ga, gb, ws, stats, N, H, W, nb, fin, bl, st);
-        MM_CASE(8, 8) MM_CASE(8, 16) MM_CASE(16, 8) MM_CASE(16, 16) MM_CASE(16, 32) MM_CASE(32, 16) MM_CASE(32, 32)
-#undef MM_CASE
+        int rc = OCRS_ERR_ARG;
+        if (rs)
+            rc = rs_bwd_launch(x, tA, tB, wd, wp, CinTot, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, coef, ga, gb, ws, stats, Cout, N, H, W, fin, st, nullptr,
+                               nullptr, nullptr, nullptr, bl);
+        else
+            with_int<808, 816, 1608, 1616, 1632, 3216, 3232>(100 * Cin + Cout, [&](auto k) {  // (Cin, Cout) of the instantiations
+                rc = mm_bwd_launch<k() / 100, k() % 100>(x, tA, tB, wd, wp, CinTot, (const bf16*)g1, (const bf16*)g2, pooled, (const bf16*)z, bn, coef, ga, gb, ws, stats,
+                                                         N, H, W, nb, fin, bl, st);
+            });
+        if (rc != OCRS_OK) return rc;
         mm_bwd_second_stage(ws, nb, Cin, Cout, x.Ca, dwpw + c_off, CinTot, dwdw + c_off * 9, gsA, gsB, svA, svB, tA, tB, bl, true, st);
         ws = ws_full;
     }
@@ -986,8 +970,8 @@ int ocrs_mm_bwd_fin_head(const void* xa, int Ca, const float* tra, const float* 
     Src2<bf16> x{(const bf16*)xa, nullptr, Ca, 0};
     const int nb = rs_bwd_blocks(Ca, Cout, N, H, W, 0);
     const BwdLast bl = mm_bwd_last(gsum_a != nullptr, Ca, Ca, gsum_a, nullptr, saved_a, nullptr);
-    rs_bwd_launch(x, tra, nullptr, wdw, wpw, Ca, nullptr, nullptr, (const bf16*)z, bn, nullptr, (bf16*)gxa, nullptr, ws, gsum_a != nullptr, Cout, N, H, W, fin, st, gl,
-                  whead, nullptr, nullptr, bl);
+    if (int rc = rs_bwd_launch(x, tra, nullptr, wdw, wpw, Ca, nullptr, nullptr, (const bf16*)z, bn, nullptr, (bf16*)gxa, nullptr, ws, gsum_a != nullptr, Cout, N, H, W, fin, st, gl,
+                      whead, nullptr, nullptr, bl)) return rc;
     mm_bwd_second_stage(ws, nb, Ca, Cout, Ca, dwpw, Ca, dwdw, gsum_a, nullptr, saved_a, nullptr, tra, nullptr, bl, true, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
@@ -1004,8 +988,8 @@ int ocrs_mm_bwd_fin_xu(const void* xu, const float* wexp, const float* tra, cons
     Src2<bf16> x{nullptr, nullptr, 8, 0};
     const int nb = rs_bwd_blocks(8, Cout, N, H, W, g2 != nullptr);
     const BwdLast bl = mm_bwd_last(gsum_a != nullptr, 8, 8, gsum_a, nullptr, saved_a, nullptr);
-    rs_bwd_launch(x, tra, nullptr, wdw, wpw, 8, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, nullptr, (bf16*)gxa, nullptr, ws, gsum_a != nullptr, Cout, N, H, W,
-                  fin, st, nullptr, nullptr, (const bf16*)xu, wexp, bl);
+    if (int rc = rs_bwd_launch(x, tra, nullptr, wdw, wpw, 8, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, nullptr, (bf16*)gxa, nullptr, ws, gsum_a != nullptr, Cout, N, H, W,
+                      fin, st, nullptr, nullptr, (const bf16*)xu, wexp, bl)) return rc;
     mm_bwd_second_stage(ws, nb, 8, Cout, 8, dwpw, 8, dwdw, gsum_a, nullptr, saved_a, nullptr, tra, nullptr, bl, true, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
@@ -1024,8 +1008,8 @@ int ocrs_mm_bwd_fin_xu_c1(const void* xu, const float* wexp, const float* tra, c
     Src2<bf16> x{nullptr, nullptr, 8, 0};
     const int nb = rs_bwd_blocks(8, Cout, N, H, W, g2 != nullptr);
     const BwdLast bl = mm_bwd_last(gsum_a != nullptr, 8, 8, gsum_a, nullptr, saved_a, nullptr);
-    rs_bwd_launch(x, tra, nullptr, wdw, wpw, 8, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, nullptr, nullptr, nullptr, ws, gsum_a != nullptr, Cout, N, H, W,
-                  fin, st, nullptr, nullptr, (const bf16*)xu, wexp, bl, img, c1acc);
+    if (int rc = rs_bwd_launch(x, tra, nullptr, wdw, wpw, 8, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, nullptr, nullptr, nullptr, ws, gsum_a != nullptr, Cout, N, H, W,
+                      fin, st, nullptr, nullptr, (const bf16*)xu, wexp, bl, img, c1acc)) return rc;
     mm_bwd_second_stage(ws, nb, 8, Cout, 8, dwpw, 8, dwdw, gsum_a, nullptr, saved_a, nullptr, tra, nullptr, bl, true, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
@@ -1489,35 +1473,23 @@ __global__ __launch_bounds__(256) void k_bn_finalize_parts(const float* __restri
 }
 
 template <int CINB, int NST, int COUT>
-static void mm_fwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, bf16* z, float* ws, const float* gamma,
-                          bf16* pooled, int N, int H, int W, int nb, const FwdFin& fin, hipStream_t st, const XuSrc& xu = XuSrc{nullptr, nullptr}) {
+static int mm_fwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, bf16* z, float* ws, const float* gamma,
+                         bf16* pooled, int N, int H, int W, int nb, const FwdFin& fin, hipStream_t st, const XuSrc& xu = XuSrc{nullptr, nullptr}) {
     using CC = MfCfg<CINB, NST, COUT>;
     const Tiling2 tg = make_tiling2(N, H, W, CC::TW, CC::TH);
-    // (set per call: the attribute is per device and this is called from any thread; it is a cheap host-side table update)
     const bool full = H % CC::TH == 0 && W % CC::TW == 0 && (!pooled || ((H | W) & 1) == 0);
-#define MF_LAUNCH(PO_, FU_)                                                                                                                          \
-    {                                                                                                                                                \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mm_fwd<CINB, NST, COUT, PO_, FU_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM); \
-        hipLaunchKernelGGL((k_mm_fwd<CINB, NST, COUT, PO_, FU_>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, z, ws, tg, gamma, pooled, fin, xu); \
-    }
-    if constexpr (CINB == 8 && NST == 1) {
-        if (xu.u) {  // the block behind the first block (never pooled)
-#define MF_LAUNCH_XU(FU_)                                                                                                                                 \
-    {                                                                                                                                                     \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mm_fwd<CINB, NST, COUT, false, FU_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM); \
-        hipLaunchKernelGGL((k_mm_fwd<CINB, NST, COUT, false, FU_, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, z, ws, tg, gamma, pooled, fin, xu); \
-    }
-            if (full) MF_LAUNCH_XU(true) else MF_LAUNCH_XU(false)
-#undef MF_LAUNCH_XU
-            return;
-        }
-    }
-    if (pooled) {
-        if (full) MF_LAUNCH(true, true) else MF_LAUNCH(true, false)
-    } else {
-        if (full) MF_LAUNCH(false, true) else MF_LAUNCH(false, false)
-    }
-#undef MF_LAUNCH
+    return with_bools(
+        [&](auto po, auto fu, auto u) {
+            constexpr bool PO = po(), FU = fu(), XU = u();  // XU: the block behind the first block (8 -> COUT, never pooled)
+            if constexpr (XU && (PO || CINB != 8 || NST != 1)) {
+                return OCRS_ERR_ARG;
+            } else {
+                if (int rc = dyn_lds<&k_mm_fwd<CINB, NST, COUT, PO, FU, XU>>(CC::SMEM)) return rc;
+                hipLaunchKernelGGL((k_mm_fwd<CINB, NST, COUT, PO, FU, XU>), dim3(nb), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, wpw, z, ws, tg, gamma, pooled, fin, xu);
+                return OCRS_OK;
+            }
+        },
+        pooled != nullptr && !xu.u, full, xu.u != nullptr);
 }
 
 extern "C" {
@@ -1549,14 +1521,16 @@ static int mm_fwd_impl(const void* xa, const void* xb, int Ca, int Cb, const flo
     Src2<bf16> x{(const bf16*)xa, (const bf16*)xb, Ca, Cb};
     const int nb = (int)ocrs_mm_fwd_nparts(Ca, Cb, Cout, N, H, W);
     if (!pooled && rs_fwd_supported(Ca, Cb, Cout, N, H, W)) {  // the row-streaming kernel (det_rs.hip)
-        rs_fwd_launch(x, xu.u, xu.wexp, tra, trb, wdw, wpw, (bf16*)z, ws, Cout, N, H, W, nb, fin, st);
+        if (int rc = rs_fwd_launch(x, xu.u, xu.wexp, tra, trb, wdw, wpw, (bf16*)z, ws, Cout, N, H, W, nb, fin, st)) return rc;
         OCRS_LAUNCH_CHECK();
         return OCRS_OK;
     }
-#define MF_CASE(CB_, NS_, CO_) \
-    if (Cin == CB_ * NS_ && Cout == CO_ && (NS_ == 1 || Ca == 32)) mm_fwd_launch<CB_, NS_, CO_>(x, tra, trb, wdw, wpw, (bf16*)z, ws, gamma, (bf16*)pooled, N, H, W, nb, fin, st, xu);
-    MF_CASE(8, 1, 8) MF_CASE(8, 1, 16) MF_CASE(16, 1, 8) MF_CASE(16, 1, 16) MF_CASE(16, 1, 32) MF_CASE(32, 1, 16) MF_CASE(32, 1, 32) MF_CASE(32, 2, 32)
-#undef MF_CASE
+    int rc = OCRS_ERR_ARG;
+    const int nst = (Ca == 32 && Cb == 32) ? 2 : 1;  // a 32 | 32 concat input: two 32-channel sets
+    with_int<10808, 10816, 11608, 11616, 11632, 13216, 13232, 23232>(10000 * nst + 100 * (Cin / nst) + Cout, [&](auto k) {  // (sets, channels per set, Cout)
+        rc = mm_fwd_launch<k() / 100 % 100, k() / 10000, k() % 100>(x, tra, trb, wdw, wpw, (bf16*)z, ws, gamma, (bf16*)pooled, N, H, W, nb, fin, st, xu);
+    });
+    if (rc != OCRS_OK) return rc;
     if (fin.counter && Cin == 16 && Cout == 8)  // (see mm_fwd_fink: this shape's statistics are finalised by their own launch)
         hipLaunchKernelGGL(k_bn_finalize_parts, dim3((2 * Cout + 31) / 32), dim3(256), 0, st, ws, nb, fin.count, Cout, fin.gamma, fin.beta, fin.eps, fin.momentum,
                            fin.tr, fin.saved, fin.run_mean, fin.run_var, fin.nbt, fin.lo);

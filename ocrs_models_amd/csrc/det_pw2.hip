@@ -280,19 +280,18 @@ int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
     OCRS_CHECK_ARG(det_pw2_supported(Cin, Cout, 1) && Ca % 8 == 0 && Cb % 8 == 0 && (long)N * H * W < (1L << 31));
     Src2<bf16> x{(const bf16*)xa, (const bf16*)xb, Ca, Cb};
     const int nb = pw2_grid(Cin, Cout, N, H, W);
-#define PW2_CASE(CI_, CO_)                                                                                                                  \
-    if (Cin == CI_ && Cout == CO_) {                                                                                                        \
-        using CC = Pw2Cfg<CI_, CO_>;                                                                                                        \
-        const Tiling2 tg = make_tiling2(N, H, W, CC::TW, CC::TH);                                                                           \
-        if (pooled)                                                                                                                         \
-            OCRS_LAUNCH_T((k_pw_bwd2<CI_, CO_, true>), dim3(nb), dim3(256), CC::SMEM, st, x, tra, trb, wdw, (const bf16*)g1, (const bf16*)g2, \
-                               (const bf16*)z, bn, coef, wpk_d, (bf16*)du, dwpw, ws, tg, ldu, ldw);                                                   \
-        else                                                                                                                                \
-            OCRS_LAUNCH_T((k_pw_bwd2<CI_, CO_, false>), dim3(nb), dim3(256), CC::SMEM, st, x, tra, trb, wdw, (const bf16*)g1, (const bf16*)g2, \
-                               (const bf16*)z, bn, coef, wpk_d, (bf16*)du, dwpw, ws, tg, ldu, ldw);                                                   \
-    }
-    PW2_CASE(8, 8) PW2_CASE(8, 16) PW2_CASE(16, 8) PW2_CASE(16, 16) PW2_CASE(16, 32) PW2_CASE(32, 16) PW2_CASE(32, 32)
-#undef PW2_CASE
+    const bool hit = with_int<808, 816, 1608, 1616, 1632, 3216, 3232>(100 * Cin + Cout, [&](auto k) {  // (Cin, Cout)
+        constexpr int CI = k() / 100, CO = k() % 100;
+        using CC = Pw2Cfg<CI, CO>;
+        const Tiling2 tg = make_tiling2(N, H, W, CC::TW, CC::TH);
+        with_bools(
+            [&](auto pp) {
+                OCRS_LAUNCH_T((k_pw_bwd2<CI, CO, pp()>), dim3(nb), dim3(256), CC::SMEM, st, x, tra, trb, wdw, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, bn, coef,
+                              wpk_d, (bf16*)du, dwpw, ws, tg, ldu, ldw);
+            },
+            pooled != 0);
+    });
+    if (!hit) return OCRS_ERR_ARG;
     if (ws) det_wgrad_reduce_launch(ws, nb, Cin * Cout, dwpw, Cin, ldw, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;

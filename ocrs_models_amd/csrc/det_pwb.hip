@@ -399,33 +399,20 @@ int det_pwb_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
     Src2<bf16> x{(const bf16*)xa, (const bf16*)xb, Ca, Cb};
     const Tiling2 tg = make_tiling2(N, H, W, 8, pwb_th(Cin, Cout));
     const int gx = det_pwb_gx(Cin, Cout, N, H, W, pooled), ny = pwb_ny(Cin), Cb_ = Cin / ny;  // Cb_: channels per block
-    bool done = false;
-#define PWB_LAUNCH(CI_, CO_, PP_, GG_)                                                                                                              \
-    {                                                                                                                                               \
-        using CC = PwbCfg<CI_, CO_>;                                                                                                                \
-        static DevOnce attr_set;                                                                                                               \
-        if (attr_set.need()) {                                                                                                                            \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pwb<CI_, CO_, PP_, GG_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM) != \
-                hipSuccess)                                                                                                                         \
-                return OCRS_ERR_HIP;                                                                                                                \
-            attr_set.done();                                                                                                                        \
-        }                                                                                                                                           \
-        OCRS_LAUNCH_T((k_pwb<CI_, CO_, PP_, GG_>), dim3(gx, ny), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, (const bf16*)g1, (const bf16*)g2, (const bf16*)z, \
-                      bn, coef, wpk_d, (bf16*)du, ws, tg, fin);                                                                                          \
-        done = true;                                                                                                                                \
-    }
-#define PWB_CASE(CI_, CO_)                                                      \
-    if (!done && Cb_ == CI_ && Cout == CO_) {                                   \
-        if (pooled) {                                                           \
-            if (g2) PWB_LAUNCH(CI_, CO_, true, true) else PWB_LAUNCH(CI_, CO_, true, false) \
-        } else {                                                                \
-            if (g2) PWB_LAUNCH(CI_, CO_, false, true) else PWB_LAUNCH(CI_, CO_, false, false) \
-        }                                                                       \
-    }
-    PWB_CASE(32, 64) PWB_CASE(64, 64) PWB_CASE(64, 128) PWB_CASE(128, 64) PWB_CASE(128, 128) PWB_CASE(128, 256)
-#undef PWB_CASE
-#undef PWB_LAUNCH
-    OCRS_CHECK_ARG(done);
+    int rc = OCRS_ERR_ARG;
+    with_int<32064, 64064, 64128, 128064, 128128, 128256>(1000 * Cb_ + Cout, [&](auto k) {  // (channels per block, Cout)
+        constexpr int CI = k() / 1000, CO = k() % 1000;
+        using CC = PwbCfg<CI, CO>;
+        rc = with_bools(
+            [&](auto pp, auto gg) {
+                if (int rc = dyn_lds<&k_pwb<CI, CO, pp(), gg()>>(CC::SMEM)) return rc;
+                OCRS_LAUNCH_T((k_pwb<CI, CO, pp(), gg()>), dim3(gx, ny), dim3(CC::NT), CC::SMEM, st, x, tra, trb, wdw, (const bf16*)g1, (const bf16*)g2, (const bf16*)z,
+                              bn, coef, wpk_d, (bf16*)du, ws, tg, fin);
+                return OCRS_OK;
+            },
+            pooled != 0, g2 != nullptr);
+    });
+    if (rc != OCRS_OK) return rc;
     det_wgrad_reduce_launch(ws, gx, Cin * Cout, dwpw, Cin, Cin, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;

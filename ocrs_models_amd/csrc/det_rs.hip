@@ -1175,10 +1175,10 @@ int rs_bwd_blocks(int Cin, int Cout, int N, int H, int W, int g2) {
     rs_geometry(N, H, W, rs_wps(Cin, Cout), NS, NP, NB, PB, njobs, nb);
     return nb;
 }
-void rs_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, int ldw, const bf16* g1, const bf16* g2,
-                   const bf16* z, const float* bn, const float* coef, bf16* gxa, bf16* gxb, float* ws, bool stats, int Cout, int N, int H, int W,
-                   const BnFin& fin, hipStream_t st, const float* gl, const float* whead, const bf16* xu, const float* wexp, const BwdLast& bl, const float* img,
-                   double* c1acc) {
+int rs_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, const float* wdw, const float* wpw, int ldw, const bf16* g1, const bf16* g2,
+                  const bf16* z, const float* bn, const float* coef, bf16* gxa, bf16* gxb, float* ws, bool stats, int Cout, int N, int H, int W,
+                  const BnFin& fin, hipStream_t st, const float* gl, const float* whead, const bf16* xu, const float* wexp, const BwdLast& bl, const float* img,
+                  double* c1acc) {
     RsArgs a;
     a.bl = bl;
     a.img = img;
@@ -1196,48 +1196,40 @@ void rs_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb, cons
     a.fin = fin;
     (void)stats;
     const int Cin = x.Ca + x.Cb;
-#define RS_LAUNCH(CI_, CO_, G2_, SP_)                                                                                                        \
-    {                                                                                                                                        \
-        using CC = RsCfg<CI_, CO_>;                                                                                                          \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_bwd<CI_, CO_, G2_, SP_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM); \
-        OCRS_LAUNCH_T((k_rs_bwd<CI_, CO_, G2_, SP_>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);                                             \
-    }
     if (xu) {  // the block behind the first block (8 -> 8 channels, input rebuilt from the u plane; one or two gradients)
-        using CC = RsCfg<8, 8>;
-        if (img && c1acc) {  // C1: also the first block's weight-gradient sums, no dx~ store (+ the image / u rings behind the regular LDS layout)
-            constexpr int SM = CC::SMEM + CC::NW * (2 * 6 * 34 * 4 + 32);
-            if (g2) {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_bwd<8, 8, true, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SM);
-                OCRS_LAUNCH_T((k_rs_bwd<8, 8, true, false, false, true, true>), dim3(nb), dim3(CC::NT), SM, st, a);
-            } else {
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_bwd<8, 8, false, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SM);
-                OCRS_LAUNCH_T((k_rs_bwd<8, 8, false, false, false, true, true>), dim3(nb), dim3(CC::NT), SM, st, a);
-            }
-            return;
-        }
-        if (g2) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_bwd<8, 8, true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);
-            OCRS_LAUNCH_T((k_rs_bwd<8, 8, true, false, false, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);
-        } else {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_bwd<8, 8, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);
-            OCRS_LAUNCH_T((k_rs_bwd<8, 8, false, false, false, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);
-        }
-        return;
+        // C1: also the first block's weight-gradient sums, no dx~ store (+ the image / u rings behind the regular LDS layout)
+        return with_bools(
+            [&](auto g, auto c) {
+                using CC = RsCfg<8, 8>;
+                constexpr bool G2 = g(), C1 = c();
+                constexpr int SM = C1 ? CC::SMEM + CC::NW * (2 * 6 * 34 * 4 + 32) : CC::SMEM;
+                if (int rc = dyn_lds<&k_rs_bwd<8, 8, G2, false, false, true, C1>>(SM)) return rc;
+                OCRS_LAUNCH_T((k_rs_bwd<8, 8, G2, false, false, true, C1>), dim3(nb), dim3(CC::NT), SM, st, a);
+                return OCRS_OK;
+            },
+            g2 != nullptr, img && c1acc);
     }
     if (gl) {  // the block in front of out_conv (8 -> 8 channels, one source, one gradient)
         using CC = RsCfg<8, 8>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_bwd<8, 8, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);
+        if (int rc = dyn_lds<&k_rs_bwd<8, 8, false, false, true>>(CC::SMEM)) return rc;
         OCRS_LAUNCH_T((k_rs_bwd<8, 8, false, false, true>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);
-        return;
+        return OCRS_OK;
     }
-#define RS_CASE(CI_, CO_)                                                                 \
-    if (Cin == CI_ && Cout == CO_) {                                                      \
-        if (g2) RS_LAUNCH(CI_, CO_, true, false) else RS_LAUNCH(CI_, CO_, false, false)   \
-    }
-    RS_CASE(8, 8)
-    RS_CASE(8, 16)
-#undef RS_CASE
-#undef RS_LAUNCH
+    int rc = OCRS_ERR_ARG;
+    if (Cin == 8)
+        with_int<8, 16>(Cout, [&](auto co) {
+            constexpr int CO = co();
+            using CC = RsCfg<8, CO>;
+            rc = with_bools(
+                [&](auto g) {
+                    constexpr bool G2 = g();
+                    if (int rc = dyn_lds<&k_rs_bwd<8, CO, G2, false>>(CC::SMEM)) return rc;
+                    OCRS_LAUNCH_T((k_rs_bwd<8, CO, G2, false>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);
+                    return OCRS_OK;
+                },
+                g2 != nullptr);
+        });
+    return rc;
 }
 
 // ---- row-streaming forward (k_rs_fwd): Cin = 8 (one source or the u plane) or 16 (one source or the 8 | 8 concat), Cout = 8, no fused pooling
@@ -1254,8 +1246,8 @@ int rs_fwd_blocks(int N, int H, int W) {
     rs_geometry(N, H, W, kRsfWps, NS, NP, NB, PB, njobs, nb);
     return nb;
 }
-void rs_fwd_launch(const Src2<bf16>& x, const bf16* xu, const float* wexp, const float* tra, const float* trb, const float* wdw, const float* wpw, bf16* z, float* ws,
-                   int Cout, int N, int H, int W, int nb, const FwdFin& fin, hipStream_t st) {
+int rs_fwd_launch(const Src2<bf16>& x, const bf16* xu, const float* wexp, const float* tra, const float* trb, const float* wdw, const float* wpw, bf16* z, float* ws,
+                  int Cout, int N, int H, int W, int nb, const FwdFin& fin, hipStream_t st) {
     RsfArgs a;
     a.xa = x.a; a.xb = x.b; a.Ca = x.Ca; a.Cb = x.Cb; a.xu = xu; a.wexp = wexp; a.tra = tra; a.trb = trb; a.wdw = wdw; a.wpw = wpw; a.z = z; a.ws = ws;
     a.N = N; a.H = H; a.W = W;
@@ -1263,16 +1255,23 @@ void rs_fwd_launch(const Src2<bf16>& x, const bf16* xu, const float* wexp, const
     rs_geometry(N, H, W, kRsfWps, a.NS, a.NP, a.NB, a.PB, a.njobs, nb_geo);
     (void)nb_geo;  // (the caller's nb = rs_fwd_blocks(): the number of partials it allocated)
     a.fin = fin;
-#define RSF_LAUNCH(CI_, CO_, XU_)                                                                                                              \
-    {                                                                                                                                          \
-        using CC = RsfCfg<CI_, CO_>;                                                                                                           \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_fwd<CI_, CO_, XU_>), hipFuncAttributeMaxDynamicSharedMemorySize, CC::SMEM);    \
-        OCRS_LAUNCH_T((k_rs_fwd<CI_, CO_, XU_>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);                                                    \
-    }
-    const int Cin = x.Ca + x.Cb;
-    if (Cin == 16) RSF_LAUNCH(16, 8, false)
-    else if (Cout == 8) {
-        if (xu) RSF_LAUNCH(8, 8, true) else RSF_LAUNCH(8, 8, false)
-    }
-#undef RSF_LAUNCH
+    if (Cout != 8) return OCRS_ERR_ARG;
+    int rc = OCRS_ERR_ARG;
+    with_int<8, 16>(x.Ca + x.Cb, [&](auto ci) {
+        constexpr int CI = ci();
+        rc = with_bools(
+            [&](auto u) {
+                constexpr bool XU = u();
+                if constexpr (XU && CI != 8) {
+                    return OCRS_ERR_ARG;
+                } else {
+                    using CC = RsfCfg<CI, 8>;
+                    if (int rc = dyn_lds<&k_rs_fwd<CI, 8, XU>>(CC::SMEM)) return rc;
+                    OCRS_LAUNCH_T((k_rs_fwd<CI, 8, XU>), dim3(nb), dim3(CC::NT), CC::SMEM, st, a);
+                    return OCRS_OK;
+                }
+            },
+            xu != nullptr);
+    });
+    return rc;
 }

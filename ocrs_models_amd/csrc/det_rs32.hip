@@ -1473,7 +1473,7 @@ static double* rs32_last_scratch(int ndoubles, hipStream_t st) {
     static double* g_own[16] = {};
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 16) return nullptr;
-    constexpr int CAP = BWD_LAST_SLOTS * 2 * 32 + 2;
+    constexpr int CAP = bwd_last_doubles(32);
     if (ndoubles > CAP) return nullptr;
     if (!g_own[d]) {
         double* p = nullptr;
@@ -1485,6 +1485,12 @@ static double* rs32_last_scratch(int ndoubles, hipStream_t st) {
         g_own[d] = p;
     }
     return g_own[d];
+}
+// BwdLast of a launch that wants its producers' sums: ok = false when there is no scratch to be had
+static BwdLast rs32_bwd_last(bool want, int Cin, int Ca, double* gsA, double* gsB, const float* svA, const float* svB, hipStream_t st, bool& ok) {
+    double* p = want ? rs32_last_scratch(bwd_last_doubles(Cin), st) : nullptr;
+    ok = !want || p;
+    return bwd_last(want, Cin, Ca, gsA, gsB, svA, svB, p);
 }
 }  // namespace
 
@@ -1509,18 +1515,12 @@ int det_rs32_ctw_launch(const float* x, const float* tr, const float* g, float* 
     if (smem < (4096 + 64) * sizeof(float)) smem = (4096 + 64) * sizeof(float);
     for (int l = 0; l < nl; ++l) {
         Rs32CW a{x, tr, g, ws + (long)l * grid * 4 * ne, Cup, Cout, l * CE, N, h, w, H, W, jb};
-#define CTW32_CASE(MT_, CE_)                                                                                    \
-    if (MT == MT_ && CE == CE_) {                                                                              \
-        static DevOnce once;                                                                                   \
-        if (once.need()) {                                                                                     \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs32_ctw<MT_, CE_>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) \
-                return OCRS_ERR_HIP;                                                                           \
-            once.done();                                                                                       \
-        }                                                                                                      \
-        OCRS_LAUNCH_T((k_rs32_ctw<MT_, CE_>), dim3(grid), dim3(256), smem, st, a);                             \
-    }
-        CTW32_CASE(1, 8) CTW32_CASE(1, 16) CTW32_CASE(2, 8) CTW32_CASE(2, 16)
-#undef CTW32_CASE
+        int rc = OCRS_ERR_ARG;
+        with_int<108, 116, 208, 216>(100 * MT + CE, [&](auto k) {
+            constexpr int MT_ = k() / 100, CE_ = k() % 100;
+            if ((rc = dyn_lds<&k_rs32_ctw<MT_, CE_>>(96 * 1024)) == OCRS_OK) OCRS_LAUNCH_T((k_rs32_ctw<MT_, CE_>), dim3(grid), dim3(256), smem, st, a);
+        });
+        if (rc != OCRS_OK) return rc;
         OCRS_LAUNCH_CHECK();
         // dW[c][o0 + oo][pos] += column (c * CE + oo) * 9 + pos of the partials: rows of 9 CE elements at a pitch of 9 Cout; db[o0 + oo] behind them
         bwd_reduce_or_defer(a.ws, grid * 4, ne, dW + (long)l * CE * 9, Cup * 9 * CE, 9 * CE, 9 * Cout, dbias + l * CE, CE, st);
@@ -1557,18 +1557,13 @@ int ocrs_rs32_fwd(const float* xa, const float* xb, int Ca, int Cb, const float*
             FwdFin{counter, count, bn_w, bn_b, eps, momentum, tr, saved, run_mean, run_var, nbt, lo}};
     const int nset = Cin > 16 ? 2 : 1, mt = Cout > 16 ? 2 : 1;
     const int grid = rs32_grid(a.jb.njobs, nset * mt == 1 ? 3 : 2);
-#define RS32F_CASE(NS_, MT_, SP_, PL_, P_)                                                                         \
-    if (nset == NS_ && mt == MT_ && (Cb != 0) == SP_ && (pooled != nullptr) == PL_) {                             \
-        OCRS_LAUNCH_T((k_rs32_fwd<NS_, MT_, SP_, PL_, P_>), dim3(grid), dim3(256), 0, st, a);                     \
-        OCRS_LAUNCH_CHECK();                                                                                      \
-        return OCRS_OK;                                                                                           \
-    }
-    RS32F_CASE(1, 1, false, false, 4) RS32F_CASE(1, 1, false, true, 4) RS32F_CASE(1, 1, true, false, 4) RS32F_CASE(1, 1, true, true, 4)
-    RS32F_CASE(1, 2, false, false, 4) RS32F_CASE(1, 2, false, true, 4) RS32F_CASE(1, 2, true, false, 4) RS32F_CASE(1, 2, true, true, 4)
-    RS32F_CASE(2, 1, false, false, 2) RS32F_CASE(2, 1, false, true, 2) RS32F_CASE(2, 1, true, false, 2) RS32F_CASE(2, 1, true, true, 2)
-    RS32F_CASE(2, 2, false, false, 2) RS32F_CASE(2, 2, false, true, 2) RS32F_CASE(2, 2, true, false, 2) RS32F_CASE(2, 2, true, true, 2)
-#undef RS32F_CASE
-    return OCRS_ERR_ARG;
+    const bool hit = with_int<11, 12, 21, 22>(10 * nset + mt, [&](auto k) {
+        constexpr int NS = k() / 10, MT = k() % 10, P = NS == 1 ? 4 : 2;  // P: input rows in flight
+        with_bools([&](auto sp, auto pl) { OCRS_LAUNCH_T((k_rs32_fwd<NS, MT, sp(), pl(), P>), dim3(grid), dim3(256), 0, st, a); }, Cb != 0, pooled != nullptr);
+    });
+    if (!hit) return OCRS_ERR_ARG;
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
 }
 
 // 1 if ocrs_rs32_bwd runs this block shape: fp32 storage, direct (not max-pooled) gradient source, Cin = Ca + Cb in {8, 16} (concat 8 | 8), Cout in {8, 16}
@@ -1592,23 +1587,14 @@ static int rs32_bwd_one(const float* x, const float* tr, const float* wdw, const
                         float* dwdw, float* ws, const float* saved_p, double* gsum_p, int Cout, int N, int H, int W, hipStream_t st) {
     const int Cin = 16;
     const bool stats = gsum_p != nullptr;
-    BwdLast bl{nullptr, nullptr, gsum_p, nullptr, saved_p, nullptr, Cin, 0};
-    if (stats) {
-        double* p = rs32_last_scratch(BWD_LAST_SLOTS * 2 * Cin + 2, st);
-        if (!p) return OCRS_ERR_HIP;
-        bl.raw = p;
-        bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
-    }
+    bool ok;
+    const BwdLast bl = rs32_bwd_last(stats, Cin, Cin, gsum_p, nullptr, saved_p, nullptr, st, ok);
+    if (!ok) return OCRS_ERR_HIP;
     Rs32B a{x, nullptr, tr, nullptr, wdw, wpw, g1, g2, z, bn, gx, nullptr, ws, Cin, 0, Cout, N, H, W, rs32_jobs(N, H, W, RS32_COLS, kRs32Rows),
             BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, ldw, nullptr, nullptr};
     const int grid = rs32_grid(a.jb.njobs, 3);
-#define RS32O_CASE(G2_, ST_)                                                                          \
-    if ((g2 != nullptr) == G2_ && stats == ST_) {                                                    \
-        OCRS_LAUNCH_T((k_rs32_bwd<false, G2_, ST_, 1, false>), dim3(grid), dim3(256), 0, st, a);     \
-        OCRS_LAUNCH_CHECK();                                                                         \
-    }
-    RS32O_CASE(false, false) RS32O_CASE(false, true) RS32O_CASE(true, false) RS32O_CASE(true, true)
-#undef RS32O_CASE
+    with_bools([&](auto g, auto s_) { OCRS_LAUNCH_T((k_rs32_bwd<false, g(), s_(), 1, false>), dim3(grid), dim3(256), 0, st, a); }, g2 != nullptr, stats);
+    OCRS_LAUNCH_CHECK();
     bwd_reduce_or_defer(ws, grid, Cout * Cin + 9 * Cin, dwpw, Cout * Cin, Cin, ldw, dwdw, 9 * Cin, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
@@ -1640,58 +1626,36 @@ int ocrs_rs32_bwd(const float* xa, const float* xb, int Ca, int Cb, const float*
                             gsum_b, Cout, N, H, W, st);
     }
     const bool stats = gsum_a || gsum_b;
-    BwdLast bl{nullptr, nullptr, gsum_a, gsum_b, saved_a, saved_b, Ca, 0};
-    if (stats) {
-        double* p = rs32_last_scratch(BWD_LAST_SLOTS * 2 * Cin + 2, st);
-        if (!p) return OCRS_ERR_HIP;
-        bl.raw = p;
-        bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
-    }
+    bool ok;
+    const BwdLast bl = rs32_bwd_last(stats, Cin, Ca, gsum_a, gsum_b, saved_a, saved_b, st, ok);
+    if (!ok) return OCRS_ERR_HIP;
     const bool dual = !pooled && Cb == 0 && Cin == 8 && Cout == 8;  // two 14-column strips per wave (8-channel tensors fill half the lanes)
     Rs32B a{xa, xb, tra, trb, wdw, wpw, g1, g2, z, bn, gxa, gxb, ws, Ca, Cb, Cout, N, H, W,
             rs32_jobs(N, H, W, pooled ? RS32P_COLS : (dual ? 2 * RS32_COLS : RS32_COLS), kRs32Rows), BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, Cin, nullptr, nullptr};
     const bool wide = Cin > 16 || Cout > 16;
     const int grid = rs32_grid(a.jb.njobs, (pooled || wide || (dual && g2)) ? 2 : 3);
-    if (wide) {
-#define RS32X_CASE(NS_, MT_, SP_, G2_, ST_)                                                                                  \
-    if (Cin == 16 * NS_ && Cout == 16 * MT_ && (Cb != 0) == SP_ && (g2 != nullptr) == G2_ && stats == ST_) {               \
-        OCRS_LAUNCH_T((k_rs32_bwdx<NS_, MT_, SP_, G2_, ST_>), dim3(grid), dim3(256), 0, st, a);                             \
-        OCRS_LAUNCH_CHECK();                                                                                                \
+    if (pooled) OCRS_CHECK_ARG(H >= 2 && W >= 2);
+    const bool two = g2 != nullptr;
+    int rc = OCRS_ERR_ARG;
+    if (wide) {  // 16 -> 32 from one source: the only wide form
+        if (Cin == 16 && Cout == 32 && !Cb)
+            rc = with_bools([&](auto g, auto s_) { OCRS_LAUNCH_T((k_rs32_bwdx<1, 2, false, g(), s_()>), dim3(grid), dim3(256), 0, st, a); return OCRS_OK; }, two, stats);
+    } else if (pooled) {
+        rc = with_bools([&](auto g, auto s_) { OCRS_LAUNCH_T((k_rs32_bwdp<g(), s_()>), dim3(grid), dim3(256), 0, st, a); return OCRS_OK; }, two, stats);
+    } else {
+        rc = with_bools(
+            [&](auto sp, auto du, auto g, auto s_) {
+                if constexpr (sp() && du()) {  // (two strips per wave: single-source blocks only)
+                    return OCRS_ERR_ARG;
+                } else {
+                    OCRS_LAUNCH_T((k_rs32_bwd<sp(), g(), s_(), 1, du()>), dim3(grid), dim3(256), 0, st, a);
+                    return OCRS_OK;
+                }
+            },
+            Cb != 0, dual, two, stats);
     }
-        RS32X_CASE(1, 2, false, false, false) RS32X_CASE(1, 2, false, false, true) RS32X_CASE(1, 2, false, true, false) RS32X_CASE(1, 2, false, true, true)
-#undef RS32X_CASE
-        bwd_reduce_or_defer(ws, grid, Cout * Cin + 9 * Cin, dwpw, Cout * Cin, Cin, Cin, dwdw, 9 * Cin, st);
-        OCRS_LAUNCH_CHECK();
-        return OCRS_OK;
-    }
-    if (pooled) {
-        OCRS_CHECK_ARG(H >= 2 && W >= 2);
-#define RS32P_CASE(G2_, ST_)                                                                    \
-    if ((g2 != nullptr) == G2_ && stats == ST_) {                                               \
-        OCRS_LAUNCH_T((k_rs32_bwdp<G2_, ST_>), dim3(grid), dim3(256), 0, st, a);                \
-        OCRS_LAUNCH_CHECK();                                                                    \
-    }
-        RS32P_CASE(false, false) RS32P_CASE(false, true) RS32P_CASE(true, false) RS32P_CASE(true, true)
-#undef RS32P_CASE
-        bwd_reduce_or_defer(ws, grid, Cout * Cin + 9 * Cin, dwpw, Cout * Cin, Cin, Cin, dwdw, 9 * Cin, st);
-        OCRS_LAUNCH_CHECK();
-        return OCRS_OK;
-    }
-#define RS32B_CASE(SP_, G2_, ST_)                                                                      \
-    if ((Cb != 0) == SP_ && (g2 != nullptr) == G2_ && stats == ST_) {                                 \
-        if constexpr (!SP_) {                                                                         \
-            if (dual)                                                                                 \
-                OCRS_LAUNCH_T((k_rs32_bwd<false, G2_, ST_, 1, true>), dim3(grid), dim3(256), 0, st, a); \
-            else                                                                                      \
-                OCRS_LAUNCH_T((k_rs32_bwd<false, G2_, ST_, 1, false>), dim3(grid), dim3(256), 0, st, a); \
-        } else {                                                                                      \
-            OCRS_LAUNCH_T((k_rs32_bwd<SP_, G2_, ST_, 1>), dim3(grid), dim3(256), 0, st, a);           \
-        }                                                                                             \
-        OCRS_LAUNCH_CHECK();                                                                          \
-    }
-    RS32B_CASE(false, false, false) RS32B_CASE(false, false, true) RS32B_CASE(false, true, false) RS32B_CASE(false, true, true)
-    RS32B_CASE(true, false, false) RS32B_CASE(true, false, true) RS32B_CASE(true, true, false) RS32B_CASE(true, true, true)
-#undef RS32B_CASE
+    if (rc != OCRS_OK) return rc;
+    OCRS_LAUNCH_CHECK();
     bwd_reduce_or_defer(ws, grid, Cout * Cin + 9 * Cin, dwpw, Cout * Cin, Cin, Cin, dwdw, 9 * Cin, st);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
@@ -1712,21 +1676,14 @@ int ocrs_rs32_convt_fwd(const float* x, const float* tr, const float* wt, const 
     const int nset = Cup / 16, mt = 4 * Cout / 16;
     const int grid = rs32_grid(a.jb.njobs, 2);
     const size_t smem = (size_t)mt * 4 * nset * 64 * 4 * sizeof(float);
-#define CTF32_CASE(NS_, MT_)                                                                                   \
-    if (nset == NS_ && mt == MT_) {                                                                           \
-        static DevOnce once;                                                                                  \
-        if (once.need()) {                                                                                    \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs32_ctf<NS_, MT_>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) \
-                return OCRS_ERR_HIP;                                                                          \
-            once.done();                                                                                      \
-        }                                                                                                     \
-        OCRS_LAUNCH_T((k_rs32_ctf<NS_, MT_>), dim3(grid), dim3(256), smem, st, a);                            \
-        OCRS_LAUNCH_CHECK();                                                                                  \
-        return OCRS_OK;                                                                                       \
-    }
-    CTF32_CASE(1, 2) CTF32_CASE(2, 4) CTF32_CASE(2, 8)
-#undef CTF32_CASE
-    return OCRS_ERR_ARG;
+    int rc = OCRS_ERR_ARG;
+    with_int<102, 204, 208>(100 * nset + mt, [&](auto k) {  // (channel sets, output tiles)
+        constexpr int NS = k() / 100, MT = k() % 100;
+        if ((rc = dyn_lds<&k_rs32_ctf<NS, MT>>(64 * 1024)) == OCRS_OK) OCRS_LAUNCH_T((k_rs32_ctf<NS, MT>), dim3(grid), dim3(256), smem, st, a);
+    });
+    if (rc != OCRS_OK) return rc;
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
 }
 
 // 1 if ocrs_rs32_convt_dgrad runs this shape: fp32, (Cup, Cout) in {(16, 8), (32, 16)}
@@ -1742,24 +1699,18 @@ int ocrs_rs32_convt_dgrad(const float* g, const float* wt, float* dx, const floa
     OCRS_CHECK_ARG(ocrs_rs32_convt_dgrad_supported(Cup, Cout, 0) && g && wt && dx && N > 0 && h > 0 && w > 0 && H <= 2 * h + 1 && W <= 2 * w + 1);
     OCRS_CHECK_ARG((!gsum || (x && tr && saved)) && (long)N * H * W * Cout * 4 < (1L << 32) && (long)N * h * w * Cup * 4 < (1L << 32));
     const bool stats = gsum != nullptr;
-    BwdLast bl{nullptr, nullptr, gsum, nullptr, saved, nullptr, Cup, 0};
-    if (stats) {
-        double* p = rs32_last_scratch(BWD_LAST_SLOTS * 2 * Cup + 2, st);
-        if (!p) return OCRS_ERR_HIP;
-        bl.raw = p;
-        bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cup);
-    }
+    bool ok;
+    const BwdLast bl = rs32_bwd_last(stats, Cup, Cup, gsum, nullptr, saved, nullptr, st, ok);
+    if (!ok) return OCRS_ERR_HIP;
     Rs32CD a{g, wt, x, tr, dx, Cup, Cout, N, h, w, H, W, rs32_jobs(N, h, w, 16, 32), bl};
     const int grid = rs32_grid(a.jb.njobs, 2);
-#define CTD32_CASE(MT_, CE_, ST_)                                                               \
-    if (Cup == 16 * MT_ && Cout == CE_ && stats == ST_) {                                       \
-        OCRS_LAUNCH_T((k_rs32_ctd<MT_, CE_, ST_>), dim3(grid), dim3(256), 0, st, a);            \
-        OCRS_LAUNCH_CHECK();                                                                    \
-        return OCRS_OK;                                                                         \
-    }
-    CTD32_CASE(1, 8, false) CTD32_CASE(1, 8, true) CTD32_CASE(2, 16, false) CTD32_CASE(2, 16, true)
-#undef CTD32_CASE
-    return OCRS_ERR_ARG;
+    const bool hit = with_int<1608, 3216>(100 * Cup + Cout, [&](auto k) {
+        constexpr int MT = k() / 1600, CE = k() % 100;
+        with_bools([&](auto s_) { OCRS_LAUNCH_T((k_rs32_ctd<MT, CE, s_()>), dim3(grid), dim3(256), 0, st, a); }, stats);
+    });
+    if (!hit) return OCRS_ERR_ARG;
+    OCRS_LAUNCH_CHECK();
+    return OCRS_OK;
 }
 
 // 1 if ocrs_rs32_bwd_head runs the block in front of out_conv: fp32, 8 -> 8, single source
@@ -1776,19 +1727,14 @@ int ocrs_rs32_bwd_head(const float* xa, int Ca, const float* tra, const float* w
     OCRS_CHECK_ARG(gxa && dwpw && dwdw && ws && N > 0 && H > 0 && W > 0 && (!gsum_a || saved_a) && (long)N * H * W * 8 * 4 < (1L << 32));
     const int Cin = Ca;
     const bool stats = gsum_a != nullptr;
-    BwdLast bl{nullptr, nullptr, gsum_a, nullptr, saved_a, nullptr, Ca, 0};
-    if (stats) {
-        double* p = rs32_last_scratch(BWD_LAST_SLOTS * 2 * Cin + 2, st);
-        if (!p) return OCRS_ERR_HIP;
-        bl.raw = p;
-        bl.counter = reinterpret_cast<unsigned*>(p + BWD_LAST_SLOTS * 2 * Cin);
-    }
+    bool ok;
+    const BwdLast bl = rs32_bwd_last(stats, Cin, Ca, gsum_a, nullptr, saved_a, nullptr, st, ok);
+    if (!ok) return OCRS_ERR_HIP;
     // two 14-column strips per wave (8-channel tensors fill half the lanes)
     Rs32B a{xa, nullptr, tra, nullptr, wdw, wpw, nullptr, nullptr, z, bn, gxa, nullptr, ws, Ca, 0, Cout, N, H, W,
             rs32_jobs(N, H, W, 2 * RS32_COLS, kRs32Rows), BnFin{gsum, gamma, saved, dgamma, dbeta, (long)N * H * W}, bl, Cin, gl, whead};
     const int grid = rs32_grid(a.jb.njobs, 3);
-    if (stats) OCRS_LAUNCH_T((k_rs32_bwd<false, false, true, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
-    else OCRS_LAUNCH_T((k_rs32_bwd<false, false, false, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
+    with_bools([&](auto s_) { OCRS_LAUNCH_T((k_rs32_bwd<false, false, s_(), 1, true, true>), dim3(grid), dim3(256), 0, st, a); }, stats);
     OCRS_LAUNCH_CHECK();
     bwd_reduce_or_defer(ws, grid, Cout * Cin + 9 * Cin, dwpw, Cout * Cin, Cin, Cin, dwdw, 9 * Cin, st);
     OCRS_LAUNCH_CHECK();

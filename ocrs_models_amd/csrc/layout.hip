@@ -304,24 +304,6 @@ __global__ __launch_bounds__(256) void k_lay_attn_bwd(const float* __restrict__ 
 static size_t attn_fwd_lds(int nt) { return (size_t)3 * nt * 16 * ALD * sizeof(float); }
 static size_t attn_bwd_lds(int nt) { return ((size_t)4 * nt * 16 * ALD + 3 * nt * 16) * sizeof(float); }
 
-template <int NT>
-static int attn_set_attr() {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lay_attn_fwd<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_fwd_lds(NT)) != hipSuccess)
-        return 1;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lay_attn_bwd<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_bwd_lds(NT)) != hipSuccess)
-        return 1;
-    return 0;
-}
-static int attn_attrs() {
-    static DevOnce once;
-    if (once.need()) {
-        if (attn_set_attr<1>() || attn_set_attr<2>() || attn_set_attr<3>() || attn_set_attr<4>() || attn_set_attr<5>() || attn_set_attr<6>() ||
-            attn_set_attr<7>() || attn_set_attr<8>())
-            return 1;
-        once.done();
-    }
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // y = LayerNorm(x + dropout(a)) over rows of 256 floats, one wave per row (lane = 4 columns); stat [rows][2] = mean | rstd.
@@ -620,10 +602,11 @@ long ocrs_layout_attn_supported(int S) { return S >= 1 && S <= 128 ? 1 : 0; }
 int ocrs_layout_attn_fwd(const float* qkv, float* out, int S, int W, float p, long seed, int site, hipStream_t st) {
     OCRS_CHECK_ARG(qkv && out && ocrs_layout_attn_supported(S) && W >= 1 && W <= 65535 && p >= 0.f && p < 1.f);
     OCRS_CHECK_ARG(((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) & 15) == 0);
-    if (attn_attrs()) return OCRS_ERR_HIP;
     const DropKey dk = make_key(p, seed, site);
     const int nt = (S + 15) / 16;
-#define CALL(N_) hipLaunchKernelGGL(k_lay_attn_fwd<N_>, dim3(W, 4), dim3(256), attn_fwd_lds(N_), st, qkv, out, S, W, dk)
+#define CALL(N_)                                                                   \
+    if (int rc = dyn_lds<&k_lay_attn_fwd<N_>>((int)attn_fwd_lds(N_))) return rc; \
+    hipLaunchKernelGGL(k_lay_attn_fwd<N_>, dim3(W, 4), dim3(256), attn_fwd_lds(N_), st, qkv, out, S, W, dk)
     LAY_ATTN_DISPATCH(nt, CALL)
 #undef CALL
     OCRS_LAUNCH_CHECK();
@@ -633,10 +616,11 @@ int ocrs_layout_attn_fwd(const float* qkv, float* out, int S, int W, float p, lo
 int ocrs_layout_attn_bwd(const float* qkv, const float* dout, float* dqkv, int S, int W, float p, long seed, int site, hipStream_t st) {
     OCRS_CHECK_ARG(qkv && dout && dqkv && ocrs_layout_attn_supported(S) && W >= 1 && W <= 65535 && p >= 0.f && p < 1.f);
     OCRS_CHECK_ARG(((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dqkv)) & 15) == 0);
-    if (attn_attrs()) return OCRS_ERR_HIP;
     const DropKey dk = make_key(p, seed, site);
     const int nt = (S + 15) / 16;
-#define CALL(N_) hipLaunchKernelGGL(k_lay_attn_bwd<N_>, dim3(W, 4), dim3(256), attn_bwd_lds(N_), st, qkv, dout, dqkv, S, W, dk)
+#define CALL(N_)                                                                   \
+    if (int rc = dyn_lds<&k_lay_attn_bwd<N_>>((int)attn_bwd_lds(N_))) return rc; \
+    hipLaunchKernelGGL(k_lay_attn_bwd<N_>, dim3(W, 4), dim3(256), attn_bwd_lds(N_), st, qkv, dout, dqkv, S, W, dk)
     LAY_ATTN_DISPATCH(nt, CALL)
 #undef CALL
     OCRS_LAUNCH_CHECK();

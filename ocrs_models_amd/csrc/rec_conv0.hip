@@ -357,14 +357,10 @@ __global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ img
     }
 }
 
-// k_conv0_bwd_mm's launcher for ocrs_conv0_bwd: 1 if this kernel took the call (bf16 gradient, even H and W)
+// k_conv0_bwd_mm's launcher for ocrs_conv0_bwd: 1 if this kernel took the call (bf16 gradient, even H and W), 0 if not, -1: HIP error
 static int conv0_bwd_mm_launch(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype, hipStream_t st) {
     if (dtype != 1 || (H & 1) || (W & 1) || H < 2 || W < 2 || (long)N * (H / 2) * (((W / 2) + 31) / 32) >= (1L << 30)) return 0;
-    static DevOnce attr;
-    if (attr.need()) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv0_bwd_mm), hipFuncAttributeMaxDynamicSharedMemorySize, C0_SMEM);
-        attr.done();
-    }
+    if (dyn_lds<&k_conv0_bwd_mm>(C0_SMEM) != OCRS_OK) return -1;
     const long nsteps = (long)N * (H / 2) * (((W / 2) + 31) / 32);
     long grid = (nsteps + 3) / 4;
     if (grid > (long)kNumCU * 3) grid = (long)kNumCU * 3;  // three workgroups per CU (see the LDS note in the kernel)
@@ -391,7 +387,8 @@ int ocrs_conv0_fwd(const float* img, const float* w, const float* bias, void* ou
 int ocrs_conv0_bwd(const float* img, const float* w, const float* bias, const void* g, float* dW, float* db, int N, int H, int W, int dtype,
                    hipStream_t st) {
     OCRS_CHECK_ARG(img && w && bias && g && dW && db);
-    if (conv0_bwd_mm_launch(img, w, bias, g, dW, db, N, H, W, dtype, st)) {
+    if (const int took = conv0_bwd_mm_launch(img, w, bias, g, dW, db, N, H, W, dtype, st)) {
+        if (took < 0) return OCRS_ERR_HIP;
         OCRS_LAUNCH_CHECK();
         return OCRS_OK;
     }

@@ -238,14 +238,8 @@ int conv3x3_c128_launch(const void* x, int ldx, const void* wpk, void* out, int 
     const bool two = H < 16;  // two images x 8 rows per tile
     const int TH = two ? 8 : 16, NI = two ? 2 : 1;
     const long ntiles = (long)((N + NI - 1) / NI) * ((W + C2_TW - 1) / C2_TW) * ((H + TH - 1) / TH);
-    static DevOnce attr_set;
-    if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c128<16>), hipFuncAttributeMaxDynamicSharedMemorySize, C2_SMEM) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c128<8>), hipFuncAttributeMaxDynamicSharedMemorySize, C2_SMEM) != hipSuccess)
-            return OCRS_ERR_HIP;
-        attr_set.done();
-    }
     const int grid = persistent_grid(ntiles, 2);
+    if (int rc = two ? dyn_lds<&k_conv3x3_c128<8>>(C2_SMEM) : dyn_lds<&k_conv3x3_c128<16>>(C2_SMEM)) return rc;
     if (two)
         hipLaunchKernelGGL(k_conv3x3_c128<8>, dim3(grid), dim3(256), C2_SMEM, st, (const bf16*)x, ldx, wpk, (bf16*)out, ldo, bias, relu, gstat, Cin, N, H, W);
     else

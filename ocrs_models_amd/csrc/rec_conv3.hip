@@ -386,12 +386,8 @@ R3Plan r3_plan(int M, int H, int W, int KW) {
 template <int MH, int WM, int NTW, int UPS>
 int r3_launch(const R3Plan& pl, const void* x, int ldx, const void* wpk, void* out, int ldo, const float* bias, int relu, double* gstat, int Cin, int N, int H, int W,
               int Hi, int Wi, int KW, int pad, hipStream_t st) {
-    static DevOnce attr_set;
     auto kern = &k_conv3x3_rows<MH, WM, NTW, UPS>;
-    if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return OCRS_ERR_HIP;
-        attr_set.done();
-    }
+    if (int rc = dyn_lds<&k_conv3x3_rows<MH, WM, NTW, UPS>>(160 * 1024)) return rc;
     // whole passes per block, as evenly as the pass count allows (two / four passes = one image per CU at B = 256)
     const int total = N * ((H + pl.R - 1) / pl.R);
     int grid = total < kNumCU ? total : kNumCU;

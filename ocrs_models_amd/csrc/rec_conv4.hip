@@ -297,12 +297,8 @@ R4Plan r4_plan(int M, int Cin, int H, int W) {
 template <int MH>
 int r4_launch(const R4Plan& pl, const void* x, int ldx, const void* wpk, void* out, int ldo, const float* bias, int relu, double* gstat, int Cin, int N, int H, int W,
               hipStream_t st) {
-    static DevOnce attr_set;
     auto kern = &k_conv3x3_tile<MH, 4>;
-    if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return OCRS_ERR_HIP;
-        attr_set.done();
-    }
+    if (int rc = dyn_lds<&k_conv3x3_tile<MH, 4>>(160 * 1024)) return rc;
     const int total = N * ((H + pl.R - 1) / pl.R) * ((W + pl.TWc - 1) / pl.TWc);
     int grid = total < kNumCU ? total : kNumCU;
     const int ppb = (total + grid - 1) / grid;

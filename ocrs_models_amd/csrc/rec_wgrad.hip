@@ -772,15 +772,7 @@ int ocrs_wgrad_gather(const void* A, int ldA, int CA, const float* trA, const vo
     long gx;
     int gy;
     wgrad_gather_grid(CA, CB, KH * KW, P, dtype, gx, gy);
-    static DevOnce attr_set;
-    if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_gather<float, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_gather<bf16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) !=
-                hipSuccess)
-            return OCRS_ERR_HIP;
-        attr_set.done();
-    }
+    if (int rc = dtype == 1 ? dyn_lds<&k_wgrad_gather<bf16, 128>>(96 * 1024) : dyn_lds<&k_wgrad_gather<float, 64>>(96 * 1024)) return rc;
     if (dtype == 1 && ws) {
         int g, gy2, ta, cpb;
         wgrad_gather_tr_grid(CA, CB, KH * KW, P, g, gy2, ta, cpb);
@@ -834,17 +826,10 @@ int ocrs_conv3x3_wgrad(const void* dz, int Cout, const void* x, int Cin, float* 
     OCRS_CHECK_ARG(dz && x && dW && Cout % 8 == 0 && Cout <= 128 && Cin % 32 == 0);
     const int gy = Cin / 32;
     const long gx = wgrad3x3_gx(Cin, N, H, W);  // few flushing blocks: each loops over many tiles
-    static DevOnce attr_set;
-    if (attr_set.need()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wgrad<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wgrad_tr<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
-                hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_wgrad_tr<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
-                hipSuccess)
-            return OCRS_ERR_HIP;
-        attr_set.done();
-    }
+    if (int rc = dtype != 1    ? dyn_lds<&k_conv3x3_wgrad<float>>(140 * 1024)
+                 : Cout > 64 ? dyn_lds<&k_conv3x3_wgrad_tr<128>>(64 * 1024)
+                             : dyn_lds<&k_conv3x3_wgrad_tr<64>>(64 * 1024))
+        return rc;
     if (dtype == 1) {
         if (Cout > 64)
             hipLaunchKernelGGL(k_conv3x3_wgrad_tr<128>, dim3((int)gx, gy), dim3(256), (128 * 136 + 180 * 40) * 2, st, (const bf16*)dz, Cout, (const bf16*)x,
