@@ -145,7 +145,9 @@ int ocrs_bn_bwd_reduce(const void* g1, const void* g2, int pooled, const void* z
 int ocrs_bn_bwd_finalize(const double* gsum, long count, int C, const float* gamma, const float* saved, float* coef, float* dgamma,
                          float* dbeta, hipStream_t st);
 /* autograd of the 1x1 conv (dgrad written to du, wgrad accumulated into dwpw [Cout][Cin]). */
-/*   ws: ocrs_pw_bwd_ws_floats() floats of workspace (per-block partials, deterministic two-stage reduction) or NULL (float atomics). */
+/*   ws: ocrs_pw_bwd_ws_floats() floats of workspace (per-block partials, deterministic two-stage reduction) or NULL (float atomics).  Inside a
+ *   deferral window (ocrs_bwd_defer_begin) kernels 1-3 of ocrs_pw_bwd_kernel queue that reduction until ocrs_bwd_defer_flush -- ws must stay alive
+ *   until then -- except the first of kernel 3's two launches, which share ws; kernel 4 always reduces at once. */
 long ocrs_pw_bwd_ws_floats(int Cin, int Cout, int N, int H, int W);
 int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1,
                 const void* g2, int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw,
@@ -175,6 +177,12 @@ int ocrs_dw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
  * saved_a / gsum_a, saved_b / gsum_b: as ocrs_dw_bwd (nullable). */
 long ocrs_mm_bwd_supported(int Ca, int Cb, int Cout, int dtype); /* 1 / 0 */
 long ocrs_mm_bwd_ws_floats(int Ca, int Cb, int Cout, int N, int H, int W);
+/* nb, the number of per-block partials ONE launch of the block backward leaves in ws (every entry point of this family; 0: unsupported shape).
+ * Partial b is ws[b * ne .. (b + 1) * ne), ne = Cout * Cin + 11 * Cin floats:  [Cout][Cin] dWpw | [Cin][9] dWdw | [Cin][S1 | S2] interleaved, the
+ * launch's share of S1 = sum ghat', S2 = sum ghat' x~ over its pixels (ghat' = dL/dx~ where x~ > 0; defined only when gsum_a / gsum_b ask for sums).  They stay
+ * in ws after the launch and after its reduction.  A 32 | 32 concat input runs as two launches of Cin = 32 (source a, then b): nb is the per-launch
+ * value and the second launch's partials start at float nb * (Cout * 32 + 11 * 32 + 1024) of ws.  two_grads: g2 != NULL. */
+long ocrs_mm_bwd_nparts(int Ca, int Cb, int Cout, int pooled, int two_grads, int N, int H, int W);
 int ocrs_mm_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const float* wpw,
                 const void* g1, const void* g2, int pooled, const void* z, const float* bn, const float* coef, void* gxa, void* gxb, float* dwpw,
                 float* dwdw, float* ws, const float* saved_a, double* gsum_a, const float* saved_b, double* gsum_b, int Cout, int N, int H,

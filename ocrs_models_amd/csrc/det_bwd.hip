@@ -1267,14 +1267,14 @@ static long pw_bwd_route_ws(int route, int Cin, int Cout, int N, int H, int W) {
     switch (route) {
     case 1: return (long)det_pwb_gx(Cin, Cout, N, H, W, 0) * Cin * Cout;  // (the not-pooled grid is the larger one)
     case 2: return det_pw2_ws_floats(Cin, Cout, N, H, W);
-    case 3: return det_pw2_ws_floats(32, Cout, N, H, W);  // (the two launches run one after the other on the same partials)
+    case 3: return det_pw2_ws_floats(32, Cout, N, H, W);  // (the two launches run one after the other on the same partials: the first reduces them at once)
     case 4: return (long)pw_bwd_generic_gx(Cin, Cout, N, H, W) * Cin * Cout;
     }
     return 0;
 }
 
-void det_wgrad_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st) {
-    if (bwd_defer_reduce(ws, nb, nelem, dw, nelem, cin, ldw, nullptr, 0)) return;  // (ocrs_bwd_defer_begin .. _flush: one launch for all of them)
+void det_wgrad_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st, bool may_defer) {
+    if (may_defer && bwd_defer_reduce(ws, nb, nelem, dw, nelem, cin, ldw, nullptr, 0)) return;  // (ocrs_bwd_defer_begin .. _flush: one launch for all of them)
     OCRS_LAUNCH_T(k_wgrad_partials_reduce, dim3((nelem + 31) / 32), dim3(256), 0, st, ws, nb, nelem, dw, cin, ldw);
 }
 
@@ -1364,7 +1364,9 @@ int ocrs_pw_bwd(const void* xa, const void* xb, int Ca, int Cb, const float* tra
         const char* wp = static_cast<const char*>(wpk_d);
         const size_t half_frag_bytes = 2 * 64 * 8 * sizeof(bf16);  // two M tiles of one K chunk
         OCRS_CHECK_ARG(Cout <= 32);
-        int rc = det_pw2_launch(xa, nullptr, 32, 0, tra, nullptr, wdw, g1, g2, pooled, z, bn, coef, wp, du, dwpw, ws, Cout, N, H, W, 64, 64, st);
+        // The two launches share ws: the first one's partials are reduced before the second overwrites them, also inside a deferral window (queued,
+        // both reductions would read the second launch's partials at the flush).
+        int rc = det_pw2_launch(xa, nullptr, 32, 0, tra, nullptr, wdw, g1, g2, pooled, z, bn, coef, wp, du, dwpw, ws, Cout, N, H, W, 64, 64, st, false);
         if (rc != OCRS_OK) return rc;
         return det_pw2_launch(xb, nullptr, 32, 0, trb, nullptr, wdw + 32 * 9, g1, g2, pooled, z, bn, coef, wp + half_frag_bytes,
                               static_cast<bf16*>(du) + 32, dwpw + 32, ws, Cout, N, H, W, 64, 64, st);

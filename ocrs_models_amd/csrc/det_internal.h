@@ -5,7 +5,8 @@
 #include "det_common.h"
 
 // det_bwd.hip: dw[(e / cin) * ldw + e % cin] += sum_b ws[b][e] (k_wgrad_partials_reduce), queued instead while a deferral window is open
-void det_wgrad_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st);
+// (may_defer = false: launched now in any case -- for a workspace that the next launch overwrites)
+void det_wgrad_reduce_launch(const float* ws, int nb, int nelem, float* dw, int cin, int ldw, hipStream_t st, bool may_defer = true);
 
 // det_c1.hip: the first block's row-pair kernels.  supported: whole 64-column segments and row pairs (W % 64 == 0, H % 2 == 0)
 long det_c1v2_supported(int N, int H, int W);
@@ -16,7 +17,7 @@ long det_pw2_supported(int Cin, int Cout, int dtype);
 long det_pw2_ws_floats(int Cin, int Cout, int N, int H, int W);
 int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
                    int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
-                   int H, int W, int ldu, int ldw, hipStream_t st);
+                   int H, int W, int ldu, int ldw, hipStream_t st, bool may_defer = true);
 // det_pwb.hip: deep-level pointwise backward k_pwb.  supported: bf16, Cin in {32 .. 256}, Cout in {64, 128, 256} (Cout >= 64), Cin * 8 >= Cout
 long det_pwb_supported(int Cin, int Cout, int dtype);
 int det_pwb_gx(int Cin, int Cout, int N, int H, int W, int pooled);  // blocks of the launch = workspace slots of Cin * Cout floats

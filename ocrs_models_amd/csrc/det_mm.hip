@@ -870,6 +870,10 @@ static int mm_bwd_launch(const Src2<bf16>& x, const float* tra, const float* trb
 static BwdLast mm_bwd_last(bool want, int Cin, int Ca, double* gsA, double* gsB, const float* svA, const float* svB) {
     return bwd_last(want, Cin, Ca, gsA, gsB, svA, svB, want ? bwd_defer_scratch(bwd_last_doubles(Cin)) : nullptr);  // (no window: the reduce runs in line)
 }
+// per-block partials of ONE launch of mm_bwd_impl over a Cin-channel input (a 32 | 32 concat: Cin = 32, per launch)
+static int mm_bwd_nb(bool rs, int Cin, int Cout, int pooled, int two_grads, int N, int H, int W) {
+    return rs ? rs_bwd_blocks(Cin, Cout, N, H, W, two_grads) : mm_grid(mm_bwd_th(Cin, Cout, pooled ? 1 : 0), N, H, W, pooled ? 1 : 0);
+}
 static void mm_bwd_second_stage(const float* ws, int nb, int Cin, int Cout, int Ca, float* dwpw, int ldw, float* dwdw, double* gsA, double* gsB, const float* svA,
                                 const float* svB, const float* tA, const float* tB, const BwdLast& bl, bool may_defer, hipStream_t st) {
     const int ne = Cout * Cin + 11 * Cin;
@@ -901,6 +905,12 @@ long ocrs_mm_bwd_ws_floats(int Ca, int Cb, int Cout, int N, int H, int W) {
     const long rs = rs_bwd_supported(Ca, Cb, Cout, 0, N, H, W) ? (long)rs_bwd_blocks(Cin, Cout, N, H, W, 0) * (Cout * Cin + 11 * Cin) : 0;  // row-streaming form (det_rs.hip)
     return tiled > rs ? tiled : rs;
 }
+// the number nb of per-block partials one launch of the block backward leaves in ws (0: unsupported shape); see the header for their layout
+long ocrs_mm_bwd_nparts(int Ca, int Cb, int Cout, int pooled, int two_grads, int N, int H, int W) {
+    if (!ocrs_mm_bwd_supported(Ca, Cb, Cout, 1) || H < 2 || W < 2) return 0;
+    const bool split = Ca == 32 && Cb == 32;
+    return mm_bwd_nb(!split && rs_bwd_supported(Ca, Cb, Cout, pooled, N, H, W), split ? 32 : Ca + Cb, Cout, pooled, two_grads, N, H, W);
+}
 
 // Backward of one DepthwiseConv block on the matrix cores (replaces ocrs_pw_bwd + ocrs_dw_bwd [+ ocrs_bn_bwd_reduce of the producers]):
 //   xa | xb (Ca | Cb channels) with load transforms tra | trb: the block input;  wdw [Cin][9], wpw [Cout][Cin]: fp32 master weights;
@@ -931,8 +941,7 @@ static int mm_bwd_impl(const void* xa, const void* xb, int Ca, int Cb, const flo
         double* gsB = split ? nullptr : gsum_b;
         const bool stats = gsA || gsB;
         const bool rs = !split && rs_bwd_supported(Ca, Cb, Cout, pooled, N, H, W);  // the row-streaming kernel (det_rs.hip) covers this launch
-        const int nb = rs ? rs_bwd_blocks(Cin, Cout, N, H, W, g2 != nullptr)
-                          : mm_grid(mm_bwd_th(Cin, Cout, pooled ? 1 : 0), N, H, W, pooled ? 1 : 0);
+        const int nb = mm_bwd_nb(rs, Cin, Cout, pooled, g2 != nullptr, N, H, W);
         const float* wd = wdw + c_off * 9;
         const float* wp = wpw + c_off;
         // deferred second stage (ocrs_bwd_defer_begin): the producers' sums by the last workgroup of the block kernel, the weight-gradient reduce queued

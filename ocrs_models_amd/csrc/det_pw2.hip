@@ -272,7 +272,7 @@ long det_pw2_ws_floats(int Cin, int Cout, int N, int H, int W) { return (long)pw
 
 int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* tra, const float* trb, const float* wdw, const void* g1, const void* g2,
                  int pooled, const void* z, const float* bn, const float* coef, const void* wpk_d, void* du, float* dwpw, float* ws, int Cout, int N,
-                 int H, int W, int ldu, int ldw, hipStream_t st) {
+                 int H, int W, int ldu, int ldw, hipStream_t st, bool may_defer) {
     // ldu / ldw: row strides (elements) of du [P][ldu] and dwpw [Cout][ldw]: Cin for a whole block, larger when this launch handles one
     // half of a concat block's input channels (the caller offsets wdw / wpk_d / du / dwpw to the half)
     const int Cin = Ca + Cb;
@@ -292,7 +292,7 @@ int det_pw2_launch(const void* xa, const void* xb, int Ca, int Cb, const float* 
             pooled != 0);
     });
     if (!hit) return OCRS_ERR_ARG;
-    if (ws) det_wgrad_reduce_launch(ws, nb, Cin * Cout, dwpw, Cin, ldw, st);
+    if (ws) det_wgrad_reduce_launch(ws, nb, Cin * Cout, dwpw, Cin, ldw, st, may_defer);
     OCRS_LAUNCH_CHECK();
     return OCRS_OK;
 }
