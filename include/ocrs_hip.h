@@ -687,6 +687,30 @@ int ocrs_orient_votes(const float* quads, long n, const int* count, float min_as
  * (clamped; 0 steps give 0): the maxima exact, the sum in time order in fp64. */
 int ocrs_path_confidence(const float* log_probs, int T, int B, int C, const int* steps, double* scores, hipStream_t st);
 
+/* ------------------------------------------------------------------ directions --------------- */
+/* Text in mixed directions on one page (csrc/line_dirs.hip; Python: inference/directions.py; restated for the tests in
+ * tests/directions_ref.py): the sideways words of a page are read as the words of a second, virtual page, the page turned by one quarter
+ * turn, through the page-batch path.  Nothing here allocates or synchronises.
+ * ocrs_axis_split: per quad of quads [n][4][2] fp32 the long side L by the crop-frame rule (the longer of c0->c1 and c1->c2; on a tie the one
+ * with the larger |x|; lengths as sqrtf(x * x + y * y), one rounding per operation); the quad is SIDEWAYS iff none of its eight coordinates is
+ * a NaN and |L.y| > |L.x|.  With m = min(count, n) rows (count: optional device int32) of which U are upright: out_quads rows 0 .. U - 1 are
+ * the upright quads as they are, rows U .. m - 1 the sideways quads mapped to the page turned by one quarter turn, (x, y) -> (y, (W-1) - x),
+ * the bits ocrs_turn_quads(k = 1, inverse = 1) gives; both groups in input order (a scan, no atomic counter: equal input gives equal
+ * bytes).  page_of_word [n] = 0 | 1, source_index [n] = the input row of every output row, word_offs [3] = 0, U, m.  Rows from m on are not
+ * written.  16-byte aligned quads and out_quads, which must not overlap.  n == 0 launches nothing (word_offs is then the caller's).  n <= 65536:
+ * the call has no workspace, so every workgroup of 256 rows classifies all rows again -- sized for the words of one page (a few thousand);
+ * more is error 1. */
+int ocrs_axis_split(const float* quads, long n, const int* count, int H, int W, float* out_quads, int* page_of_word, int* word_offs, int* source_index,
+                    hipStream_t st);
+/* batch_out = batch_in, an [n][OH][Wpad] fp32 recognition batch, with every crop i whose flags[i] != 0 (flags NULL: every crop) turned by 180
+ * degrees within its valid width w = clamp(widths[i], 0, Wpad): out[i][y][x] = in[i][OH - 1 - y][w - 1 - x] for x < w; the columns from w on
+ * and the other crops are copied.  An exact permutation of the 4-byte elements.  Any Wpad >= 1 and any 4-byte aligned bases; where Wpad is a
+ * multiple of 4 and batch_out is 16-byte aligned a lane moves 16 bytes, reversed in registers.  batch_out must not overlap batch_in. */
+int ocrs_flip_crops(const float* batch_in, float* batch_out, long n, int OH, int Wpad, const long long* widths, const int* flags, hipStream_t st);
+/* flags[i] = (probe[i] != 0 && s_flip[i] > s_plain[i]) ? 1 : 0 for n crops: the comparison in fp64 and strict, so equal scores and a NaN on
+ * either side give 0; probe is the page of every crop's line (0 = upright, never flipped) or any int32 mask. */
+int ocrs_flip_flags(const double* s_plain, const double* s_flip, const int* probe, long n, int* flags, hipStream_t st);
+
 /* ------------------------------------------------------------------ beam search -------------- */
 /* CTC prefix beam search and forced alignment by the rule of DESIGN.md §18 (csrc/ctc_beam.hip; Python: text.beam_decode_spans,
  * text.ctc_align_spans; restated in tests/beam_ref.py).  Both generalise ctc_greedy_decode_text (datasets/util.py:147-177), the greedy rule:

@@ -181,6 +181,23 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Inclusive scan of one int per lane over the 256 lanes of a workgroup -> (this lane's prefix, the total of all 256).  Used by the line
+// stage (text_lines.hip) and the axis split (line_dirs.hip).
+__device__ __forceinline__ int2 block_scan_256(int v) {
+    __shared__ int s_scan[256];
+    const int t = threadIdx.x;
+    __syncthreads();  // (an earlier call's total may still be read)
+    s_scan[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int add = t >= o ? s_scan[t - o] : 0;
+        __syncthreads();
+        s_scan[t] += add;
+        __syncthreads();
+    }
+    return make_int2(s_scan[t], s_scan[255]);
+}
+
 // Deterministic block-level sum of N per-thread values (all threads of a 256-thread block contribute to the same N outputs): fixed wave
 // shuffle tree -> one LDS slot per (wave, value) -> thread i < N adds the four waves in order.  No atomics: float LDS atomics from several
 // waves onto one address complete in arrival order, which made every statistic that went through them differ in the last bits from run to

@@ -24,6 +24,7 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "crop_frame.h"  // (behind the pragma: long_side() is compiled here with one rounding per operation)
 
 namespace {
 
@@ -106,8 +107,6 @@ __global__ __launch_bounds__(256) void k_turn_half(const uint8_t* __restrict__ s
 }
 
 // ---- quads ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long row_count(const int* __restrict__ count, long n) { return count ? min((long)max(*count, 0), n) : n; }
-
 // one lane = one point.  wm = W - 1, hm = H - 1 as fp32 (exact: both below 2^24).
 __global__ __launch_bounds__(256) void k_turn_quads(const float* __restrict__ quads, long n, const int* __restrict__ count, float wm, float hm, int k, int inverse,
                                                     float* __restrict__ out) {
@@ -125,13 +124,9 @@ __global__ __launch_bounds__(256) void k_turn_quads(const float* __restrict__ qu
 // The long side of a quad by the crop-frame rule (csrc/crop_frame.h: the longer of c0->c1 and c1->c2; on a tie the one with the larger |x|).
 // -> its length if the quad votes (short > 0 and long >= min_aspect * short), else -1; horiz: |L.x| >= |L.y|.
 __device__ __forceinline__ float vote_length(const float* __restrict__ q, float min_aspect, bool& horiz) {
-    const float4 a = reinterpret_cast<const float4*>(q)[0], c = reinterpret_cast<const float4*>(q)[1];
-    const float e1x = a.z - a.x, e1y = a.w - a.y, e2x = c.x - a.z, e2y = c.y - a.w;
-    const float l1 = sqrtf(e1x * e1x + e1y * e1y), l2 = sqrtf(e2x * e2x + e2y * e2y);
-    const bool first = l1 > l2 || (l1 == l2 && fabsf(e1x) >= fabsf(e2x));
-    const float lng = first ? l1 : l2, sht = first ? l2 : l1;
-    horiz = fabsf(first ? e1x : e2x) >= fabsf(first ? e1y : e2y);
-    return (sht > 0.0f && lng >= min_aspect * sht) ? lng : -1.0f;  // (a NaN length fails both comparisons)
+    const LongSide s = long_side(reinterpret_cast<const float4*>(q)[0], reinterpret_cast<const float4*>(q)[1]);
+    horiz = fabsf(s.x) >= fabsf(s.y);
+    return (s.sht > 0.0f && s.lng >= min_aspect * s.sht) ? s.lng : -1.0f;  // (a NaN length fails both comparisons)
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {

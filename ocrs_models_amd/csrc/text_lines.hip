@@ -231,22 +231,6 @@ __global__ __launch_bounds__(kTile) void k_line_order(const float* __restrict__ 
     }
 }
 
-// Inclusive scan of one int per lane over the 256 lanes of a workgroup -> (this lane's prefix, the total of all 256).
-__device__ __forceinline__ int2 block_scan_256(int v) {
-    __shared__ int s_scan[256];
-    const int t = threadIdx.x;
-    __syncthreads();  // (an earlier call's total may still be read)
-    s_scan[t] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int add = t >= o ? s_scan[t - o] : 0;
-        __syncthreads();
-        s_scan[t] += add;
-        __syncthreads();
-    }
-    return make_int2(s_scan[t], s_scan[255]);
-}
-
 // One workgroup: L = number of heads, then line_offsets[0..L] = exclusive scan of the line lengths in line order, 256 at a time.
 __global__ __launch_bounds__(256) void k_line_scan(const int* __restrict__ count, long cap, const int* __restrict__ head, const int* __restrict__ len_sorted,
                                                    int* __restrict__ line_offsets, int* __restrict__ n_lines) {

@@ -1,7 +1,7 @@
 """The reference's evaluation entry point (ocrs_models/eval_detection.py:19-69) on the GPU:
 
     python -m ocrs_models_amd.eval_detection MODEL IMAGE OUT_BASENAME [--rec-model CKPT] [--lines [--reading-order] [--rectify {quad,chain}]] [--chars] [--beam-width N]
-        [--lm FILE [--lm-weight A] [--lm-bonus B]] [--tile TH TW [--tile-overlap VH VW]] [--orientation {auto,0,1,2,3}]
+        [--lm FILE [--lm-weight A] [--lm-bonus B]] [--tile TH TW [--tile-overlap VH VW]] [--orientation {auto,0,1,2,3}] [--directions mixed]
 
 loads a detection checkpoint, runs ``inference.detect_words`` on the image and writes the same four files: ``-input.png`` (the page as the
 model sees it), ``-text-regions.png`` (the page under the text mask), ``-text-probs.png`` and ``-text-words.png`` (the word quads drawn
@@ -23,6 +23,8 @@ shows the tiles' probability maps side by side in their grid.  ``--orientation K
 quarter turns counter-clockwise make it upright, ``auto`` (with ``--rec-model``) lets ``inference.page_orientation`` find K.  The page is turned
 (``inference.turn_page``), detected and read upright -- the pictures show the upright page -- and the JSON objects come back on the page as it
 was given, each with ``"turns"``; the turns are printed to stderr and written to ``-orientation.json`` with the vote and the probe's scores.
+``--directions mixed`` (with ``--lines`` and ``--rec-model``) also reads sideways text on the upright page
+(``read_lines(directions="mixed")``): the JSON objects gain ``"direction"`` and ``"direction_scores"``.
 The image is read and the pictures are written with PIL on the host; that is not a hot path.
 """
 from __future__ import annotations
@@ -93,7 +95,13 @@ def main(argv=None):
     parser.add_argument("--orientation", choices=("auto", "0", "1", "2", "3"), default=None, metavar="K", help="the page is scanned sideways or upside "
                         "down: K in 0..3 quarter turns counter-clockwise make it upright; auto (with --rec-model) finds K from the word quads and "
                         "a recogniser probe.  The JSON objects are on the page as given and gain the turns")
+    parser.add_argument("--directions", choices=("mixed",), default=None, help="with --lines and --rec-model: also read sideways text on the upright "
+                        "page (row headers, axis labels, margin notes); every JSON object gains the line's direction and the probe's two scores")
     args = parser.parse_args(argv)
+    if args.directions is not None and not (args.lines and args.rec_model):
+        parser.error("--directions needs --lines and --rec-model (sideways words are grouped into lines and a recogniser probe decides which way up they read)")
+    if args.directions is not None and args.chars:
+        parser.error("--directions does not go with --chars")
     if args.orientation == "auto" and not args.rec_model:
         parser.error("--orientation auto needs --rec-model (the probe reads the longest words both ways up)")
     if args.reading_order and not args.lines:
@@ -170,7 +178,7 @@ def main(argv=None):
     if args.lines:
         if rec is not None:
             lines = inference.read_lines(rec, page, det["quads"], reading_order=args.reading_order, chars=args.chars, beam_width=args.beam_width, lm=lm,
-                                         rectify=args.rectify)
+                                         rectify=args.rectify, directions=args.directions)
             for line in lines if turns is None else inference.turn_results(lines, turns, *inference.turn_shape(*page_h.shape, turns)):
                 print(json.dumps(line))
             line_quads = [line["quad"] for line in lines]

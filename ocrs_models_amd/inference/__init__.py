@@ -79,6 +79,13 @@ page that was passed (``turn_results``); every dict gains ``"turns"``; the same 
 (``page_orientation``: a vote over the word quads for the axis, ``orientation_votes``, and a recogniser probe of the longest words both ways
 up for the sign, ``path_confidence``; at most three more waits).  None, the default, is today's path unchanged.
 
+Mixed directions (csrc/line_dirs.hip, C ABI section "directions"; restated for the tests in tests/directions_ref.py).  ``orientation``
+turns the whole page; sideways text on an upright page -- row headers, the label of a y axis, a margin note -- is what ``directions="mixed"`` of
+``read_lines`` and ``ocr_lines`` reads: ``split_by_axis`` sends the words whose long side is steeper than 45 degrees to a second, virtual page,
+``turn_page(page, 1)``, both pages go through the page-batch path below, ``line_directions`` probes every sideways line both ways up
+(``flip_crops``, ``path_confidence``, ``flip_flags``) and ``mixed_results`` maps the sideways lines back; every dict gains ``"direction"`` and
+``"direction_scores"``; the same three waits.  None, the default, is today's path unchanged.
+
 Page batches (C ABI section "page batches").  ``ocr_pages`` reads a list of pages of any sizes with ONE detection forward, one
 zero-padded mask canvas, one line stage that keeps to each word's own page, one pooled crop plan and one set of width-sorted recognition chunks
 for the crops of all pages: three host synchronisations for the whole batch (the word offsets, the plan's totals, the labels) instead of three
@@ -89,7 +96,7 @@ runs ``ocr_pages`` over annotated pages and says how many words were found and h
 to annotated words one to one on the device, ``OcrAccuracyStats`` keeps integer counters there across ``update`` calls (no wait) and
 ``result()`` is the one wait.  It consumes the drivers' results and changes none of them.
 
-The package, by stage: ``evaluate`` (the accuracy above), ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops), ``orient`` (page turns and their detection),
+The package, by stage: ``evaluate`` (the accuracy above), ``args`` (argument checks, asynchronous copies), ``detect``, ``tiles``, ``crops``, ``lines`` (lines and reading order), ``chain`` (chain crops), ``orient`` (page turns and their detection), ``directions`` (sideways lines on an upright page),
 ``decode`` (the recogniser, characters, and the ``Decoded`` record every decode is read into), ``assemble`` (record + host lists -> result
 dicts, no GPU) and ``drivers`` (``ocr_page``, ``read_words``, ``read_lines``, ``ocr_lines``, ``ocr_pages``).  Everything is re-exported here.
 """
@@ -101,6 +108,7 @@ from .crops import CropPlan, crop_plan, crops_to_batches, plan_chunks, rectify_c
 from .decode import CharBoxes, CharSpans, Decoded, char_boxes, chars_to_host, decode_crop_spans, recognize_crops, space_label, word_chars  # noqa: F401
 from .detect import (MASK_SIZE, SHRINK_DISTANCE, _cc_quads_pages_sizes, binarize_resize, binarize_resize_pages, cc_quads_pages, detect_words,  # noqa: F401
                      detect_words_batch, expand_quads, gather_page_quads, pack_pages)
+from .directions import AxisSplit, flip_crops, flip_flags, line_directions, mixed_results, split_by_axis, turn_flagged  # noqa: F401
 from .drivers import _read_crops, ocr_lines, ocr_page, ocr_pages, read_lines, read_words  # noqa: F401
 from .evaluate import Matches, OcrAccuracyStats, evaluate_pages, match_words  # noqa: F401
 from .lines import ReadingOrder, TextLines, find_lines, find_lines_pages, page_text, reading_order, split_by_page  # noqa: F401

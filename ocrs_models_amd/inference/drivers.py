@@ -9,7 +9,7 @@ from itertools import accumulate
 import torch
 
 from ..text import DEFAULT_ALPHABET, LMGain
-from . import chain, crops, decode, detect, orient
+from . import chain, crops, decode, detect, directions as dirs, orient
 from . import lines as line_stage
 from .args import _check_pages, _to_host_async
 from .assemble import assemble_results
@@ -88,15 +88,20 @@ def _crop_stages(rectify: str, words: torch.Tensor, lines, output_height: int, c
     return partial(crops.crop_plan, quads, output_height, count), partial(cut_quads, quads), None
 
 
-def _read_quads(rec_model, plan_of, cut, spines, words: torch.Tensor, lines, order, max_batch: int, width_unit: int, alphabet, chars: bool, beam_width, lm):
+def _read_quads(rec_model, plan_of, cut, spines, words: torch.Tensor, lines, order, max_batch: int, width_unit: int, alphabet, chars: bool, beam_width, lm,
+                before_read=None):
     """The tail after detection, once: plan the crops (``plan_of()``), cut them (``cut(plan)``), batch them, read them (``_read_crops``);
     the three first arguments are what ``_crop_stages`` returned.
     -> ``(flat result list, line_page_offs as a host list or None)``: the lines' page offsets are copied ahead of the plan's totals, so they
-    have arrived when those have.  Two host synchronisations: the plan's totals and the labels."""
+    have arrived when those have.  Two host synchronisations: the plan's totals and the labels.  ``before_read(plan, batches) -> batches``
+    (``directions="mixed"``): device work on the batches between the batching and the read; what it copies to the host is queued ahead of
+    the read on the same stream, so it has arrived when the labels have."""
     plan = plan_of()
     lpo_h = None if lines is None or lines.line_page_offs is None else _to_host_async(lines.line_page_offs)
     batches = crops.crops_to_batches(cut(plan), plan, max_batch, width_unit)
     lpo = None if lpo_h is None else lpo_h.tolist()
+    if before_read is not None:
+        batches = before_read(plan, batches)
     return _read_crops(rec_model, batches, alphabet, words, lines, plan.host()[0], order, lpo, plan if chars else None, beam_width, lm, spines), lpo
 
 
@@ -143,10 +148,45 @@ def ocr_page(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE,
     return read_words(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, chars, beam_width, lm, orientation)
 
 
+def _read_lines_mixed(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int, max_batch: int, width_unit: int, alphabet, max_gap: float,
+                      min_cos: float, reading_order: bool, block_gap: float, beam_width, lm, rectify: str) -> list[dict]:
+    """``read_lines(directions="mixed")``: the page as a batch of two virtual pages -- the upright words on the page, the
+    sideways words on ``turn_page(page, 1)`` (``split_by_axis``) -- through ``find_lines_pages``, ``reading_order``, one page store, one plan
+    and one set of chunks, as ``ocr_pages`` runs them (``_read_quads``); between the batching and the read the probe of page 1's crops
+    (``line_directions``) and the flagged crops turned (``turn_flagged``); then ``mixed_results``.  The flags, the scores and the reading
+    order are copied to the host ahead of the final read on the same stream: the two waits of ``read_lines`` (the plan's totals and the
+    labels)."""
+    orient._check_turn_page(page_u8, "read_lines")
+    page = page_u8 if page_u8.dim() == 3 else page_u8[None]  # (the page store takes (1,H,W) pages)
+    H, W = (int(v) for v in page.shape[-2:])
+    split = dirs.split_by_axis(quads, H, W)
+    found = line_stage.find_lines_pages(split.quads, split.page_of_word, split.word_offs, max_gap, min_cos)
+    order = line_stage.reading_order(found, block_gap) if reading_order else None
+    store = detect.pack_pages([page, orient.turn_page(page, 1)])
+    stages = _crop_stages(rectify, split.quads, found, output_height, lambda q, plan: crops.rectify_crops_pages(*store, q, found.page_of_line, plan),
+                          lambda sp, plan: chain.rectify_chain_pages(*store, sp, found.page_of_line, plan))
+    probed = {}
+
+    def probe_and_turn(plan, batches):
+        imgs, image_widths, perm = batches
+        n_lines = plan.host()[0]
+        probe = found.page_of_line.index_select(0, plan.table[:n_lines, 7].long())  # the page of every crop's line, in the batches' order
+        flags, scores = dirs.line_directions(rec_model, imgs, image_widths, probe)
+        final = dirs.turn_flagged(imgs, image_widths, flags)
+        probed.update(flags=_to_host_async(flags), scores=_to_host_async(scores), perm=perm, n=n_lines,
+                      line_at=None if order is None else _to_host_async(order.line_order))
+        return final, image_widths, perm
+
+    flat, lpo = _read_quads(rec_model, *stages, split.quads, found, order, max_batch, width_unit, alphabet, False, beam_width, lm, probe_and_turn)
+    flags, scores, perm, n_lines = probed["flags"].tolist(), probed["scores"].tolist(), probed["perm"], probed["n"]
+    line_at = list(range(n_lines)) if probed["line_at"] is None else probed["line_at"][:n_lines].tolist()
+    return dirs.mixed_results(flat, lpo, line_at, [flags[p] for p in perm], [scores[p] for p in perm], H, W)
+
+
 def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_height: int = 64, max_batch: int = 256, width_unit: int = 64,
                alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0, min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0,
                chars: bool = False, beam_width: int | None = None, lm: LMGain | None = None, rectify: str = "quad",
-               orientation: int | None = None) -> list[dict]:
+               orientation: int | None = None, directions: str | None = None) -> list[dict]:
     """The half of ``ocr_lines`` after detection: word quads (N,4,2), N > 0, on the device -> the list ``ocr_lines`` returns.  Two host
     synchronisations: the plan's totals (which bring the line count) and the labels; the line table and the quads are copied to the host
     ahead of the recogniser on the same stream, so they have arrived when the labels have -- and so has the reading order, which with
@@ -162,10 +202,20 @@ def read_lines(rec_model, page_u8: torch.Tensor, quads: torch.Tensor, output_hei
     words as ``[x, y]`` lists: the mid-points of each word's left and right edge, in chain order) and ``"height"`` (the crop's height on the
     page); with ``chars`` the character quads follow the spine; the same waits.  Any other value is an argument error.
     ``orientation``: as in ``read_words`` -- the page and the quads are the upright page's, an int k maps the results back to
-    the page that ``turn_page(.., k)`` made it from; the mapped keys are ``"quad"``, ``"words"``, ``"char_quads"`` and ``"spine"``."""
+    the page that ``turn_page(.., k)`` made it from; the mapped keys are ``"quad"``, ``"words"``, ``"char_quads"`` and ``"spine"``.
+    ``directions``: None, the default, is the path above unchanged.  ``"mixed"`` also reads sideways text: the words whose
+    long side is steeper than 45 degrees are grouped and read on ``turn_page(page, 1)``, a recogniser probe decides per sideways line which
+    way up it reads, and the result is one flat list -- the upright lines, then the sideways ones, each group in its line (or reading)
+    order -- on the page that was passed.  Every dict gains ``"direction"`` (the quarter turns counter-clockwise that make the line upright:
+    0, or 1 / 3 for a sideways line that reads downwards / upwards) and ``"direction_scores"`` (``[S_plain, S_flip]`` of the probe, None for
+    upright lines) in front of ``"block"``; three recogniser forwards instead of one; the same two waits.  With ``chars=True`` it is an
+    argument error, and so is any other value.  ``orientation`` composes from outside: the directions are those of the upright page."""
     decode._check_lm_args("read_lines", beam_width, lm)
     _check_rectify("read_lines", rectify)
     _check_upright_turns("read_lines", orientation)
+    if dirs._check_directions("read_lines", directions, chars) is not None:
+        return _turned_back(_read_lines_mixed(rec_model, page_u8, quads, output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order,
+                                              block_gap, beam_width, lm, rectify), page_u8, orientation)
     found = line_stage.find_lines(quads, None, max_gap, min_cos)
     order = line_stage.reading_order(found, block_gap) if reading_order else None
     stages = _crop_stages(rectify, quads, found, output_height, partial(crops.rectify_crops, page_u8), partial(chain.rectify_chain, page_u8))
@@ -176,7 +226,7 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE
               output_height: int = 64, max_batch: int = 256, width_unit: int = 64, alphabet=DEFAULT_ALPHABET, max_gap: float = 2.0,
               min_cos: float = 0.9, reading_order: bool = False, block_gap: float = 1.0, chars: bool = False,
               beam_width: int | None = None, lm: LMGain | None = None, tile=None, overlap=None, tile_batch: int = 16,
-              rectify: str = "quad", orientation=None) -> list[dict]:
+              rectify: str = "quad", orientation=None, directions: str | None = None) -> list[dict]:
     """Page (1,H,W) uint8 on the device -> ``[{"quad": line quad, "text": str, "words": [word quads in chain order]}, ...]`` in line order:
     ``detect_words``, ``find_lines``, then one crop per LINE through the stages ``ocr_page`` runs per word.  The same three host
     synchronisations as ``ocr_page``: the component count, the plan's totals and the labels (``read_lines``).  A page without components
@@ -189,9 +239,12 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE
     tiles, as ``detect_words`` describes; still three waits.  ``rectify`` (DESIGN.md §21): ``"quad"`` or ``"chain"``, as in ``read_lines``;
     still three waits.  ``orientation``: None, an int 0..3 or ``"auto"``, as in ``ocr_page``: the page is turned upright, read as
     it always is, and ``"quad"``, ``"words"``, ``"char_quads"`` and ``"spine"`` are mapped back to the page that was passed; every dict gains
-    ``"turns"``; still three waits for an int, at most three more (and the second detection's) for ``"auto"``."""
+    ``"turns"``; still three waits for an int, at most three more (and the second detection's) for ``"auto"``.  ``directions`` (DESIGN.md
+    §24): None or ``"mixed"``, as in ``read_lines``: sideways words become lines of their own, read the right way up, every dict gains
+    ``"direction"`` and ``"direction_scores"``; still three waits; not with ``chars=True``."""
     decode._check_lm_args("ocr_lines", beam_width, lm)
     _check_rectify("ocr_lines", rectify)
+    dirs._check_directions("ocr_lines", directions, chars)
     det = None
     if orient._check_orientation("ocr_lines", orientation) is not None:
         probe = dict(size=size, threshold=threshold, expand=expand, output_height=output_height, max_batch=max_batch, width_unit=width_unit, tile=tile,
@@ -202,7 +255,7 @@ def ocr_lines(det_model, rec_model, page_u8: torch.Tensor, size=detect.MASK_SIZE
     if det["n"] == 0:
         return []
     return read_lines(rec_model, page_u8, det["quads"], output_height, max_batch, width_unit, alphabet, max_gap, min_cos, reading_order, block_gap, chars,
-                      beam_width, lm, rectify, orientation)
+                      beam_width, lm, rectify, orientation, directions)
 
 
 def ocr_pages(det_model, rec_model, pages, lines: bool = True, size=detect.MASK_SIZE, threshold: float = 0.5, expand: float = detect.SHRINK_DISTANCE,
